@@ -15,7 +15,13 @@ tensor-parallel over the N GPUs with RCCL all-reduces inside the decode hipGraph
 (Qwen2-7B at TP 8 uses uneven q-head shards with kv-head replication); "scaling":
 "strong".  `--parallel replicas`: N independent batch-1 replicas ("weak").
 
-JSON extras: "roofline" for the dominant kernel (gate/up GEMV, timed live with hipEvents on
+A plain run does only what the headline needs: engine + synthetic weights, prefill (one
+warm pass, --prefill-iters timed), --warmup decode steps, --steps timed steps, then the
+JSON line ("ms_per_step" = the timed interval / --steps).  `--dump-outputs DIR` also writes
+what the timed steps computed (DIR/token_ids.npy, DIR/logits.npy).  Everything below runs
+only with `--full`.
+
+JSON extras (--full): "roofline" for the dominant kernel (gate/up GEMV, timed live with hipEvents on
 the engine stream, launches cycling over layers 1..L-1 as the step does), "step_roofline"
 for the whole decode step, "cpu_baseline" (the naive C++ oracle forward over the same
 synthetic weights on host cores, rank 0 / N = 1) with the BASELINE config-1 CPU run and a
@@ -61,7 +67,16 @@ def parse(argv=None):
     ap.add_argument("--prefill-single", action="store_true",
                     help="B > 1: prefill the B prompts one qie_prefill call each (default: one batched pass)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything else this benchmark measures: live per-kernel "
+                         "timing and the roofline of the dominant kernel, the other BASELINE configs (2 and 4; "
+                         "config 5 at N > 1), the CPU baseline and the full-depth GPU-vs-oracle parity sample "
+                         "(minutes). Without it only the headline is set up, warmed up, timed and printed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed as DIR/<name>.npy: token_ids (float64 "
+                         "[steps][B], the greedy id of every timed step) and logits (float32 [B][V], the last timed "
+                         "step's). Same arguments, same inputs: two builds can be compared output for output")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline / parity leg")
     ap.add_argument("--cpu-prompt", type=int, default=16)
     ap.add_argument("--cpu-decode", type=int, default=8)
     ap.add_argument("--cpu-full", action="store_true",
@@ -83,7 +98,7 @@ def parse(argv=None):
     ap.add_argument("--c5-steps", type=int, default=64,
                     help="N > 1 (tensor-parallel): timed decode steps of the Qwen2-72B config-5 line")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the other single-GPU BASELINE configs (2 and 4) in the default line")
+                    help="--full: skip the other BASELINE configs (2 and 4; config 5 at N > 1)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher only: print the child ranks' environments as JSON and exit (no GPU)")
     return ap.parse_args(argv)
@@ -230,18 +245,9 @@ def run(a):
     value = groups * B * a.steps / dt
     prefill_tok_s = groups * B * P / t_prefill
 
-    # ---------------- per-kernel live timing (hipEvents on the engine stream; weight
-    # kernels cycle through layers 1..L-1 so no layer's weights are replayed from cache)
-    kern = {}
-    for which, name in [(0, "gate_up_gemv"), (1, "down_gemv"), (2, "qkv_gemv"), (3, "o_gemv"),
-                        (4, "lm_head_gemv"), (5, "attention")]:
-        us, by = batch.time_kernel(which, 54)
-        kern[name] = {"avg_us": round(us, 3), "bytes": by, "GBps": round(by / us / 1e3, 1)}
-    dom = kern["gate_up_gemv"]
-    # PMC summaries exist for the headline (bf16, B = 1) and config 4 (fp8, B = 8) shapes
-    pmc_tag = ("" if B == 1 and not a.fp8 else "fp8_b8_" if B == 8 and a.fp8 else None) \
-        if spec.name == "Qwen2-7B" and tp == 1 else None
-    traffic, traffic_src = pmc_traffic("gate_up", pmc_tag) if pmc_tag is not None else (None, None)
+    if a.dump_outputs:   # every rank makes the calls (logits are collective under TP); rank 0 writes
+        dump_outputs(a.dump_outputs if rank == 0 else None, batch, B, P, a.steps)
+
     avg_ctx = P + (a.steps + 1) / 2.0
     step_bytes = spec.decode_weight_bytes(fp8=a.fp8) + B * spec.kv_bytes_per_position() * avg_ctx
     step_gbs = step_bytes / (ms_step * 1e-3) / 1e9 / tp   # per GPU (TP: each streams ~1/tp of the weights)
@@ -270,20 +276,37 @@ def run(a):
         "prefill_mode": "batched" if B > 1 and not a.prefill_single else "per-sequence",
         # whole-job prefill TFLOP/s (all groups' prompts; TP ranks compute one prompt together)
         "prefill_tflops_job": round(groups * spec.prefill_flops(P, B) / t_prefill / 1e12, 1),
-        "roofline": {"bound": "hbm", "kernel": "gate_up_gemv (rms + gate/up GEMV + SwiGLU, layers 1..L-1)",
-                     "achieved": dom["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(dom["GBps"] / HBM_PEAK_GBS, 4), "traffic": traffic,
-                     "stream_peak": round(STREAM_GATE_UP_GBS, 1),
-                     "frac_vs_stream": round(dom["GBps"] / STREAM_GATE_UP_GBS, 4), "stream_source": STREAM_SRC,
-                     "algorithmic_bytes": dom["bytes"], "traffic_source": traffic_src},
         "step_roofline": {"bytes_per_step": step_bytes, "achieved_GBps_per_gpu": round(step_gbs, 1),
                           "frac": round(step_gbs / HBM_PEAK_GBS, 4),
                           "roofline_tok_s": round(HBM_PEAK_GBS * 1e9 * tp / step_bytes * B * (world // tp), 1)},
-        "kernels": kern,
-        "cpu_baseline": None,
+        "full": a.full,
     }
+    if a.dump_outputs:
+        out["outputs"] = {"dir": a.dump_outputs, "names": ["token_ids", "logits"]}
     if tp_note:
         out["note"] = tp_note
+    if a.full:
+        # ---------------- per-kernel live timing (hipEvents on the engine stream; weight
+        # kernels cycle through layers 1..L-1 so no layer's weights are replayed from cache)
+        kern = {}
+        for which, name in [(0, "gate_up_gemv"), (1, "down_gemv"), (2, "qkv_gemv"), (3, "o_gemv"),
+                            (4, "lm_head_gemv"), (5, "attention")]:
+            us, by = batch.time_kernel(which, 54)
+            kern[name] = {"avg_us": round(us, 3), "bytes": by, "GBps": round(by / us / 1e3, 1)}
+        dom = kern["gate_up_gemv"]
+        # PMC summaries exist for the headline (bf16, B = 1) and config 4 (fp8, B = 8) shapes
+        pmc_tag = ("" if B == 1 and not a.fp8 else "fp8_b8_" if B == 8 and a.fp8 else None) \
+            if spec.name == "Qwen2-7B" and tp == 1 else None
+        traffic, traffic_src = pmc_traffic("gate_up", pmc_tag) if pmc_tag is not None else (None, None)
+        out["roofline"] = {"bound": "hbm", "kernel": "gate_up_gemv (rms + gate/up GEMV + SwiGLU, layers 1..L-1)",
+                           "achieved": dom["GBps"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": round(dom["GBps"] / HBM_PEAK_GBS, 4), "traffic": traffic,
+                           "stream_peak": round(STREAM_GATE_UP_GBS, 1),
+                           "frac_vs_stream": round(dom["GBps"] / STREAM_GATE_UP_GBS, 4),
+                           "stream_source": STREAM_SRC,
+                           "algorithmic_bytes": dom["bytes"], "traffic_source": traffic_src}
+        out["kernels"] = kern
+        out["cpu_baseline"] = None
     if comm is not None and a.comm == "peer":   # a timed-out exchange must not yield a number
         errs = group.allgather(comm.peer_error())
         out["config"]["peer_error_words"] = errs
@@ -293,11 +316,11 @@ def run(a):
             return 4
     headline = (spec.name == "Qwen2-7B" and B == 1 and P == 2048 and not a.fp8 and not a.page_tokens
                 and world == 1 and not a.no_graph)
-    if rank == 0 and headline and not a.no_configs:
+    if a.full and rank == 0 and headline and not a.no_configs:
         out["configs"] = other_configs(Q, S, W)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not a.fp8 and B == 1:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not a.fp8 and B == 1:
         out["cpu_baseline"] = cpu_baseline(spec, a, batch, eng)
-    if comm is not None and not a.no_configs:   # BASELINE configs[4]: the 72B curve, every rank
+    if a.full and comm is not None and not a.no_configs:   # BASELINE configs[4]: the 72B curve, every rank
         batch.close()
         eng.close()
         out["configs"] = {"config5": config5(Q, S, W, a, comm, group, rank, local)}
@@ -309,8 +332,27 @@ def run(a):
     return 0
 
 
-# BASELINE.json configs[1] and configs[3]: the other single-GPU configurations, timed by the
-# driver's own default bench run (one engine each, after the headline)
+def dump_outputs(out_dir, batch, B, P, steps):
+    """What a caller of the timed decode receives, read back after it (the timed call itself
+    is unchanged): the greedy token of every timed step, from each sequence's history row
+    (positions P+1 .. P+steps; P holds the prefill's token), and the last step's logits
+    (bf16 widened to float32, exact).  Qwen2-7B at B = 1: 511 ids + 152,064 logits, < 1 MB.
+    out_dir None: make the calls, write nothing (ranks > 0)."""
+    ids = np.stack([batch.history(s, P + steps + 1)[P + 1:] for s in range(B)], axis=1).astype(np.float64)
+    logits = (batch.logits().astype(np.uint32) << 16).view(np.float32)
+    if out_dir is None:
+        return
+    budget = 64_000_000 - ids.nbytes
+    if logits.nbytes > budget:   # a large batch: a fixed, seeded sample of the vocabulary columns
+        cols = np.sort(np.random.default_rng(0).choice(logits.shape[1], budget // (4 * B), replace=False))
+        logits = np.ascontiguousarray(logits[:, cols])
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "token_ids.npy"), ids)
+    np.save(os.path.join(out_dir, "logits.npy"), logits)
+
+
+# BASELINE.json configs[1] and configs[3]: the other single-GPU configurations, timed by
+# `--full` (one engine each, after the headline)
 OTHER_CONFIGS = [
     {"key": "config2", "model": "Qwen2-0.5B", "batch": 1, "prompt": 128, "gen": 128, "fp8": False,
      "workload": "Qwen2-0.5B bf16, batch=1, prompt=128, gen=128 (BASELINE configs[1])"},

@@ -14,6 +14,8 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 from conftest import ROOT
 
 from qwen_inference_engine_amd import spec as S
@@ -78,6 +80,42 @@ def test_tp_shardable_presets():
     assert [S.shard_heads(28, 4, 8, r)[0] for r in range(8)] == [4, 3, 4, 3, 4, 3, 4, 3]
     assert S.shard_heads(28, 4, 32, 0) is None       # 8 ranks per kv head > its 7 q heads
     assert S.shard_heads(28, 4, 6, 0) is None        # 6 neither divides nor is a multiple of 4
+
+
+class _FakeBatch:
+    """history / logits of a batch after P prompt tokens + the prefill's token + `steps` decode steps."""
+
+    def __init__(self, B, V, P, steps):
+        self.B, self.V, self.P, self.steps = B, V, P, steps
+
+    def history(self, s, n):
+        assert n == self.P + self.steps + 1
+        return (np.arange(n, dtype=np.int32) + 1000 * s)
+
+    def logits(self):
+        return (np.arange(self.B * self.V, dtype=np.uint32) % 65521).astype(np.uint16).reshape(self.B, self.V)
+
+
+def test_dump_outputs_window_dtypes_and_size_cap(tmp_path):
+    """--dump-outputs: token_ids = the timed steps' ids (history positions P+1 .. P+steps) as
+    float64 [steps][B]; logits = the bf16 rows widened exactly to float32; above 64 MB the
+    logits become a fixed, seeded sample of columns (the same columns on every run)."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse([]).full is False and bench.parse(["--full"]).full is True
+    assert bench.parse(["--dump-outputs", "d"]).dump_outputs == "d" and bench.parse([]).dump_outputs is None
+    fb = _FakeBatch(2, 1000, 5, 3)
+    bench.dump_outputs(str(tmp_path / "a"), fb, 2, 5, 3)
+    ids, lg = np.load(tmp_path / "a" / "token_ids.npy"), np.load(tmp_path / "a" / "logits.npy")
+    assert ids.dtype == np.float64 and ids.tolist() == [[6, 1006], [7, 1007], [8, 1008]]
+    assert lg.dtype == np.float32 and np.array_equal(lg.view(np.uint32), fb.logits().astype(np.uint32) << 16)
+    big = _FakeBatch(128, 152064, 5, 3)                     # 77.9 MB of float32 logits
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), big, 128, 5, 3)
+    lb, lc = np.load(tmp_path / "b" / "logits.npy"), np.load(tmp_path / "c" / "logits.npy")
+    assert lb.shape == (128, (64_000_000 - 3 * 128 * 8) // (128 * 4)) and lb.nbytes + 3 * 128 * 8 <= 64_000_000
+    assert np.array_equal(lb.view(np.uint32), lc.view(np.uint32))
+    bench.dump_outputs(None, fb, 2, 5, 3)                   # ranks > 0: calls made, nothing written
 
 
 def test_pmc_traffic_is_read_from_the_benched_configuration():

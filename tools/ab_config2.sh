@@ -10,8 +10,9 @@ OUT=gpurun_out/r05_ab_config2.jsonl
 : > $OUT
 for round in 1 2 3; do
   for tree in _ab/r03 .; do
+    full=--full; [ $tree = _ab/r03 ] && full=   # the round-3 bench has no --full (it always ran the kernel timings)
     for args in "--steps 127 --warmup 8" "--steps 511 --warmup 16"; do
-      line=$(cd $tree && timeout -k 10 120 python bench.py --model Qwen2-0.5B --prompt 128 --gen 128 $args \
+      line=$(cd $tree && timeout -k 10 120 python bench.py $full --model Qwen2-0.5B --prompt 128 --gen 128 $args \
              --no-cpu-baseline 2>/dev/null | tail -1)
       rc=$?
       [ $rc -eq 0 ] || { echo "bench failed rc=$rc ($tree)"; exit $rc; }

@@ -14,15 +14,17 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_ou
 rc=$?; tail -2 gpurun_out/smoke.log; echo "smoke rc=$rc"
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
 [ "${SKIP_BENCH:-0}" = "1" ] && exit 0
-timeout -k 10 ${BENCH_TIMEOUT:-600} python bench.py ${BENCH_ARGS:-} > gpurun_out/bench.log 2>&1
-rc=$?; tail -3 gpurun_out/bench.log; echo "bench rc=$rc"
+# the bench line (--full) and the profile go to $QIE_OUT (default bench_out/, relative to the repository root)
+R=$PWD; O=$R/${QIE_OUT:-bench_out}; mkdir -p "$O"
+timeout -k 10 ${BENCH_TIMEOUT:-600} python bench.py --full ${BENCH_ARGS:-} > "$O/bench.log" 2>&1
+rc=$?; tail -3 "$O/bench.log"; echo "bench rc=$rc"
 [ $rc -eq 0 ] || exit $rc
 if [ "${PROFILE:-0}" = "1" ]; then
   cd /tmp && export TMPDIR=/tmp
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$GRAFT_REPO_ROOT/gpurun_out/prof" \
-      -o run -- python3 "$GRAFT_REPO_ROOT/bench.py" --steps 64 --warmup 4 --prefill-iters 1 --no-cpu-baseline ${PROF_ARGS:-} \
-      > "$GRAFT_REPO_ROOT/gpurun_out/prof.log" 2>&1
-  rc=$?; echo "rocprof rc=$rc"; cd "$GRAFT_REPO_ROOT"
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" \
+      -o run -- python3 "$R/bench.py" --full --steps 64 --warmup 4 --prefill-iters 1 --no-cpu-baseline ${PROF_ARGS:-} \
+      > "$O/prof.log" 2>&1
+  rc=$?; echo "rocprof rc=$rc"; cd "$R"
   [ $rc -eq 0 ] || exit $rc
 fi
 if [ "${PMC:-0}" = "1" ]; then

@@ -9,5 +9,5 @@ timeout -k 10 700 python3 -u -m pytest tests/test_gpu_ops.py tests/test_gpu_head
 rc=$?; tail -3 $OUT/tests.log; echo "tests rc=$rc"; [ $rc -eq 0 ] || exit $rc
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/$OUT/prof" -o run \
-    -- python3 "$R/bench.py" --steps 16 --warmup 4 --prefill-iters 2 --no-cpu-baseline --no-configs > "$R/$OUT/prof.log" 2>&1
+    -- python3 "$R/bench.py" --full --steps 16 --warmup 4 --prefill-iters 2 --no-cpu-baseline --no-configs > "$R/$OUT/prof.log" 2>&1
 rc=$?; echo "rocprof rc=$rc"; exit $rc

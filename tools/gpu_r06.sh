@@ -61,7 +61,7 @@ fi
 if on peer; then
   timeout -k 10 600 python -u -m pytest tests/test_gpu_tp.py -k "peer" -x -v --timeout 300 --timeout-method thread \
     > $OUT/peer_tests.log 2>&1; rc=$?; tail -3 $OUT/peer_tests.log; [ $rc -eq 0 ] || exit $rc
-  QIE_BENCH_ONE_DEVICE=1 timeout -k 10 900 python -u bench.py --gpus 2 --comm peer --no-cpu-baseline \
+  QIE_BENCH_ONE_DEVICE=1 timeout -k 10 900 python -u bench.py --full --gpus 2 --comm peer --no-cpu-baseline \
     > $OUT/tp2.json 2> $OUT/tp2.err; rc=$?; echo "tp2 rc=$rc"; exit $rc
 fi
 exit 0

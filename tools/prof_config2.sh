@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 mkdir -p "$R/gpurun_out"
 cd /tmp && export TMPDIR=/tmp
 for tree in ${TREES:-cur}; do   # the round-3 tree segfaults on the host under rocprofv3 (launch_step)
-  src=$R; extra=--no-configs
+  src=$R; extra="--full --no-configs"
   [ $tree = r03 ] && { src=$R/_ab/r03; extra=; }   # the round-3 bench has no config lines
   timeout -k 10 240 rocprofv3 --kernel-trace --output-format csv -d "$R/gpurun_out/prof_c2_$tree" -o run \
       -- python3 "$src/bench.py" --model Qwen2-0.5B --prompt 128 --gen 128 --steps 127 --warmup 8 \

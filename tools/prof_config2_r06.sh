@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 mkdir -p "$R/gpurun_out"
 cd /tmp && export TMPDIR=/tmp
 for tree in ${TREES:-r03 cur}; do
-  src=$R; extra=--no-configs
+  src=$R; extra="--full --no-configs"
   [ $tree = r03 ] && { src=$R/_ab/r03; extra=; }
   timeout -k 10 240 rocprofv3 --kernel-trace --output-format csv -d "$R/gpurun_out/prof_c2g_$tree" -o run \
       -- python3 "$src/bench.py" --model Qwen2-0.5B --prompt 128 --gen 128 --steps 64 --warmup 4 \

@@ -136,12 +136,12 @@ def in_graph_decode(trace):
     return out
 
 
-HEADLINE = ("`rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 64 --warmup 4 "
+HEADLINE = ("`rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 64 --warmup 4 "
             "--prefill-iters 1 --no-cpu-baseline --no-configs` (Qwen2-7B bf16, batch 1, prompt 2048; prefill x2 + 4 "
             "warm-up + 64 timed hipGraph decode steps + bench's live kernel timings).")
 
 
-def main(tag="r01", src="gpurun_out/prof", desc=HEADLINE, how="tools/gpu_check.sh PROFILE=1"):
+def main(tag="r01", src="bench_out/prof", desc=HEADLINE, how="tools/gpu_check.sh PROFILE=1"):
     src = os.path.join(ROOT, src)
     trace = list(csv.DictReader(open(os.path.join(src, "run_kernel_trace.csv"))))
     groups = collections.defaultdict(list)

@@ -14,11 +14,11 @@ if on 1; then bash tools/prof_config2.sh || exit $?; fi
 if on 2; then
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/gpurun_out/prof" -o run \
-      -- python3 "$R/bench.py" --steps 64 --warmup 4 --prefill-iters 1 --no-cpu-baseline --no-configs \
+      -- python3 "$R/bench.py" --full --steps 64 --warmup 4 --prefill-iters 1 --no-cpu-baseline --no-configs \
       > "$R/gpurun_out/prof.log" 2>&1
   rc=$?; echo "rocprof headline rc=$rc"; [ $rc -eq 0 ] || exit $rc
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$R/gpurun_out/prof_cfg4" -o run \
-      -- python3 "$R/bench.py" --steps 64 --warmup 4 --prefill-iters 1 --no-cpu-baseline --no-configs \
+      -- python3 "$R/bench.py" --full --steps 64 --warmup 4 --prefill-iters 1 --no-cpu-baseline --no-configs \
       --batch 8 --fp8 --prompt 1024 --gen 256 --page-tokens 128 > "$R/gpurun_out/prof_cfg4.log" 2>&1
   rc=$?; echo "rocprof config4 rc=$rc"; [ $rc -eq 0 ] || exit $rc
   cd "$R"
