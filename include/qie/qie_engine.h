@@ -178,6 +178,20 @@ int qie_prefill(qie_batch* b, int32_t seq, const int32_t* ids, int32_t n, const 
  * or NULL.  Paged batches: all-or-nothing on the pool, as qie_prefill. */
 int qie_prefill_batch(qie_batch* b, int32_t seq0, int32_t n_seqs, const int32_t* ids, int32_t len,
                       const qie_sampling* s, int32_t* next_ids);
+/* Extends live sequence `seq`: n ids (host) at positions pos0 .. pos0+n-1, attending to the
+ * cached rows [0, pos0) and to each other causally; writes their KV rows, samples the next
+ * token from the last row (host *next_id, may be NULL) and makes it the current token at
+ * position pos0 + n.  1 <= pos0 <= the sequence's current position: rows >= pos0 (a pending
+ * current token, rows written by decode steps since) are overwritten, as with
+ * qie_batch_set_position.  The sequence's pages are kept and grown.  The sampling step
+ * counter restarts as after a fresh qie_prefill (the sampled token is step 0's).
+ * All-or-nothing: bad arguments, an idle or released slot, pos0 above the current position
+ * and pos0 + n >= max_ctx return -22, a page pool that cannot hold the new rows returns -28,
+ * both before anything is launched — the sequence continues as if the call had not been
+ * made.  Engines created with prefill_fp8 return -22: their block-scaled activation
+ * numerics are defined for a prefill from position 0 only. */
+int qie_prefill_append(qie_batch* b, int32_t seq, const int32_t* ids, int32_t n, int32_t pos0,
+                       const qie_sampling* s, int32_t* next_id);
 /* One decode step for all B sequences (hipGraph replay when enabled);
  * next_ids: host [B] or NULL (then nothing is synchronised). */
 int qie_decode_step(qie_batch* b, const qie_sampling* s, int32_t* next_ids);

@@ -153,6 +153,23 @@ int qie_attention(const void* q, int64_t M, const int32_t* pos, int32_t rows_per
                   const qie_kv_cache* cache, int32_t layer, int32_t n_heads, void* out,
                   void* ws, void* stream);
 
+/* qie_attention's contract (row m attends to [0, pos[m]] of sequence m / rows_per_seq,
+ * positions non-decreasing within a sequence, the rows' own K/V already in the cache) for
+ * a block of new rows over a long cached prefix: an MFMA kernel with one workgroup per
+ * (sequence, kv head, key split, block of 128 flattened (token, head-in-group) rows), so
+ * K/V bytes are read once per (kv head, split, row block); fp32 partials in ws, merged by
+ * a second launch (none, and no ws, when the cache has a single split).  head_dim 64 or
+ * 128, any rows_per_seq >= 1, contiguous and paged caches; never synchronises or allocates.
+ * ws must hold qie_attention_extend_workspace_bytes() and need not be initialised.
+ * qie_attention_extend_split_tokens: the keys per split (a multiple of 64) of a call of M
+ * rows on a cache of max_ctx keys. */
+int64_t qie_attention_extend_workspace_bytes(int64_t M, int32_t n_heads, int32_t head_dim,
+                                             int32_t max_ctx);
+int32_t qie_attention_extend_split_tokens(int64_t M, int32_t max_ctx);
+int qie_attention_extend(const void* q, int64_t M, const int32_t* pos, int32_t rows_per_seq,
+                         const qie_kv_cache* cache, int32_t layer, int32_t n_heads, void* out,
+                         void* ws, void* stream);
+
 /* Decode attention with the q/k post-projection fused in (one launch per layer):
  * qkv rows [B][(nq + 2 nkv) hd] straight from the QKV projection; applies qk-norm
  * (q_norm/k_norm non-NULL) and RoPE at pos[m] to q and to the new k, appends the

@@ -112,6 +112,9 @@ SIGNATURES = [
                                _I32, _F, _I32, _P, _P]),
     ("qie_attention_workspace_bytes", C.c_int64, [_I64, _I32, _I32, _I32]),
     ("qie_attention", C.c_int, [_P, _I64, _P, _I32, C.POINTER(KvCacheC), _I32, _I32, _P, _P, _P]),
+    ("qie_attention_extend_workspace_bytes", C.c_int64, [_I64, _I32, _I32, _I32]),
+    ("qie_attention_extend_split_tokens", C.c_int32, [_I64, _I32]),
+    ("qie_attention_extend", C.c_int, [_P, _I64, _P, _I32, C.POINTER(KvCacheC), _I32, _I32, _P, _P, _P]),
     ("qie_attention_decode_workspace_bytes", C.c_int64, [_I64, _I32, _I32, _I32, _I32]),
     ("qie_attention_decode", C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _I32, C.POINTER(KvCacheC), _I32, _F, _I32,
                                        _P, _P, _P]),
@@ -180,6 +183,7 @@ SIGNATURES = [
     ("qie_batch_block_table", C.c_int, [_P, _I32, _PI32, _I32]),
     ("qie_prefill", C.c_int, [_P, _I32, _PI32, _I32, C.POINTER(SamplingC), _PI32]),
     ("qie_prefill_batch", C.c_int, [_P, _I32, _I32, _PI32, _I32, C.POINTER(SamplingC), _PI32]),
+    ("qie_prefill_append", C.c_int, [_P, _I32, _PI32, _I32, _I32, C.POINTER(SamplingC), _PI32]),
     ("qie_decode_step", C.c_int, [_P, C.POINTER(SamplingC), _PI32]),
     ("qie_decode", C.c_int, [_P, _I32, C.POINTER(SamplingC), _PI32]),
     ("qie_batch_logits", C.c_int, [_P, _P]),

@@ -234,9 +234,10 @@ __global__ void set_state_kernel(int m, int32_t pos_v, int32_t step_v, int32_t t
 }
 
 // positions of n_seqs equal-length prompts laid end to end: row i sits at i % len
-__global__ void iota_kernel(int32_t* p, int n, int len) {
+// (plus base: an append's rows start at its pos0)
+__global__ void iota_kernel(int32_t* p, int n, int len, int base) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = i % len;
+    if (i < n) p[i] = base + i % len;
 }
 
 // prompt z (blockIdx.y) of len ids -> history row z of dst (stride dst_stride)
@@ -728,12 +729,21 @@ static bool prefill_mx(const qie_engine* e) {
     return e->fp8 && e->opts.prefill_fp8;
 }
 
-static int ensure_prefill_scratch(qie_batch* b, int64_t n) {
+// Workspace of the attention form a prefill of n rows runs: qie_attention from position 0,
+// qie_attention_extend (sized for the cache's run length, as batch_cache hands it over) for an
+// append
+static int64_t prefill_attn_ws_bytes(const qie_batch* b, int64_t n, bool extend) {
+    const qie_model_spec& s = b->e->spec;
+    if (extend) return qie_attention_extend_workspace_bytes(n, b->e->sh.nq, s.head_dim, b->max_ctx + b->run_pad);
+    return qie_attention_workspace_bytes(n, b->e->sh.nq, s.head_dim, b->max_ctx);
+}
+
+static int ensure_prefill_scratch(qie_batch* b, int64_t n, bool extend) {
     if (n <= b->pf_rows) {
         // rows fit; the attention workspace is not monotone in n (<= 8 rows run the split
-        // kernel with partials, longer prompts need none), so size it for this n
-        const qie_model_spec& s = b->e->spec;
-        const int64_t ws = qie_attention_workspace_bytes(n, b->e->sh.nq, s.head_dim, b->max_ctx);
+        // kernel with partials, longer prompts need none; an append's split partials grow
+        // with its rows), so size it for this n and this form
+        const int64_t ws = prefill_attn_ws_bytes(b, n, extend);
         if (ws > b->pf_attn_ws_bytes) {
             hipFree(b->pf_attn_ws);
             b->pf_attn_ws = nullptr;
@@ -770,7 +780,7 @@ static int ensure_prefill_scratch(qie_batch* b, int64_t n) {
     QIE_TRY(dmalloc((void**)&b->pf_ids, n * 4));
     b->pf_attn_ws = nullptr;
     b->pf_attn_ws_bytes = 0;
-    int64_t ws = qie_attention_workspace_bytes(n, sh.nq, s.head_dim, b->max_ctx);
+    int64_t ws = prefill_attn_ws_bytes(b, n, extend);
     QIE_TRY(dmalloc(&b->pf_attn_ws, (size_t)ws));
     b->pf_attn_ws_bytes = ws;
     b->pf_rows = n;
@@ -1317,19 +1327,41 @@ void qie_batch_destroy(qie_batch* b) {
 // to end): every GEMM runs once over all n_seqs * len rows, attention and the KV append see
 // the prompts as sequences of rows_per_seq = len, and the head samples the n_seqs last rows
 // in one launch.  n_seqs = 1 is qie_prefill.
-static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, int len, const qie_sampling* smp,
-                        int32_t* next_ids, const char* who) {
-    QIE_REQUIRE(b && ids && len > 0 && n_seqs > 0 && seq0 >= 0 && seq0 + n_seqs <= b->B, "%s: bad arguments", who);
-    QIE_REQUIRE(len < b->max_ctx, "%s: prompt of %d tokens does not fit max_ctx %d", who, len, b->max_ctx);
+// pos0 > 0 (qie_prefill_append, n_seqs = 1): the rows continue live sequence seq0 at positions
+// pos0 .. pos0 + len - 1 — its pages are kept and grown, the ids land at history offset pos0,
+// and attention over the cached prefix runs qie_attention_extend; everything else (the layer
+// loop, tensor parallelism, the head) is the same code.
+static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, int len, int pos0,
+                        const qie_sampling* smp, int32_t* next_ids, const char* who) {
+    QIE_REQUIRE(b && ids && len > 0 && n_seqs > 0 && seq0 >= 0 && seq0 + n_seqs <= b->B && pos0 >= 0,
+                "%s: bad arguments", who);
+    QIE_REQUIRE((int64_t)pos0 + len < b->max_ctx, "%s: %d tokens from position %d do not fit max_ctx %d", who, len,
+                pos0, b->max_ctx);
+    const bool append = pos0 > 0;
     qie_engine* e = b->e;
     const qie_model_spec& s = e->spec;
+    if (append) {
+        QIE_REQUIRE(n_seqs == 1, "%s: one sequence per call", who);
+        QIE_REQUIRE(!b->idle[seq0], "%s: slot %d holds no live sequence", who, seq0);
+        QIE_REQUIRE(pos0 <= b->h_pos[seq0], "%s: pos0 %d is past sequence %d's current position %d", who, pos0, seq0,
+                    b->h_pos[seq0]);
+        QIE_REQUIRE(!(e->fp8 && e->opts.prefill_fp8),
+                    "%s: not available on a prefill_fp8 engine (block-scaled fp8 activations are defined for a "
+                    "prefill from position 0 only: an append has no reference to be checked against)", who);
+    }
     const int64_t n = (int64_t)n_seqs * len;   // rows
     QIE_REQUIRE(n <= INT32_MAX, "%s: %lld rows", who, (long long)n);
     for (int64_t i = 0; i < n; i++)
         QIE_REQUIRE(ids[i] >= 0 && ids[i] < s.vocab, "%s: token id %d out of range", who, ids[i]);
     hipStream_t st = e->stream;
-    QIE_TRY(ensure_prefill_scratch(b, n));
-    if (b->d_table) {   // all-or-nothing: the slots' own pages count, nothing is dropped on failure
+    if (append && b->d_table) {   // all-or-nothing, before anything is allocated or launched
+        const int64_t need = ((int64_t)pos0 + len + b->page_tokens - 1) / b->page_tokens - b->held[seq0];
+        if (need > (int64_t)b->free_pages.size())
+            return fail(-28, "%s: KV pool exhausted (%lld more pages needed for %d rows at position %d, %zu free)",
+                        who, (long long)need, len, pos0, b->free_pages.size());
+    }
+    QIE_TRY(ensure_prefill_scratch(b, n, append));
+    if (b->d_table && !append) {   // all-or-nothing: the slots' own pages count, nothing is dropped on failure
         const int64_t need = ((int64_t)len + b->page_tokens - 1) / b->page_tokens * n_seqs;
         int64_t held = 0;
         for (int z = 0; z < n_seqs; z++) held += b->held[seq0 + z];
@@ -1340,9 +1372,10 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
     // a prefill starts a new sequence in each slot: every target slot's pages go back to
     // the pool BEFORE any slot draws, so the check above (free + held) is exactly what the
     // draws below can use and none of them can fail part way
-    for (int z = 0; z < n_seqs; z++) drop_pages(b, seq0 + z);
+    if (!append)
+        for (int z = 0; z < n_seqs; z++) drop_pages(b, seq0 + z);
     for (int z = 0; z < n_seqs; z++) {
-        QIE_TRY(ensure_pages(b, seq0 + z, len));
+        QIE_TRY(ensure_pages(b, seq0 + z, (int64_t)pos0 + len));
         b->idle[seq0 + z] = 0;
     }
     QIE_TRY(flush_table(b));
@@ -1350,9 +1383,9 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
     const int64_t H = s.hidden, hd = s.head_dim, QD = (int64_t)sh.nq * hd, KD = (int64_t)sh.nkv * hd;
     const int64_t QKVD = QD + 2 * KD, I = sh.ffn;
     QIE_HIP(hipMemcpyAsync(b->pf_ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b->pf_pos, (int)n, len);
+    hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b->pf_pos, (int)n, len, pos0);
     hipLaunchKernelGGL(copy_ids_kernel, dim3((len + 255) / 256, n_seqs), dim3(256), 0, st, b->pf_ids,
-                       b->d_hist + (int64_t)seq0 * b->max_ctx, len, (int64_t)b->max_ctx);
+                       b->d_hist + (int64_t)seq0 * b->max_ctx + pos0, len, (int64_t)b->max_ctx);
     QIE_TRY(qie_embedding(e->w.embed, b->pf_ids, b->pf_x, n, H, st));
     const qie_kv_cache cache = batch_cache(b, seq0);
     // fp8 engine, >= 256 rows: the GEMMs run on the dequantised bf16 copy (layers_pf); with
@@ -1365,6 +1398,13 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
         return a;
     };
     const bool mx = prefill_mx(e);
+    // attention of the new rows: from position 0 the rows are the whole context (qie_attention's
+    // causal prefill forms); an append's rows attend to the cached prefix as well
+    auto attend = [&](int l) -> int {
+        if (append)
+            return qie_attention_extend(b->pf_q, n, b->pf_pos, len, &cache, l, sh.nq, b->pf_att, b->pf_attn_ws, st);
+        return qie_attention(b->pf_q, n, b->pf_pos, len, &cache, l, sh.nq, b->pf_att, b->pf_attn_ws, st);
+    };
     // fp8 activations: quantise the projection input x [n][K] (bf16) into pf_q8 / pf_e8 and
     // point the linear at the codes
     auto mx_in = [&](qie_linear_args& a, const uint16_t* x, int64_t K) -> int {
@@ -1386,7 +1426,7 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
             QIE_TRY(qie_linear(&a, st));
             QIE_TRY(qie_qkv_post(b->pf_qkv, n, b->pf_pos, len, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, sh.nq,
                                  &cache, l, s.rms_eps, s.numerics, b->pf_q, st));
-            QIE_TRY(qie_attention(b->pf_q, n, b->pf_pos, len, &cache, l, sh.nq, b->pf_att, b->pf_attn_ws, st));
+            QIE_TRY(attend(l));
             a = lin_proj(e);
             QIE_TRY(mx_in(a, b->pf_att, QD));
             a.w[0] = L.wo; a.seg_rows[0] = H;
@@ -1416,7 +1456,7 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
         QIE_TRY(qie_linear(&a, st));
         QIE_TRY(qie_qkv_post(b->pf_qkv, n, b->pf_pos, len, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, sh.nq,
                              &cache, l, s.rms_eps, s.numerics, b->pf_q, st));
-        QIE_TRY(qie_attention(b->pf_q, n, b->pf_pos, len, &cache, l, sh.nq, b->pf_att, b->pf_attn_ws, st));
+        QIE_TRY(attend(l));
         a = pf_base();
         a.x = b->pf_att; a.ldx = QD; a.w[0] = L.wo; a.seg_rows[0] = H;
         a.M = n; a.K = QD; a.N = H; a.ldy = H;
@@ -1431,9 +1471,9 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
         a.M = n; a.K = I; a.N = H; a.ldy = H;
         QIE_TRY(row_parallel(b, a, b->pf_x, b->pf_part, n));
     }
-    // position of each last prompt token; finalize advances it to len (the new token).
+    // position of each last prompt token; finalize advances it to pos0 + len (the new token).
     for (int z = 0; z < n_seqs; z++) {
-        hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(64), 0, st, seq0 + z, len - 1, 0,
+        hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(64), 0, st, seq0 + z, pos0 + len - 1, 0,
                            ids[(int64_t)z * len + len - 1], b->d_pos, b->d_step, b->d_hist, b->max_ctx,
                            (const uint4*)e->w.embed, (uint4*)b->x_res, (int64_t)H / 8, 0, rope_cur_args(b));
         QIE_LAUNCH_CHECK();
@@ -1445,7 +1485,7 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
         last = b->pf_hn;
     }
     QIE_TRY(enqueue_head(b, last, H, seq0, n_seqs, smp));
-    for (int z = 0; z < n_seqs; z++) b->h_pos[seq0 + z] = len;
+    for (int z = 0; z < n_seqs; z++) b->h_pos[seq0 + z] = pos0 + len;
     if (next_ids) {
         QIE_HIP(hipMemcpyAsync(next_ids, b->d_ids + seq0, (size_t)n_seqs * 4, hipMemcpyDeviceToHost, st));
         QIE_HIP(hipStreamSynchronize(st));
@@ -1455,12 +1495,18 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
 }
 
 int qie_prefill(qie_batch* b, int32_t seq, const int32_t* ids, int32_t n, const qie_sampling* smp, int32_t* next_id) {
-    return prefill_rows(b, seq, 1, ids, n, smp, next_id, "qie_prefill");
+    return prefill_rows(b, seq, 1, ids, n, 0, smp, next_id, "qie_prefill");
+}
+
+int qie_prefill_append(qie_batch* b, int32_t seq, const int32_t* ids, int32_t n, int32_t pos0,
+                       const qie_sampling* smp, int32_t* next_id) {
+    QIE_REQUIRE(pos0 >= 1, "qie_prefill_append: pos0 must be >= 1 (a sequence starts with qie_prefill)");
+    return prefill_rows(b, seq, 1, ids, n, pos0, smp, next_id, "qie_prefill_append");
 }
 
 int qie_prefill_batch(qie_batch* b, int32_t seq0, int32_t n_seqs, const int32_t* ids, int32_t len,
                       const qie_sampling* smp, int32_t* next_ids) {
-    return prefill_rows(b, seq0, n_seqs, ids, len, smp, next_ids, "qie_prefill_batch");
+    return prefill_rows(b, seq0, n_seqs, ids, len, 0, smp, next_ids, "qie_prefill_batch");
 }
 
 static bool same_sampling(const qie_sampling& a, const qie_sampling* b) {

@@ -241,11 +241,35 @@ class Batch:
             _lib.check(self.lib.qie_batch_create(engine.h, batch, max_ctx, C.byref(h)), "qie_batch_create")
         self.h = h
 
-    def prefill(self, seq: int, ids: Sequence[int], sampling: Sampling = GREEDY) -> int:
+    def prefill(self, seq: int, ids: Sequence[int], sampling: Sampling = GREEDY, chunk: Optional[int] = None) -> int:
+        """Start sequence `seq` with the prompt `ids`.  chunk: feed the prompt in pieces of at
+        most `chunk` ids (the first through qie_prefill, the rest through append), which bounds
+        the prefill scratch by the chunk; returns the last piece's token."""
+        if chunk is not None:
+            from .scheduler import prefill_chunks
+            pieces = prefill_chunks(len(ids), chunk)
+            tok = self.prefill(seq, ids[:pieces[0][1]], sampling)
+            for off, n in pieces[1:]:
+                tok = self.append(seq, ids[off:off + n], off, sampling)
+            return tok
         arr = (C.c_int32 * len(ids))(*[int(i) for i in ids])
         out = C.c_int32(-1)
         sc = sampling.to_c()
         _lib.check(self.lib.qie_prefill(self.h, seq, arr, len(ids), C.byref(sc), C.byref(out)), "qie_prefill")
+        return out.value
+
+    def append(self, seq: int, ids: Sequence[int], pos0: Optional[int] = None, sampling: Sampling = GREEDY) -> int:
+        """Extend live sequence `seq` with `ids` at positions pos0 .. pos0+len-1 over its cached
+        rows [0, pos0) (qie_prefill_append); returns the token sampled after the last id.
+        pos0=None: the sequence's current position — the pending current token is replaced by
+        ids[0].  A smaller pos0 rewinds: rows from pos0 on are overwritten."""
+        if pos0 is None:
+            pos0 = int(self.positions()[seq])
+        arr = (C.c_int32 * len(ids))(*[int(i) for i in ids])
+        out = C.c_int32(-1)
+        sc = sampling.to_c()
+        _lib.check(self.lib.qie_prefill_append(self.h, seq, arr, len(ids), int(pos0), C.byref(sc), C.byref(out)),
+                   "qie_prefill_append")
         return out.value
 
     def prefill_batch(self, seq0: int, prompts: Sequence[Sequence[int]], sampling: Sampling = GREEDY) -> List[int]:

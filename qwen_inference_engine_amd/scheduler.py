@@ -34,6 +34,7 @@ class Request:
     slot: int = -1
     pages: int = 0
     done: bool = False
+    chunks: list = dataclasses.field(default_factory=list)   # (offset, length) prompt pieces still to prefill
 
 
 def prefill_runs(admitted: Sequence[Request]) -> List[List[Request]]:
@@ -49,9 +50,27 @@ def prefill_runs(admitted: Sequence[Request]) -> List[List[Request]]:
     return runs
 
 
+def prefill_chunks(n: int, chunk: Optional[int]) -> List[tuple]:
+    """(offset, length) pieces in which a prompt of n ids is prefilled: the whole prompt when
+    chunk is None, else pieces of `chunk` ids with a shorter last one.  The first piece starts
+    the sequence (qie_prefill), every later one extends it at its offset (qie_prefill_append)."""
+    if n < 1:
+        raise ValueError("prefill_chunks: empty prompt")
+    if chunk is None:
+        return [(0, n)]
+    if chunk < 1:
+        raise ValueError("prefill_chunks: chunk must be >= 1")
+    return [(off, min(chunk, n - off)) for off in range(0, n, chunk)]
+
+
 class ContinuousBatcher:
     def __init__(self, engine: Engine, slots: int = 8, max_ctx: Optional[int] = None, page_tokens: int = 128,
-                 n_pages: int = 0, sampling: Sampling = GREEDY, keep_logits: bool = False):
+                 n_pages: int = 0, sampling: Sampling = GREEDY, keep_logits: bool = False,
+                 prefill_chunk: Optional[int] = None):
+        # prefill_chunk: a prompt longer than this takes its first chunk at admission and one
+        # more chunk per step() (qie_prefill_append), so an admission stalls the live slots for
+        # one chunk's prefill at a time; its first token is emitted after the last chunk
+        self.prefill_chunk = prefill_chunk
         self.batch: Batch = engine.batch(slots, max_ctx, page_tokens=page_tokens, n_pages=n_pages)
         self.keep_logits = keep_logits          # copy each token's logit row (tests / diagnostics)
         self.max_ctx = self.batch.max_ctx
@@ -109,27 +128,51 @@ class ContinuousBatcher:
         # equal-length prompts landing in consecutive slots prefill in one pass
         # (qie_prefill_batch); tokens are emitted in admission order afterwards
         first: Dict[int, int] = {}
-        for run in prefill_runs(admitted):
+        whole: List[Request] = []
+        for r in admitted:
+            pieces = prefill_chunks(len(r.prompt), self.prefill_chunk)
+            if len(pieces) > 1:   # chunked: the first piece now, its token is not the request's
+                self.batch.prefill(r.slot, r.prompt[:pieces[0][1]], self.sampling)
+                r.chunks = pieces[1:]
+            else:
+                whole.append(r)
+        for run in prefill_runs(whole):
             if len(run) == 1:
                 first[run[0].rid] = self.batch.prefill(run[0].slot, run[0].prompt, self.sampling)
             else:
                 toks = self.batch.prefill_batch(run[0].slot, [r.prompt for r in run], self.sampling)
                 first.update((r.rid, t) for r, t in zip(run, toks))
-        lg = self.batch.logits() if self.keep_logits and admitted else None
-        for r in admitted:
+        lg = self.batch.logits() if self.keep_logits and whole else None
+        for r in whole:
             self._emit(r, first[r.rid], out, lg)
+
+    def _advance_chunks(self, out: list, fresh: set) -> None:
+        """One more prompt piece for every slot still in chunked prefill (not the requests
+        admitted in this step: they took their piece at admission).  pos0 is explicit: the
+        decode step that ran since the last piece wrote one row at the slot's position, and this
+        piece overwrites it."""
+        for r in self.slots:
+            if r is None or not r.chunks or r.rid in fresh:
+                continue
+            off, n = r.chunks.pop(0)
+            tok = self.batch.append(r.slot, r.prompt[off:off + n], off, self.sampling)
+            if not r.chunks:
+                self._emit(r, tok, out)
 
     def step(self) -> List[tuple]:
         """Admit what fits, then one decode step for every slot; returns the (request id,
         token) pairs produced, in slot order."""
         out: List[tuple] = []
+        before = {r.rid for r in self.slots if r is not None}
         self._admit(out)
+        self._advance_chunks(out, {r.rid for r in self.slots if r is not None} - before)
         if any(s is not None for s in self.slots):
             live = list(self.slots)
             ids = self.batch.decode_step(self.sampling)
             lg = self.batch.logits() if self.keep_logits else None
             for i, r in enumerate(live):
-                if r is not None and not r.done:
+                # a slot still in chunked prefill decodes too (fixed-B step); its output is dropped
+                if r is not None and not r.done and not r.chunks:
                     self._emit(r, int(ids[i]), out, lg)
         return out
 
