@@ -17,7 +17,7 @@
 // Scores: s = dot(q, k) / sqrtf(hd) in fp32; p = expf(s - max); out bf16.
 #include "qie_common.hpp"
 #include "../../include/qie/qie_ops.h"
-#include "attn_decode.hpp"
+#include "attn_mfma_tile.hpp"
 
 
 #include <cstdlib>
@@ -181,38 +181,10 @@ __global__ __launch_bounds__(256) void attn_split_kernel(AttnParams a) {
     }
 }
 
-template <int HD>
-__global__ __launch_bounds__(HD) void attn_combine_kernel(AttnParams a) {
-    const int64_t m = blockIdx.y;
-    const int h = blockIdx.x, d = threadIdx.x;
-    const int64_t base = (m * a.nq + h) * (int64_t)a.nsplit;
-    float mn = -INFINITY;
-    for (int s = 0; s < a.nsplit; s++) mn = fmaxf(mn, a.part_ml[(base + s) * 2]);
-    float l = 0.f, ov = 0.f;
-    for (int s = 0; s < a.nsplit; s++) {
-        const float ms = a.part_ml[(base + s) * 2];
-        if (ms == -INFINITY) continue;
-        const float c = expf(ms - mn);
-        l += a.part_ml[(base + s) * 2 + 1] * c;
-        ov += a.part_o[(base + s) * HD + d] * c;
-    }
-    a.out[m * (int64_t)a.nq * HD + (int64_t)h * HD + d] = f2bf(ov / l);
-}
-
 
 // ---------------------------------------------------------------------------
-// Prefill: causal flash attention on MFMA (v_mfma_f32_16x16x32_bf16).
-// K/V tiles of 64 keys staged in LDS (double-buffered, register prefetch).
-//   S^T = K . Q^T  — A = K tile (row = key, k = d) from an XOR-swizzled LDS image,
-//                    B = Q^T from registers (lane: q = lane & 15, 8 contiguous d);
-//                    so each lane holds 4 keys x 4 key-tiles of ONE query row and
-//                    the softmax row statistics need only lanes l, l^16, l^32, l^48.
-//   O  += P . V    — A = P straight from the S^T accumulators (bf16), k permuted as
-//                    key(j) = 32c + 4g + j (j < 4), 32c + 16 + 4g + (j - 4);
-//                    B = V with the SAME key permutation, read by two
-//                    ds_read_b64_tr_b16 per fragment from a row-major V image.
-// Scores: dot / sqrtf(hd) (fp32), masked keys (> query position) get -inf (the
-// reference's -1e9, self_attension.cu:88-92, underflows to the same 0).
+// Prefill: causal flash attention on MFMA; the key-tile walk, its operand layouts and LDS
+// images are attn_mfma_walk's (attn_mfma_tile.hpp).
 struct PrefillAttnParams {
     const uint16_t* q;       // [M][nq*HD]
     const int32_t* pos;      // [M]; non-decreasing within each sequence's rows
@@ -220,8 +192,7 @@ struct PrefillAttnParams {
     const uint16_t* kc;
     const uint16_t* vc;
     KvMap km;
-    int layer, nkv, nq, max_ctx;
-    int64_t M;
+    int layer, nkv, nq;
     uint16_t* out;
     int full_tiles;          // 1: tiles wholly at or below a group's first position skip the causal mask (dev A/B 0)
 };
@@ -235,23 +206,13 @@ struct PrefillAttnParams {
 // (group, key tile) products; a workgroup stages K/V tiles up to its latest row and each
 // group skips the tiles past its own last position (the contiguous 128-row q tiles this
 // replaces left the workgroup with the last tile 16x the work of the first: 2x the
-// makespan of the balanced split on 256 CUs).  Scores go to the log2 domain once
-// (dot * log2(e) / sqrt(hd)) and are exponentiated with v_exp_f32: the reference build
-// compiles with -use_fast_math, i.e. __expf / __fdividef.
+// makespan of the balanced split on 256 CUs).
 template <int HD, bool PG, int NW>
 __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_prefill_mfma2_kernel(PrefillAttnParams a) {
     constexpr int KT = 64;
-    constexpr int CPR = HD / 8;
     constexpr int KSTEPS = HD / 32;
     constexpr int DT = HD / 16;
     constexpr int QG = 2;                  // 16-row query groups per wave
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint16_t* Ks = reinterpret_cast<uint16_t*>(smem);
-    uint16_t* Vs = reinterpret_cast<uint16_t*>(smem + 2 * KT * HD * 2);
-    // V image chunk swizzle: the 16-B chunk c of key row r sits at c ^ vswz(r).  A
-    // ds_read_b64_tr_b16 half-wave reads 8 rows x 32 B at one column; unswizzled, the rows
-    // (a whole number of 256-B bank rows apart) hit the same banks: 8-way conflicts.
-    auto vswz = [](int r) { return 2 * (r & (CPR / 2 - 1)); };
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, g = lane >> 4;
@@ -289,199 +250,9 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_prefill_mfma2_kernel(Pre
         for (int ks = 0; ks < KSTEPS; ks++) qf[q][ks] = *reinterpret_cast<const bf16x8_t*>(qp + ks * 32 + g * 8);
     }
 
-    // K/V tiles go global -> LDS by LDS-DMA (global_load_lds_dwordx4): one wave-instruction
-    // = 1 KiB = RPI key rows, lane-linear in LDS, the chunk swizzle applied on the SOURCE
-    // address (LDS position p of row r holds chunk p ^ swz(r)); no staging registers and no
-    // ds_write pass.  A 64-key tile never straddles a page (page_tokens is a multiple of
-    // 128); rows past kmax re-read row kmax (same page) and are masked by position.
-    constexpr int RPI = 512 / HD;                 // key rows per 1 KiB wave-instruction
-    constexpr int IPW = KT / RPI / NW;            // wave-instructions per wave per operand
-    // Buffer loads to LDS on a per-tile resource (round 5): the lane byte offsets inside a
-    // tile are constants of the launch and the tile base is scalar, so a tile's DMAs cost no
-    // VALU (the flat form recomputed 64-bit addresses and the row clamp per tile: ~40 VALU).
-    // The resource covers the tile's rows up to kmax only: rows past it read as zeros (their
-    // keys are masked, and P = 0 times a zero V row stays 0 whatever the cache holds there).
-    uint32_t koff[IPW], voff[IPW];
-#pragma unroll
-    for (int i = 0; i < IPW; i++) {
-        const int r = (wave * IPW + i) * RPI + lane / CPR, pch = lane % CPR;
-        koff[i] = (uint32_t)(r * HD + (pch ^ (r & (CPR - 1))) * 8) * 2;
-        voff[i] = (uint32_t)(r * HD + (pch ^ vswz(r)) * 8) * 2;
-    }
-    auto issue = [&](int kt, int buf) {
-        const int64_t tb = kv_tok<PG>(a.km, seq, kt * KT, HD);
-        const int rows = min(KT, kmax + 1 - kt * KT);
-        const auto rk = __builtin_amdgcn_make_buffer_rsrc((void*)(kb + tb), (short)0, rows * HD * 2, 0x00020000);
-        const auto rv = __builtin_amdgcn_make_buffer_rsrc((void*)(vb + tb), (short)0, rows * HD * 2, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < IPW; i++) {
-            const int inst = wave * IPW + i;
-            buf_lds16(rk, Ks + buf * KT * HD + inst * 512, koff[i]);
-            buf_lds16(rv, Vs + buf * KT * HD + inst * 512, voff[i]);
-        }
-    };
-
     f32x4_t oacc[QG][DT];
-#pragma unroll
-    for (int q = 0; q < QG; q++)
-#pragma unroll
-        for (int d = 0; d < DT; d++) oacc[q][d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     float m_run[QG], l_run[QG];
-#pragma unroll
-    for (int q = 0; q < QG; q++) {
-        m_run[q] = -INFINITY;
-        l_run[q] = 0.f;
-    }
-    const float sl2 = 1.4426950408889634f / sqrtf((float)HD);   // log2(e) / sqrt(hd)
-
-    issue(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int cur = 0;
-    // which of the wave's two groups take a key tile is a run of tiles per case (positions
-    // are non-decreasing, and group 1 is the later one): both groups for tiles [0, nkt0),
-    // group 1 alone up to nkt1, then barriers only up to the workgroup's nkt.  One loop per
-    // case with the tile body instantiated for it: no MFMA sits behind a per-instruction
-    // exec-mask branch (the compiler could not prove on[] uniform and wrapped every MFMA in
-    // s_and_saveexec / s_cbranch_execz / s_or_b64), and — unlike a three-way branch inside
-    // one loop — the accumulators need no register copies where the cases meet.
-    auto tile = [&](const int kt, const uint16_t* K, const uint16_t* Vt, auto q0c, auto q1c) {
-            constexpr bool ON[QG] = {decltype(q0c)::value, decltype(q1c)::value};
-            f32x4_t sacc[QG][4];
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-#pragma unroll
-                for (int q = 0; q < QG; q++) sacc[q][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-                const int r = t * 16 + fr;
-#pragma unroll
-                for (int ks = 0; ks < KSTEPS; ks++) {
-                    const int ch = ks * 4 + g;
-                    const bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(K + r * HD + ((ch ^ (r & (CPR - 1))) * 8));
-#pragma unroll
-                    for (int q = 0; q < QG; q++)
-                        if (ON[q]) sacc[q][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[q][ks], sacc[q][t], 0, 0, 0);
-                }
-            }
-            float pv[QG][4][4];   // this tile's probabilities (fp32), split into bf16 parts at P.V
-#pragma unroll
-            for (int q = 0; q < QG; q++) {
-                if (!ON[q]) continue;
-                float (&sv)[4][4] = pv[q];
-                float mt = -INFINITY;
-                // (an fma form, exp2(fma(s, sl2, -m)), saves 16 VALU per tile but rounds
-                // differently: config 2's 128-decision parity run then had a flip at a top-2 gap
-                // 0.34 against the oracle's own 0.31 spread — not taken)
-                if (kt * KT + KT - 1 <= gmin[q]) {   // wave-uniform: no key of the tile is masked
-#pragma unroll
-                    for (int t = 0; t < 4; t++)
-#pragma unroll
-                        for (int r = 0; r < 4; r++) {
-                            const float sc = sacc[q][t][r] * sl2;
-                            sv[t][r] = sc;
-                            mt = fmaxf(mt, sc);
-                        }
-                } else {
-#pragma unroll
-                    for (int t = 0; t < 4; t++)
-#pragma unroll
-                        for (int r = 0; r < 4; r++) {
-                            const int key = kt * KT + t * 16 + g * 4 + r;
-                            const float sc = key <= qpos[q] ? sacc[q][t][r] * sl2 : -INFINITY;
-                            sv[t][r] = sc;
-                            mt = fmaxf(mt, sc);
-                        }
-                }
-                mt = xor32_max(xor16_max(mt));
-                const float m_new = fmaxf(m_run[q], mt);   // finite: tile 0 holds key 0 <= every position
-                const float alpha = __builtin_amdgcn_exp2f(m_run[q] - m_new);
-                float ls = 0.f;
-#pragma unroll
-                for (int t = 0; t < 4; t++)
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        const float e = __builtin_amdgcn_exp2f(sv[t][r] - m_new);
-                        sv[t][r] = e;
-                        ls += e;
-                    }
-                ls = xor32_sum(xor16_sum(ls));
-                l_run[q] = l_run[q] * alpha + ls;
-                m_run[q] = m_new;
-                // O *= alpha only where some row's max grew: alpha == 1 exactly otherwise
-                // (exp2(0)), and tile 0's O is zero — skipping is bit-identical (a wave-uniform
-                // ballot; once the running maxima settle most tiles skip the 32 products)
-                if (kt > 0 && __builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
-                    float ar[4];
-#pragma unroll
-                    for (int r = 0; r < 4; r++) ar[r] = __shfl(alpha, g * 4 + r, 64);
-#pragma unroll
-                    for (int d = 0; d < DT; d++)
-#pragma unroll
-                        for (int r = 0; r < 4; r++) oacc[q][d][r] *= ar[r];
-                }
-            }
-            // (Measured and dropped: softmax then P.V per group, so that group 1's softmax
-            // could issue beside group 0's MFMAs, V fragments read per group: 76.8 vs 75.3 µs.)
-            const int q4 = fr >> 2, p4 = fr & 3;
-#pragma unroll
-            for (int c = 0; c < 2; c++) {
-                // P = hi + lo: two bf16 parts carry 16 of the 24 mantissa bits of each fp32
-                // probability; the dropped remainder is < 2^-16 of p, a relative error per
-                // P.V product (<= 2^-17) below the fp32 summation-order spread of the
-                // reference's own sum over keys
-                bf16x8_t ph[QG], pl[QG];
-#pragma unroll
-                for (int q = 0; q < QG; q++) {
-                    if (!ON[q]) continue;
-                    float e8[8];
-#pragma unroll
-                    for (int jj = 0; jj < 8; jj++) e8[jj] = pv[q][2 * c + (jj >> 2)][jj & 3];
-                    uint4 pp[2];
-                    split_bf16x8<2>(e8, pp);
-                    ph[q] = __builtin_bit_cast(bf16x8_t, pp[0]);
-                    pl[q] = __builtin_bit_cast(bf16x8_t, pp[1]);
-                }
-#pragma unroll
-                for (int d = 0; d < DT; d++) {
-                    // rows vr and vr + 16 share vswz: one column offset serves both reads
-                    const int vr = 32 * c + 4 * g + q4;
-                    const uint16_t* a0 = Vt + vr * HD + (((2 * d + (p4 >> 1)) ^ vswz(vr)) * 8) + (p4 & 1) * 4;
-                    const i16x4_t v0 =
-                        __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4_t*)(a0));
-                    const i16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (__attribute__((address_space(3))) i16x4_t*)(a0 + 16 * HD));
-                    const bf16x8_t vb8 =
-                        __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7));
-#pragma unroll
-                    for (int q = 0; q < QG; q++) {
-                        if (!ON[q]) continue;
-                        oacc[q][d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ph[q], vb8, oacc[q][d], 0, 0, 0);
-                        oacc[q][d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pl[q], vb8, oacc[q][d], 0, 0, 0);
-                    }
-                }
-            }
-        };
-    int kt = 0;
-    auto run = [&](const int kend, auto q0c, auto q1c) {
-        for (; kt < kend; kt++) {
-            // into the other buffer: every wave finished tile kt-1 before the last barrier
-            if (kt + 1 < nkt) issue(kt + 1, cur ^ 1);
-            if constexpr (decltype(q0c)::value || decltype(q1c)::value)
-                tile(kt, Ks + cur * KT * HD, Vs + cur * KT * HD, q0c, q1c);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMAs of tile kt+1
-            __syncthreads();                                     // ... and every other wave's
-            cur ^= 1;
-        }
-    };
-    // tiles each group takes: kt * KT <= gpos (gpos = -1: none); gpos[1] >= gpos[0]
-    const int nkt0 = gpos[0] >= 0 ? min(nkt, gpos[0] / KT + 1) : 0;
-    const int nkt1 = gpos[1] >= 0 ? min(nkt, gpos[1] / KT + 1) : 0;
-    if (nkt1 > 0) {
-        run(nkt0, std::true_type{}, std::true_type{});
-        run(nkt1, std::false_type{}, std::true_type{});
-    } else {
-        run(nkt0, std::true_type{}, std::false_type{});
-    }
-    run(nkt, std::false_type{}, std::false_type{});
+    attn_mfma_walk<HD, PG, NW, false>(kb, vb, a.km, seq, kmax, 0, nkt, qf, qpos, gpos, gmin, oacc, m_run, l_run);
 #pragma unroll
     for (int q = 0; q < QG; q++) {
         if (!gact[q]) continue;
@@ -632,8 +403,6 @@ int qie_attention(const void* q, int64_t M, const int32_t* pos, int32_t rows_per
         pa.layer = layer;
         pa.nkv = cache->n_kv_heads;
         pa.nq = n_heads;
-        pa.max_ctx = cache->max_ctx;
-        pa.M = M;
         pa.out = (uint16_t*)out;
         pa.full_tiles = dev_env("QIE_ATTN_PF_FULL", 1);
         const size_t shm = (size_t)2 * 2 * 64 * cache->head_dim * 2;
@@ -673,16 +442,14 @@ int qie_attention(const void* q, int64_t M, const int32_t* pos, int32_t rows_per
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((unsigned)(a.nkv * a.nsplit), (unsigned)M);
     const bool pg = a.km.table != nullptr;
-    if (cache->head_dim == 128) {
-        hipLaunchKernelGGL((pg ? attn_split_kernel<128, true> : attn_split_kernel<128, false>), grid, dim3(256), 0, st, a);
-        QIE_LAUNCH_CHECK();
-        if (a.nsplit > 1) hipLaunchKernelGGL(attn_combine_kernel<128>, dim3(n_heads, (unsigned)M), dim3(128), 0, st, a);
-    } else {
-        hipLaunchKernelGGL((pg ? attn_split_kernel<64, true> : attn_split_kernel<64, false>), grid, dim3(256), 0, st, a);
-        QIE_LAUNCH_CHECK();
-        if (a.nsplit > 1) hipLaunchKernelGGL(attn_combine_kernel<64>, dim3(n_heads, (unsigned)M), dim3(64), 0, st, a);
-    }
+    auto k = cache->head_dim == 128 ? (pg ? attn_split_kernel<128, true> : attn_split_kernel<128, false>)
+                                    : (pg ? attn_split_kernel<64, true> : attn_split_kernel<64, false>);
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, st, a);
     QIE_LAUNCH_CHECK();
+    if (a.nsplit > 1) {
+        launch_attn_combine<false>(cache->head_dim, M, n_heads, a.nsplit, a.part_o, a.part_ml, a.out, st);
+        QIE_LAUNCH_CHECK();
+    }
     return 0;
 }
 

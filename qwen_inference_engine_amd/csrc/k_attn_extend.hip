@@ -16,13 +16,11 @@
 //   * every workgroup leaves fp32 partials (O, running max, sum) in the workspace and a
 //     second, ordinary launch merges them — no hand-off inside a launch.
 // Arithmetic, LDS images (LDS-DMA staging, XOR chunk swizzles, ds_read_b64_tr_b16 V reads)
-// and the per-tile softmax are attn_prefill_mfma2_kernel's (k_attention.hip), which documents
-// the operand layouts; differences are marked below.
+// and the per-tile softmax are attn_mfma_walk (attn_mfma_tile.hpp), the walk
+// attn_prefill_mfma2_kernel runs from key 0; that header documents the operand layouts.
 #include "qie_common.hpp"
 #include "../../include/qie/qie_ops.h"
-#include "attn_decode.hpp"
-
-#include <type_traits>
+#include "attn_mfma_tile.hpp"
 
 namespace qie {
 
@@ -57,7 +55,7 @@ struct ExtendAttnParams {
     KvMap km;
     int layer, nkv, nq;
     int nsplit, split_len;
-    float* part_o;    // [M][nq][nsplit][HD]
+    float* part_o;    // [M][nq][nsplit][HD]; merged by attn_combine_kernel<HD, true>
     float* part_ml;   // [M][nq][nsplit][2]: running max (log2 domain), sum
     uint16_t* out;    // [M][nq*HD]
 };
@@ -70,16 +68,11 @@ template <int HD, bool PG>
 __global__ __launch_bounds__(256, 2) void attn_extend_kernel(ExtendAttnParams a) {
     constexpr int NW = 4;
     constexpr int KT = 64;
-    constexpr int CPR = HD / 8;
     constexpr int KSTEPS = HD / 32;
     constexpr int DT = HD / 16;
     constexpr int QG = 2;                  // 16-row query groups per wave
     constexpr int NGB = QG * NW;           // groups per block
     static_assert(16 * NGB == kExtBlockRows, "attn_extend: block rows");
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint16_t* Ks = reinterpret_cast<uint16_t*>(smem);
-    uint16_t* Vs = reinterpret_cast<uint16_t*>(smem + 2 * KT * HD * 2);
-    auto vswz = [](int r) { return 2 * (r & (CPR / 2 - 1)); };
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fr = lane & 15, g = lane >> 4;
@@ -108,8 +101,7 @@ __global__ __launch_bounds__(256, 2) void attn_extend_kernel(ExtendAttnParams a)
         }
         return;
     }
-    const int kt0 = k0 / KT;
-    const int nkt = min((k0 + a.split_len) / KT, kmax / KT + 1);   // tiles [kt0, nkt); past kmax: not loaded
+    const int nkt = min((k0 + a.split_len) / KT, kmax / KT + 1);   // tiles [k0 / KT, nkt); past kmax: not loaded
 
     const int64_t head_off = kv_run_off(a.km, (int64_t)a.layer * a.nkv + kvh, HD);
     const uint16_t* kb = a.kc + head_off;
@@ -134,178 +126,9 @@ __global__ __launch_bounds__(256, 2) void attn_extend_kernel(ExtendAttnParams a)
         for (int ks = 0; ks < KSTEPS; ks++) qf[q][ks] = *reinterpret_cast<const bf16x8_t*>(qp + ks * 32 + g * 8);
     }
 
-    // K/V tiles: buffer loads to LDS on a per-tile resource that ends at row kmax (rows past
-    // it read as zeros; their keys are masked), chunk swizzle on the source address
-    constexpr int RPI = 512 / HD;                 // key rows per 1 KiB wave-instruction
-    constexpr int IPW = KT / RPI / NW;            // wave-instructions per wave per operand
-    uint32_t koff[IPW], voff[IPW];
-#pragma unroll
-    for (int i = 0; i < IPW; i++) {
-        const int r = (wave * IPW + i) * RPI + lane / CPR, pch = lane % CPR;
-        koff[i] = (uint32_t)(r * HD + (pch ^ (r & (CPR - 1))) * 8) * 2;
-        voff[i] = (uint32_t)(r * HD + (pch ^ vswz(r)) * 8) * 2;
-    }
-    auto issue = [&](int kt, int buf) {
-        const int64_t tb = kv_tok<PG>(a.km, seq, kt * KT, HD);
-        const int rows = min(KT, kmax + 1 - kt * KT);
-        const auto rk = __builtin_amdgcn_make_buffer_rsrc((void*)(kb + tb), (short)0, rows * HD * 2, 0x00020000);
-        const auto rv = __builtin_amdgcn_make_buffer_rsrc((void*)(vb + tb), (short)0, rows * HD * 2, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < IPW; i++) {
-            const int inst = wave * IPW + i;
-            buf_lds16(rk, Ks + buf * KT * HD + inst * 512, koff[i]);
-            buf_lds16(rv, Vs + buf * KT * HD + inst * 512, voff[i]);
-        }
-    };
-
     f32x4_t oacc[QG][DT];
-#pragma unroll
-    for (int q = 0; q < QG; q++)
-#pragma unroll
-        for (int d = 0; d < DT; d++) oacc[q][d] = f32x4_t{0.f, 0.f, 0.f, 0.f};
     float m_run[QG], l_run[QG];
-#pragma unroll
-    for (int q = 0; q < QG; q++) {
-        m_run[q] = -INFINITY;
-        l_run[q] = 0.f;
-    }
-    const float sl2 = 1.4426950408889634f / sqrtf((float)HD);   // log2(e) / sqrt(hd)
-
-    issue(kt0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    int cur = 0;
-    auto tile = [&](const int kt, const uint16_t* K, const uint16_t* Vt, auto q0c, auto q1c) {
-            constexpr bool ON[QG] = {decltype(q0c)::value, decltype(q1c)::value};
-            f32x4_t sacc[QG][4];
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-#pragma unroll
-                for (int q = 0; q < QG; q++) sacc[q][t] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-                const int r = t * 16 + fr;
-#pragma unroll
-                for (int ks = 0; ks < KSTEPS; ks++) {
-                    const int ch = ks * 4 + g;
-                    const bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(K + r * HD + ((ch ^ (r & (CPR - 1))) * 8));
-#pragma unroll
-                    for (int q = 0; q < QG; q++)
-                        if (ON[q]) sacc[q][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[q][ks], sacc[q][t], 0, 0, 0);
-                }
-            }
-            float pv[QG][4][4];
-#pragma unroll
-            for (int q = 0; q < QG; q++) {
-                if (!ON[q]) continue;
-                float (&sv)[4][4] = pv[q];
-                float mt = -INFINITY;
-                if (kt * KT + KT - 1 <= gmin[q]) {   // wave-uniform: no key of the tile is masked
-#pragma unroll
-                    for (int t = 0; t < 4; t++)
-#pragma unroll
-                        for (int r = 0; r < 4; r++) {
-                            const float sc = sacc[q][t][r] * sl2;
-                            sv[t][r] = sc;
-                            mt = fmaxf(mt, sc);
-                        }
-                } else {
-#pragma unroll
-                    for (int t = 0; t < 4; t++)
-#pragma unroll
-                        for (int r = 0; r < 4; r++) {
-                            const int key = kt * KT + t * 16 + g * 4 + r;
-                            const float sc = key <= qpos[q] ? sacc[q][t][r] * sl2 : -INFINITY;
-                            sv[t][r] = sc;
-                            mt = fmaxf(mt, sc);
-                        }
-                }
-                mt = xor32_max(xor16_max(mt));
-                // unlike the prefill kernel's, a split past a row's position shows it no key
-                // at all: the running max stays -inf there, and the exponent base must not
-                // (-inf - -inf is NaN)
-                const float m_new = fmaxf(m_run[q], mt);
-                const float m_use = m_new == -INFINITY ? 0.f : m_new;
-                const float alpha = __builtin_amdgcn_exp2f(m_run[q] - m_use);
-                float ls = 0.f;
-#pragma unroll
-                for (int t = 0; t < 4; t++)
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        const float e = __builtin_amdgcn_exp2f(sv[t][r] - m_use);
-                        sv[t][r] = e;
-                        ls += e;
-                    }
-                ls = xor32_sum(xor16_sum(ls));
-                l_run[q] = l_run[q] * alpha + ls;
-                m_run[q] = m_new;
-                // the split's first tile finds O zero; alpha == 1 exactly where no max grew
-                if (kt > kt0 && __builtin_amdgcn_ballot_w64(alpha != 1.0f) != 0) {
-                    float ar[4];
-#pragma unroll
-                    for (int r = 0; r < 4; r++) ar[r] = __shfl(alpha, g * 4 + r, 64);
-#pragma unroll
-                    for (int d = 0; d < DT; d++)
-#pragma unroll
-                        for (int r = 0; r < 4; r++) oacc[q][d][r] *= ar[r];
-                }
-            }
-            const int q4 = fr >> 2, p4 = fr & 3;
-#pragma unroll
-            for (int c = 0; c < 2; c++) {
-                // P = hi + lo bf16 parts, as the prefill kernel
-                bf16x8_t ph[QG], pl[QG];
-#pragma unroll
-                for (int q = 0; q < QG; q++) {
-                    if (!ON[q]) continue;
-                    float e8[8];
-#pragma unroll
-                    for (int jj = 0; jj < 8; jj++) e8[jj] = pv[q][2 * c + (jj >> 2)][jj & 3];
-                    uint4 pp[2];
-                    split_bf16x8<2>(e8, pp);
-                    ph[q] = __builtin_bit_cast(bf16x8_t, pp[0]);
-                    pl[q] = __builtin_bit_cast(bf16x8_t, pp[1]);
-                }
-#pragma unroll
-                for (int d = 0; d < DT; d++) {
-                    const int vr = 32 * c + 4 * g + q4;
-                    const uint16_t* a0 = Vt + vr * HD + (((2 * d + (p4 >> 1)) ^ vswz(vr)) * 8) + (p4 & 1) * 4;
-                    const i16x4_t v0 =
-                        __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4_t*)(a0));
-                    const i16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (__attribute__((address_space(3))) i16x4_t*)(a0 + 16 * HD));
-                    const bf16x8_t vb8 =
-                        __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7));
-#pragma unroll
-                    for (int q = 0; q < QG; q++) {
-                        if (!ON[q]) continue;
-                        oacc[q][d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ph[q], vb8, oacc[q][d], 0, 0, 0);
-                        oacc[q][d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pl[q], vb8, oacc[q][d], 0, 0, 0);
-                    }
-                }
-            }
-        };
-    int kt = kt0;
-    auto run = [&](const int kend, auto q0c, auto q1c) {
-        for (; kt < kend; kt++) {
-            // into the other buffer: every wave finished tile kt-1 before the last barrier
-            if (kt + 1 < nkt) issue(kt + 1, cur ^ 1);
-            if constexpr (decltype(q0c)::value || decltype(q1c)::value)
-                tile(kt, Ks + cur * KT * HD, Vs + cur * KT * HD, q0c, q1c);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMAs of tile kt+1
-            __syncthreads();                                     // ... and every other wave's
-            cur ^= 1;
-        }
-    };
-    // tiles of this split each group takes: [kt0, gpos / KT] (none when the group's last
-    // position lies before the split or the group is padding); group 1 is the later one
-    const int nkt0 = gpos[0] >= k0 ? min(nkt, gpos[0] / KT + 1) : kt0;
-    const int nkt1 = gpos[1] >= k0 ? min(nkt, gpos[1] / KT + 1) : kt0;
-    if (nkt1 > kt0) {
-        run(nkt0, std::true_type{}, std::true_type{});
-        run(nkt1, std::false_type{}, std::true_type{});
-    } else {
-        run(nkt0, std::true_type{}, std::false_type{});
-    }
-    run(nkt, std::false_type{}, std::false_type{});
+    attn_mfma_walk<HD, PG, NW, true>(kb, vb, a.km, seq, kmax, k0, nkt, qf, qpos, gpos, gmin, oacc, m_run, l_run);
 
     // every real row of the block leaves its slot, also the rows this split showed no key
     // ((-inf, 0) and a zero O): the workspace is never assumed initialised
@@ -341,26 +164,6 @@ __global__ __launch_bounds__(256, 2) void attn_extend_kernel(ExtendAttnParams a)
             a.part_ml[pi * 2 + 1] = l_run[q];
         }
     }
-}
-
-// Merge of the splits of one (row, q head): grid (M, nq), HD threads.  The running maxima
-// are in the log2 domain (scores * log2(e) / sqrt(hd)), so the weights are exp2.
-template <int HD>
-__global__ __launch_bounds__(HD) void attn_extend_combine_kernel(ExtendAttnParams a) {
-    const int64_t m = blockIdx.x;
-    const int h = blockIdx.y, d = threadIdx.x;
-    const int64_t base = (m * a.nq + h) * (int64_t)a.nsplit;
-    float mn = -INFINITY;
-    for (int s = 0; s < a.nsplit; s++) mn = fmaxf(mn, a.part_ml[(base + s) * 2]);
-    float l = 0.f, ov = 0.f;
-    for (int s = 0; s < a.nsplit; s++) {
-        const float ms = a.part_ml[(base + s) * 2];
-        if (ms == -INFINITY) continue;   // no visible key: its O is not read
-        const float c = __builtin_amdgcn_exp2f(ms - mn);
-        l += a.part_ml[(base + s) * 2 + 1] * c;
-        ov += a.part_o[(base + s) * HD + d] * c;
-    }
-    a.out[m * (int64_t)a.nq * HD + (int64_t)h * HD + d] = f2bf(ov / l);
 }
 
 }  // namespace qie
@@ -425,10 +228,7 @@ int qie_attention_extend(const void* q, int64_t M, const int32_t* pos, int32_t r
     hipLaunchKernelGGL(k, grid, dim3(256), shm, st, a);
     QIE_LAUNCH_CHECK();
     if (a.nsplit > 1) {
-        if (cache->head_dim == 128)
-            hipLaunchKernelGGL(attn_extend_combine_kernel<128>, dim3((unsigned)M, (unsigned)n_heads), dim3(128), 0, st, a);
-        else
-            hipLaunchKernelGGL(attn_extend_combine_kernel<64>, dim3((unsigned)M, (unsigned)n_heads), dim3(64), 0, st, a);
+        launch_attn_combine<true>(cache->head_dim, M, n_heads, a.nsplit, a.part_o, a.part_ml, a.out, st);
         QIE_LAUNCH_CHECK();
     }
     return 0;

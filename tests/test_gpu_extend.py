@@ -34,18 +34,18 @@ def _kv(oracle, hd, nkv, B):
 
 def _cache(oracle, kc_h, vc_h, paged):
     """(descriptor, keepalive) of the cache, contiguous or paged with shuffled 128-token pages."""
-    B, _, nkv, _, hd = kc_h.shape
+    B, _, nkv, maxc, hd = kc_h.shape
     if paged:
         pg = Paged(oracle, kc_h, vc_h, T, seed=7)
         return pg.cache(), pg
     kc, vc = G.dev(kc_h), G.dev(vc_h)
-    return _contig(kc, vc, L, nkv, hd, MAXC), (kc, vc)
+    return _contig(kc, vc, L, nkv, hd, maxc), (kc, vc)
 
 
-def _extend(qlib, c, q, pos, rps, nq, hd, poison=False):
+def _extend(qlib, c, q, pos, rps, nq, hd, poison=False, maxc=MAXC):
     """Runs the operator with `out` framed by one sentinel row on each side; returns [M][nq*hd]."""
     M = q.shape[0]
-    nbytes = qlib.qie_attention_extend_workspace_bytes(M, nq, hd, MAXC)
+    nbytes = qlib.qie_attention_extend_workspace_bytes(M, nq, hd, maxc)
     ws = G.zeros_bytes(nbytes)
     if poison:
         assert nbytes > 0, "the poisoned case must be a multi-split one"
@@ -157,6 +157,34 @@ def test_extend_poisoned_workspace(oracle, qlib, paged):
     q = rand_bf16(oracle, (n, nq * hd), seed=23)
     got = _extend(qlib, c, q, np.arange(pos0, pos0 + n, dtype=np.int32), n, nq, hd, poison=True)
     _check(got, _want(oracle, q, kc_h, vc_h, 0, pos0, nq, nkv, hd), "poisoned workspace")
+
+
+@pytest.mark.parametrize("paged", [False, True])
+@pytest.mark.parametrize("P", [33, 130])
+@pytest.mark.parametrize("hd,nq,nkv", [(64, 4, 4), (64, 14, 2), (128, 28, 4)])
+def test_extend_single_split_equals_prefill_bitwise(oracle, qlib, hd, nq, nkv, P, paged):
+    """P rows at positions 0..P-1 on a 512-key cache: qie_attention takes its MFMA prefill
+    kernel (rows_per_seq >= 32), qie_attention_extend has exactly one split, and both walk the
+    key tiles with the one attn_mfma_walk.  A row's result depends only on which key tiles it
+    sees and on its own masked scores, not on how rows are packed into 16-row groups and
+    workgroups (consecutive tokens there, flattened (token, head) pairs here): equal bit for bit."""
+    maxc = 512
+    assert qlib.qie_attention_extend_workspace_bytes(P, nq, hd, maxc) == 0   # one split, no merge
+    kc_h = rand_bf16(oracle, (1, L, nkv, maxc, hd), seed=hd + nkv + P)
+    vc_h = rand_bf16(oracle, (1, L, nkv, maxc, hd), seed=hd + nkv + P + 1)
+    c, keep = _cache(oracle, kc_h, vc_h, paged)
+    q = rand_bf16(oracle, (P, nq * hd), seed=P)
+    pos = np.arange(P, dtype=np.int32)
+    got = _extend(qlib, c, q, pos, P, nq, hd, maxc=maxc)
+    out = G.zeros_bf16(P, nq * hd)
+    G.check(qlib.qie_attention(G.p(G.dev(q)), P, G.p(G.dev(pos)), P, C.byref(c), LAYER, nq, G.p(out), None, None),
+            "qie_attention")
+    want = G.host_bf16(out)
+    d = np.abs(G.bf(got) - G.bf(want))
+    print(f"hd {hd} nq {nq} nkv {nkv} P {P} paged {paged}: rows differing {int((got != want).any(axis=1).sum())}, "
+          f"max |d| {d.max():.3e}")
+    assert np.isfinite(G.bf(want)).all() and want.any()
+    assert np.array_equal(got, want)
 
 
 def test_extend_bad_arguments(qlib):
