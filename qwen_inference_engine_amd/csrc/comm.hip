@@ -335,7 +335,7 @@ static void peer_pool_put(char* p) {
 // written as 8-byte words {e + 1, f32} by relaxed SYSTEM-scope atomic stores (write-through to
 // the owner's uncached buffer, single-copy atomic), and the reader polls the words themselves:
 // no system fence before a flag, no flag round trip, no fence after it.  PUSHED: the producer
-// GEMV already wrote this rank's words from its epilogue (set_gemv_push), so the kernel only
+// GEMV already wrote this rank's words from its epilogue (LinearExtras::push), so the kernel only
 // waits, reduces and advances the generation.  A word of generation e - 2 (the other value
 // the slot can hold: parity reuse, as above) carries tag e - 1, never e + 1.
 template <bool PUSHED>

@@ -15,6 +15,7 @@
 // embedding], captured once into a hipGraph; positions and token ids live in
 // device memory so the graph replays without host edits.
 #include "qie_common.hpp"
+#include "linear_plan.hpp"
 #include "../../include/qie/qie_engine.h"
 #include "qie_index.hpp"
 #include "qie_comm.hpp"
@@ -25,10 +26,6 @@
 #include <vector>
 
 namespace qie {
-int gemv(const qie_linear_args* a, hipStream_t st);
-int gemv_rope(const qie_linear_args* a, const int32_t* pos, const float* cs, const float* sn, int hd, int64_t rows,
-              hipStream_t st);
-int gemm(const qie_linear_args* a, hipStream_t st);
 bool dec8_applies(const qie_linear_args* a);
 int dec8_reserve(hipStream_t st);
 bool persist_supported(const qie_model_spec& s, int B, int tp, bool fp8, bool paged, int ncu, const char** why);
@@ -534,11 +531,11 @@ static int row_parallel(qie_batch* b, qie_linear_args& a, uint16_t* x, float* pa
     // exchange kernel only waits, reduces and adds (comm.hip peer_tag_kernel)
     PeerPush pp;
     if (rows == 1 && e->comm->peer_push(&pp, n)) {
-        set_gemv_push(&pp);
-        const int rc = qie_linear(&a, e->stream);
-        const bool taken = gemv_push_taken();
-        set_gemv_push(nullptr);
-        QIE_TRY(rc);
+        bool taken = false;
+        LinearExtras ex;
+        ex.push = &pp;
+        ex.push_taken = &taken;
+        QIE_TRY(linear(&a, ex, e->stream));
         if (taken) return e->comm->allreduce_residual_pushed(x, n, e->stream);
         return e->comm->allreduce_residual_bf16(part, x, n, e->stream);
     }
@@ -563,7 +560,7 @@ static int prenorm(qie_batch* b, qie_linear_args& a, int64_t M) {
 }
 
 // batch 1, REF numerics, no qk-norm (Qwen2): the decode QKV projection's epilogue rotates q
-// and k (gemv_rope), so the attention's critical path loses the position -> RoPE-table round
+// and k (LinearExtras::rope), so the attention's critical path loses the position -> RoPE-table round
 // trip (QIE_ATTN_PREROPED)
 static bool rope_in_projection(const qie_batch* b) {
     const qie_model_spec& s = b->e->spec;
@@ -598,8 +595,9 @@ static int enqueue_layer_decode(qie_batch* b, int l) {
     a.norm_w = L.attn_norm; a.norm_eps = s.rms_eps; a.numerics = s.numerics;
     QIE_TRY(prenorm(b, a, B));
     const bool rope_in_proj = rope_in_projection(b);
-    if (rope_in_proj) QIE_TRY(gemv_rope(&a, b->d_pos, e->rope_cos, e->rope_sin, (int)hd, QD + KD, st));
-    else QIE_TRY(gemv(&a, st));
+    LinearExtras ex;
+    if (rope_in_proj) ex.rope = RopeArgs{b->d_pos, e->rope_cos, e->rope_sin, (int)hd, QD + KD};
+    QIE_TRY(linear(&a, ex, st));
 
     set_decode_rope_cur(b->d_rope_cur);
     const int arc = qie_attention_decode(b->qkv, B, b->d_pos, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, e->sh.nq,
@@ -623,7 +621,7 @@ static int enqueue_layer_decode(qie_batch* b, int l) {
     a.epilogue = QIE_EPI_SWIGLU;
     a.norm_w = L.ffn_norm; a.norm_eps = s.rms_eps; a.numerics = s.numerics;
     QIE_TRY(prenorm(b, a, B));
-    QIE_TRY(gemv(&a, st));
+    QIE_TRY(linear(&a, LinearExtras{}, st));
 
     a = lin_proj(e);
     a.x = b->h; a.ldx = I;
@@ -684,7 +682,7 @@ static int enqueue_head(qie_batch* b, const uint16_t* x, int64_t ldx, int m0, in
         a.argmax_keys = (uint64_t*)(b->d_keys + m0);
         a.key_col0 = e->sh.vocab0;   // keys carry global vocab ids
     }
-    QIE_TRY(gemv(&a, st));
+    QIE_TRY(linear(&a, LinearExtras{}, st));
     if (greedy && use_comm(e)) QIE_TRY(e->comm->allreduce_max_u64((uint64_t*)(b->d_keys + m0), M, st));
     if (!greedy) {
         const uint16_t* lg = b->logits + (int64_t)m0 * Vl;
@@ -1917,9 +1915,10 @@ int qie_batch_time_kernel(qie_batch* b, int32_t which, int32_t iters, double* av
         }
         double lb = 0;
         qie_linear_args a = args_for(l, &lb);
+        LinearExtras ex;
         if (which == 2 && rp)   // as the step runs it
-            return gemv_rope(&a, b->d_pos, e->rope_cos, e->rope_sin, (int)s.head_dim, QD + KD, e->stream);
-        return qie_linear(&a, e->stream);
+            ex.rope = RopeArgs{b->d_pos, e->rope_cos, e->rope_sin, (int)s.head_dim, QD + KD};
+        return linear(&a, ex, e->stream);
     };
     if (which != 5) args_for(0, &by);
     hipEvent_t t0, t1;
@@ -1958,37 +1957,6 @@ int qie_batch_debug_step(qie_batch* b, const qie_sampling* smp, int32_t* next_id
     return sync_ids(b, next_ids);
 }
 
-int qie_linear(const qie_linear_args* a, void* stream) {
-    QIE_REQUIRE(a && a->x && a->y && a->w[0] && a->M > 0 && a->K > 0 && a->N > 0, "qie_linear: bad arguments");
-    QIE_REQUIRE(a->K % 8 == 0 && a->ldx >= a->K && a->ldx % 8 == 0, "qie_linear: K and ldx must be multiples of 8");
-    QIE_REQUIRE(((uintptr_t)a->x % 16) == 0, "qie_linear: x must be 16-byte aligned");
-    for (int i = 0; i < 3; i++)
-        QIE_REQUIRE(((uintptr_t)a->w[i] % 16) == 0, "qie_linear: weight segment %d must be 16-byte aligned", i);
-    if (a->epilogue == QIE_EPI_SWIGLU) {
-        QIE_REQUIRE(a->w[1] && a->seg_rows[0] == a->N && a->seg_rows[1] == a->N && a->ldy >= a->N,
-                    "qie_linear: SWIGLU needs w[0]=gate, w[1]=up with N rows each");
-    } else {
-        QIE_REQUIRE(a->seg_rows[0] + a->seg_rows[1] + a->seg_rows[2] == a->N && a->ldy >= a->N,
-                    "qie_linear: seg_rows must sum to N");
-        QIE_REQUIRE(a->seg_rows[1] == 0 || a->w[1], "qie_linear: missing weight segment 1");
-        QIE_REQUIRE(a->seg_rows[2] == 0 || a->w[2], "qie_linear: missing weight segment 2");
-    }
-    QIE_REQUIRE(a->epilogue >= 0 && a->epilogue <= 3, "qie_linear: bad epilogue");
-    QIE_REQUIRE(a->epilogue != QIE_EPI_F32 || (a->bias[0] == nullptr && a->bias[1] == nullptr && a->bias[2] == nullptr),
-                "qie_linear: F32 (partial-sum) epilogue takes no bias");
-    QIE_REQUIRE(a->argmax_keys == nullptr || a->epilogue == QIE_EPI_STORE, "qie_linear: arg-max needs STORE");
-    const bool act_fp8 = (a->flags & QIE_LINEAR_ACT_FP8) != 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (act_fp8) return gemm(a, st);   // fp8 activations: the block-scaled MFMA GEMM at every M
-    QIE_REQUIRE(!(a->flags & QIE_LINEAR_FP8_T16) ||
-                    ((a->flags & QIE_LINEAR_FP8) && a->M >= 1 && a->M <= 16 && a->K % 64 == 0 &&
-                     (a->epilogue == QIE_EPI_SWIGLU ? a->N % 16 == 0
-                                                    : a->seg_rows[0] % 16 == 0 && a->seg_rows[1] % 16 == 0 &&
-                                                          a->seg_rows[2] % 16 == 0)),
-                "qie_linear: 16-row tiled fp8 weights are read by the batched-decode kernels only (M <= 16, K %% 64 == 0, "
-                "segments of whole 16-row tiles) and, with fp8 activations, the block-scaled GEMM");
-    if (a->M <= 16) return gemv(a, st);   // GEMV (M = 1..8) or the skinny MFMA kernel (2..16)
-    return gemm(a, st);
-}
+int qie_linear(const qie_linear_args* a, void* stream) { return linear(a, LinearExtras{}, (hipStream_t)stream); }
 
 }  // extern "C"

@@ -15,6 +15,7 @@
 //   * blockIdx.x runs over M tiles so the blocks sharing a weight tile are
 //     adjacent in dispatch order (weights streamed ~once, activations L2/MALL).
 #include "qie_common.hpp"
+#include "launch_util.hpp"
 #include "../../include/qie/qie_ops.h"
 
 #include <map>
@@ -985,20 +986,13 @@ template <int EPI>
 static int launch_gemm8_t(const GemmParams& p, int n_mt, int n_tiles, const G8Split& sk, hipStream_t st) {
     const void* fn = (const void*)gemm8_kernel<EPI>;
     constexpr size_t shm = 2 * (size_t)g8::BUF;
-    static bool raised = false;
-    if (!raised) {
-        QIE_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-        raised = true;
-    }
+    QIE_TRY(raise_dynamic_lds(fn, shm));
     hipLaunchKernelGGL((gemm8_kernel<EPI>), dim3((unsigned)(n_tiles * sk.splitk)), dim3(512), shm, st, p, n_mt, sk);
     QIE_LAUNCH_CHECK();
     return 0;
 }
 static int launch_gemm8(int epi, const GemmParams& p, int n_mt, int n_tiles, const G8Split& sk, hipStream_t st) {
-    if (epi == QIE_EPI_SWIGLU) return launch_gemm8_t<QIE_EPI_SWIGLU>(p, n_mt, n_tiles, sk, st);
-    if (epi == QIE_EPI_RESIDUAL) return launch_gemm8_t<QIE_EPI_RESIDUAL>(p, n_mt, n_tiles, sk, st);
-    if (epi == QIE_EPI_F32) return launch_gemm8_t<QIE_EPI_F32>(p, n_mt, n_tiles, sk, st);
-    return launch_gemm8_t<QIE_EPI_STORE>(p, n_mt, n_tiles, sk, st);
+    return dispatch_epi(epi, [&](auto E) { return launch_gemm8_t<decltype(E)::value>(p, n_mt, n_tiles, sk, st); });
 }
 
 // Split-K slabs + tickets, one set per stream (streams of one device may run GEMMs at the same
@@ -1038,11 +1032,7 @@ template <int EPI>
 static int launch_gemm8sk_t(const GemmParams& p, int n_mt, int grid, const G8Stream& sk, hipStream_t st) {
     const void* fn = (const void*)gemm8sk_kernel<EPI>;
     constexpr size_t shm = 2 * (size_t)g8::BUF;
-    static bool raised = false;
-    if (!raised) {
-        QIE_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-        raised = true;
-    }
+    QIE_TRY(raise_dynamic_lds(fn, shm));
     hipLaunchKernelGGL((gemm8sk_kernel<EPI>), dim3((unsigned)grid), dim3(512), shm, st, p, n_mt, sk);
     QIE_LAUNCH_CHECK();
     return 0;
@@ -1065,10 +1055,7 @@ static int launch_gemm8sk(int epi, const GemmParams& p, int n_mt, int tiles, hip
     sk.slab = ws.slab;
     sk.cnt = ws.cnt;
     *launched = true;
-    if (epi == QIE_EPI_SWIGLU) return launch_gemm8sk_t<QIE_EPI_SWIGLU>(p, n_mt, grid, sk, st);
-    if (epi == QIE_EPI_RESIDUAL) return launch_gemm8sk_t<QIE_EPI_RESIDUAL>(p, n_mt, grid, sk, st);
-    if (epi == QIE_EPI_F32) return launch_gemm8sk_t<QIE_EPI_F32>(p, n_mt, grid, sk, st);
-    return launch_gemm8sk_t<QIE_EPI_STORE>(p, n_mt, grid, sk, st);
+    return dispatch_epi(epi, [&](auto E) { return launch_gemm8sk_t<decltype(E)::value>(p, n_mt, grid, sk, st); });
 }
 
 // parts per tile: the fewest rounds of (tile, part) items over the CUs, in units of a tile
@@ -1098,11 +1085,7 @@ template <int EPI, int BNT>
 static int launch_gemm_big_t(const GemmParams& p, int n_mt, int n_tiles, hipStream_t st) {
     const void* fn = (const void*)gemm_big_kernel<EPI, BNT>;
     constexpr size_t shm = (size_t)big::SLOTS * big::slot_bytes(BNT);
-    static bool raised = false;
-    if (!raised) {
-        QIE_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-        raised = true;
-    }
+    QIE_TRY(raise_dynamic_lds(fn, shm));
     hipLaunchKernelGGL((gemm_big_kernel<EPI, BNT>), dim3((unsigned)n_tiles), dim3(512), shm, st, p, n_mt);
     QIE_LAUNCH_CHECK();
     return 0;
@@ -1110,26 +1093,18 @@ static int launch_gemm_big_t(const GemmParams& p, int n_mt, int n_tiles, hipStre
 
 template <int BNT>
 static int launch_gemm_big(int epi, const GemmParams& p, int n_mt, int n_tiles, hipStream_t st) {
-    if (epi == QIE_EPI_SWIGLU) return launch_gemm_big_t<QIE_EPI_SWIGLU, BNT>(p, n_mt, n_tiles, st);
-    if (epi == QIE_EPI_RESIDUAL) return launch_gemm_big_t<QIE_EPI_RESIDUAL, BNT>(p, n_mt, n_tiles, st);
-    if (epi == QIE_EPI_F32) return launch_gemm_big_t<QIE_EPI_F32, BNT>(p, n_mt, n_tiles, st);
-    return launch_gemm_big_t<QIE_EPI_STORE, BNT>(p, n_mt, n_tiles, st);
+    return dispatch_epi(epi, [&](auto E) { return launch_gemm_big_t<decltype(E)::value, BNT>(p, n_mt, n_tiles, st); });
 }
 
 template <int WT>
 static int launch_gemm(int epi, unsigned gm, const GemmParams& p, size_t shm, hipStream_t st) {
-    if (epi == QIE_EPI_SWIGLU) {
-        hipLaunchKernelGGL((gemm_kernel<QIE_EPI_SWIGLU, WT>), dim3(gm, (unsigned)cdiv(p.N, 64)), dim3(256), shm, st, p);
-    } else if (epi == QIE_EPI_RESIDUAL) {
-        hipLaunchKernelGGL((gemm_kernel<QIE_EPI_RESIDUAL, WT>), dim3(gm, (unsigned)cdiv(p.N, BN)), dim3(256), shm, st,
-                           p);
-    } else if (epi == QIE_EPI_F32) {
-        hipLaunchKernelGGL((gemm_kernel<QIE_EPI_F32, WT>), dim3(gm, (unsigned)cdiv(p.N, BN)), dim3(256), shm, st, p);
-    } else {
-        hipLaunchKernelGGL((gemm_kernel<QIE_EPI_STORE, WT>), dim3(gm, (unsigned)cdiv(p.N, BN)), dim3(256), shm, st, p);
-    }
-    QIE_LAUNCH_CHECK();
-    return 0;
+    return dispatch_epi(epi, [&](auto E) {
+        constexpr int EPI = decltype(E)::value;
+        const unsigned gn = (unsigned)cdiv(p.N, EPI == QIE_EPI_SWIGLU ? 64 : BN);   // SwiGLU: 64 outputs per tile
+        hipLaunchKernelGGL((gemm_kernel<EPI, WT>), dim3(gm, gn), dim3(256), shm, st, p);
+        QIE_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -1458,11 +1433,7 @@ template <int EPI, bool T16>
 static int launch_gemm8mx_t(const MxParams& p, int n_mt, int n_tiles, const G8Split& sk, hipStream_t st) {
     const void* fn = (const void*)gemm8mx_kernel<EPI, T16>;
     constexpr size_t shm = 2 * (size_t)g8::BUF;
-    static bool raised = false;
-    if (!raised) {
-        QIE_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-        raised = true;
-    }
+    QIE_TRY(raise_dynamic_lds(fn, shm));
     static const int dbg = dev_env("QIE_MX_DBG", 0);
     hipLaunchKernelGGL((gemm8mx_kernel<EPI, T16>), dim3((unsigned)(n_tiles * sk.splitk)), dim3(512), shm, st, p, n_mt,
                        sk, dbg);
@@ -1471,10 +1442,7 @@ static int launch_gemm8mx_t(const MxParams& p, int n_mt, int n_tiles, const G8Sp
 }
 template <bool T16>
 static int launch_gemm8mx(int epi, const MxParams& p, int n_mt, int n_tiles, const G8Split& sk, hipStream_t st) {
-    if (epi == QIE_EPI_SWIGLU) return launch_gemm8mx_t<QIE_EPI_SWIGLU, T16>(p, n_mt, n_tiles, sk, st);
-    if (epi == QIE_EPI_RESIDUAL) return launch_gemm8mx_t<QIE_EPI_RESIDUAL, T16>(p, n_mt, n_tiles, sk, st);
-    if (epi == QIE_EPI_F32) return launch_gemm8mx_t<QIE_EPI_F32, T16>(p, n_mt, n_tiles, sk, st);
-    return launch_gemm8mx_t<QIE_EPI_STORE, T16>(p, n_mt, n_tiles, sk, st);
+    return dispatch_epi(epi, [&](auto E) { return launch_gemm8mx_t<decltype(E)::value, T16>(p, n_mt, n_tiles, sk, st); });
 }
 
 // QIE_LINEAR_ACT_FP8 (qie_ops.h): every M, one 256x256 kernel; split-K where the tiles do not

@@ -15,6 +15,8 @@
 // Grid is persistent-ish: min(tasks/4, CUs * blocks_per_cu) blocks of 4 waves
 // that grid-stride over row tasks, so the norm prologue runs once per block.
 #include "qie_common.hpp"
+#include "launch_util.hpp"
+#include "linear_plan.hpp"
 #include "../../include/qie/qie_ops.h"
 
 #include <cstdlib>
@@ -1142,262 +1144,180 @@ __global__ __launch_bounds__(NW * 64) void skinny_mfma_kernel(GemvParams p) {
     }
 }
 
-// block size bound of the one-block-per-CU GEMV variant (9 waves: Qwen2-7B QKV; O / down use 7)
-constexpr int kGemvBalancedThreads = 576;
+// ---------------------------------------------------------------------------
+// Host side: plan_linear (linear_plan.hpp) decides, the launchers below map the plan to an
+// instantiation and launch it on launch_geometry's grid.
 
-static int env_int_gemv(const char* name, int dflt) { return dev_env(name, dflt); }
+// The dev knobs of the plan, read in one place (development build: the environment at every
+// call, so a tool may change a knob between launches; shipped library: the defaults).
+static Knobs dev_knobs() {
+    Knobs k;
+    k.epre = dev_env("QIE_GEMV_EPRE", k.epre);
+    k.mkdiv = dev_env("QIE_GEMV_MKDIV", k.mkdiv);
+    k.gemv_dbg = dev_env("QIE_GEMV_DBG", k.gemv_dbg);
+    k.rpw = dev_env("QIE_GEMV_RPW", k.rpw);
+    k.rpw_lm = dev_env("QIE_GEMV_RPW_LM", k.rpw);
+    k.blocks_per_cu = dev_env("QIE_GEMV_BLOCKS_PER_CU", k.blocks_per_cu);
+    k.xfirst = dev_env("QIE_GEMV_XFIRST", k.xfirst);
+    k.xreg = dev_env("QIE_GEMV_XREG", k.xreg);
+    k.xreg4 = dev_env("QIE_GEMV_XREG4", k.xreg4);
+    k.xreg4_lm = dev_env("QIE_GEMV_XREG4_LM", k.xreg4_lm);
+    k.xreg4_sw = dev_env("QIE_GEMV_XREG4_SW", k.xreg4_sw);
+    k.swiglu_bpc = dev_env("QIE_GEMV_SWIGLU_BPC", k.swiglu_bpc);
+    k.lm_bpc = dev_env("QIE_GEMV_LM_BPC", k.lm_bpc);
+    k.res_bpc = dev_env("QIE_GEMV_RES_BPC", k.res_bpc);
+    k.qkv_bpc = dev_env("QIE_GEMV_QKV_BPC", k.qkv_bpc);
+    k.balanced = dev_env("QIE_GEMV_BALANCED", k.balanced);
+    k.rpw1 = dev_env("QIE_GEMV_RPW1", k.rpw1);
+    k.skinny_mfma = dev_env("QIE_SKINNY_MFMA", k.skinny_mfma);
+    k.skinny_lds64 = dev_env("QIE_SKINNY_LDS64", k.skinny_lds64);
+    k.skinny_xl = dev_env("QIE_SKINNY_XL", k.skinny_xl);
+    k.skinny_dbg = dev_env("QIE_SKINNY_DBG", k.skinny_dbg);
+    k.skinny_bpc = dev_env("QIE_SKINNY_BPC", k.skinny_bpc);
+    k.dec8 = dev_env("QIE_DEC8", k.dec8);
+    k.dec8_split = dev_env("QIE_DEC8_SPLIT", k.dec8_split);
+    k.dec8_split_ku = dev_env("QIE_DEC8_SPLIT_KU", k.dec8_split_ku);
+    k.t16_skinny = dev_env("QIE_T16_SKINNY", k.t16_skinny);
+    return k;
+}
 
-// UO: chunks per row in flight when K needs fewer than the default 8 wave-loads per row
-// (0 = default).  A slot past K re-reads the row's last 16 B, so at K = 896 (Qwen2-0.5B)
-// the default issued 8 loads per row of which 6 were duplicates.
+// dynamic LDS above 64 KiB (x staged at K > 32 Ki): the kernels' limit is raised to 160 KiB
+static size_t gemv_lds_limit(size_t shm) { return shm > 65536 ? 160 * 1024 : 0; }
+
 template <int MT, int RPW, int EPI, int XCH, int WT, int UO = 0>
-static int launch_gemv_t(const GemvParams& p, hipStream_t st, int blocks_per_cu) {
+static int launch_gemv_t(const GemvParams& p, const LinearPlan& pl, hipStream_t st) {
     constexpr int U = UO ? UO : ((RPW >= 4) ? 4 : 8);
     const void* fn = (const void*)gemv_kernel<MT, RPW, EPI, U, XCH, WT>;
-    const size_t shm = (p.xlds ? (size_t)MT * p.K * 2 : 0) + 64;
-    if (shm > 65536) {
-        static bool raised = false;   // per instantiation
-        if (!raised) {
-            QIE_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            raised = true;
-        }
-    }
-    const int64_t n_blocks_needed = (p.n_tasks + 3) / 4;
-    int64_t cap = (int64_t)device_cu_count() * blocks_per_cu;
-    int64_t grid64 = std::max<int64_t>(1, std::min(n_blocks_needed, cap));
-    if (blocks_per_cu == -2) {
-        // Full-residency grid-stride grid (the SwiGLU default): every CU holds the same number
-        // of blocks for the whole launch.  The balanced grid below gives every WAVE the same
-        // task count but leaves CUs with 3 and 4 blocks (948 blocks at 4 per CU for Qwen2-7B
-        // gate/up): in-graph gate/up 43.0 -> 42.2 us, 358.9 -> 361.5 tok/s (same box, A/B)
-        static size_t cached_shm2 = 0;
-        static int cached_nb2 = 0;
-        int nb = cached_shm2 == shm ? cached_nb2 : 0;
-        if (nb == 0) {
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, shm) != hipSuccess || nb < 1) nb = 2;
-            cached_shm2 = shm;
-            cached_nb2 = nb;
-        }
-        grid64 = std::max<int64_t>(1, std::min(n_blocks_needed, (int64_t)device_cu_count() * nb));
-    } else if (blocks_per_cu <= 0) {
-        // Balanced persistent grid (default): the grid is what fits on the chip at once, and
-        // the task count per wave is made (nearly) equal — e.g. gate/up (18,944 tasks) on
-        // 768 resident blocks: 7 rounds over 677 blocks instead of 4.6 rounds over 1024
-        // blocks, whose last 0.6 round ran the chip at 60 % of its waves.
-        static size_t cached_shm = 0;   // per instantiation: occupancy depends on LDS bytes
-        static int cached_nb = 0;
-        int nb = cached_shm == shm ? cached_nb : 0;
-        if (nb == 0) {
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 256, shm) != hipSuccess || nb < 1) nb = 2;
-            cached_shm = shm;
-            cached_nb = nb;
-        }
-        cap = (int64_t)device_cu_count() * nb;
-        const int64_t rounds = (p.n_tasks + 4 * cap - 1) / (4 * cap);
-        grid64 = std::max<int64_t>(1, (p.n_tasks + 4 * rounds - 1) / (4 * rounds));
-    }
-    // One block per CU for mid-sized GEMVs (4..16 row tasks per CU: Qwen2-7B QKV 2,304, O and
-    // down 1,792): 448 four-wave blocks on 256 CUs left 64 CUs with half the waves, and the
-    // whole launch waited for the doubly loaded CUs.  Block = ceil(tasks / CUs) waves, so every
-    // CU streams the same rows.  (SwiGLU and lm_head have > 9 tasks per CU: grid-stride.)
-    int threads = 256;
-    const int64_t cus = device_cu_count();
-    // one row per wave: up to 16 waves per block (Qwen2-7B O / down: 14 one-row waves per CU)
-    constexpr int LBB = RPW == 1 ? 1024 : kGemvBalancedThreads;
-    if (MT == 1 && WT == 0 && EPI != QIE_EPI_SWIGLU && blocks_per_cu < 0 && p.n_tasks > 4 * cus &&
-        p.n_tasks <= (LBB / 64) * cus &&
-        env_int_gemv("QIE_GEMV_BALANCED", 1) != 0) {
-        const int64_t nw = (p.n_tasks + cus - 1) / cus;
-        threads = (int)(64 * nw);
-        grid64 = (p.n_tasks + nw - 1) / nw;
-    }
-    const unsigned grid = (unsigned)grid64;
-    if (threads > 256) {
+    if (pl.block_waves) {   // one block per CU: the instantiation bounded at its block size
         if constexpr (MT == 1 && WT == 0 && EPI != QIE_EPI_SWIGLU) {
-            const void* fb = (const void*)gemv_kernel<MT, RPW, EPI, U, XCH, WT, LBB>;
-            if (shm > 65536) {
-                static bool raised_b = false;
-                if (!raised_b) {
-                    QIE_HIP(hipFuncSetAttribute(fb, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    raised_b = true;
-                }
-            }
-            hipLaunchKernelGGL((gemv_kernel<MT, RPW, EPI, U, XCH, WT, LBB>), dim3(grid), dim3(threads), shm, st, p);
+            constexpr int LBB = RPW == 1 ? 1024 : kGemvBalancedThreads;
+            const LaunchGeom g = launch_geometry(pl, device_cu_count(), 0);
+            QIE_TRY(raise_dynamic_lds((const void*)gemv_kernel<MT, RPW, EPI, U, XCH, WT, LBB>, gemv_lds_limit(g.lds_bytes)));
+            hipLaunchKernelGGL((gemv_kernel<MT, RPW, EPI, U, XCH, WT, LBB>), dim3(g.grid), dim3(g.threads), g.lds_bytes,
+                               st, p);
             QIE_LAUNCH_CHECK();
             return 0;
         }
     }
-    hipLaunchKernelGGL((gemv_kernel<MT, RPW, EPI, U, XCH, WT>), dim3(grid), dim3(threads), shm, st, p);
+    QIE_TRY(raise_dynamic_lds(fn, gemv_lds_limit(pl.lds_bytes)));
+    const int nb = pl.needs_occupancy() ? resident_blocks_per_cu(fn, 256, pl.lds_bytes, 2) : 0;
+    const LaunchGeom g = launch_geometry(pl, device_cu_count(), nb);
+    hipLaunchKernelGGL((gemv_kernel<MT, RPW, EPI, U, XCH, WT>), dim3(g.grid), dim3(g.threads), g.lds_bytes, st, p);
     QIE_LAUNCH_CHECK();
     return 0;
 }
 
 template <int MT, int XCH, int WT = 0, int UO = 0>
-static int launch_gemv_m(const GemvParams& p, int rpw, int epi, hipStream_t st, int bpc) {
+static int launch_gemv_m(const GemvParams& p, const LinearPlan& pl, hipStream_t st) {
     if constexpr (MT == 1 && XCH == 1 && WT == 0) {   // one row per wave (O / down, x beside the weights)
-        if (rpw == 1 && epi == QIE_EPI_RESIDUAL) return launch_gemv_t<1, 1, QIE_EPI_RESIDUAL, 1, 0, UO>(p, st, bpc);
-        if (rpw == 1 && epi == QIE_EPI_STORE) return launch_gemv_t<1, 1, QIE_EPI_STORE, 1, 0, UO>(p, st, bpc);
+        if (pl.rpw == 1 && pl.epi == QIE_EPI_RESIDUAL) return launch_gemv_t<1, 1, QIE_EPI_RESIDUAL, 1, 0, UO>(p, pl, st);
+        if (pl.rpw == 1 && pl.epi == QIE_EPI_STORE) return launch_gemv_t<1, 1, QIE_EPI_STORE, 1, 0, UO>(p, pl, st);
     }
-    if (epi == QIE_EPI_SWIGLU) {
-        return rpw >= 4 ? launch_gemv_t<MT, 4, QIE_EPI_SWIGLU, XCH, WT, UO>(p, st, bpc)
-                        : launch_gemv_t<MT, 2, QIE_EPI_SWIGLU, XCH, WT, UO>(p, st, bpc);
-    } else if (epi == QIE_EPI_RESIDUAL) {
-        return rpw >= 4 ? launch_gemv_t<MT, 4, QIE_EPI_RESIDUAL, XCH, WT, UO>(p, st, bpc)
-                        : launch_gemv_t<MT, 2, QIE_EPI_RESIDUAL, XCH, WT, UO>(p, st, bpc);
-    } else if (epi == QIE_EPI_F32) {
-        return rpw >= 4 ? launch_gemv_t<MT, 4, QIE_EPI_F32, XCH, WT, UO>(p, st, bpc)
-                        : launch_gemv_t<MT, 2, QIE_EPI_F32, XCH, WT, UO>(p, st, bpc);
-    }
-    return rpw >= 4 ? launch_gemv_t<MT, 4, QIE_EPI_STORE, XCH, WT, UO>(p, st, bpc)
-                    : launch_gemv_t<MT, 2, QIE_EPI_STORE, XCH, WT, UO>(p, st, bpc);
-}
-// x-first prologue variants (MT = 1 only): XCH 2048-element x chunks per thread
-static int launch_gemv_1(const GemvParams& p, int rpw, int epi, hipStream_t st, int bpc, int xch) {
-    // Chunks in flight per row sized to K (bf16 wave-loads per row n), so no load slot
-    // re-reads the row's tail: n <= 2 (Qwen2-0.5B, K = 896): 2 instead of 8 slots, 6 of
-    // them duplicates — lm_head 72.1 -> 47.4 us, gate/up 8.4 -> 6.3, decode 1,283 -> 1,471
-    // tok/s; n = 7 (Qwen2-7B, K = 3,584): 7 instead of 8 — gate/up 44.2 -> 42.9, QKV
-    // 9.67 -> 9.41 us, 349 -> 354 tok/s, but lm_head 166 -> 175 us (25 row tasks per wave:
-    // there the 8th slot's duplicate costs less than the bytes in flight it drops), so the
-    // vocabulary projection keeps 8; n = 10 (Qwen3-14B, K = 5,120): 5 per pass, two passes.
-    const int64_t n = (p.K + 511) / 512;   // bf16 wave-loads per row
-    const bool vocab = p.n_tasks * rpw >= 65536;
-    const int64_t ub = (n + (n + 7) / 8 - 1) / ((n + 7) / 8);   // balanced slots per pass (<= 8)
-    if (xch == 4) {   // fused norm, normalised x in every wave's registers
-        if (n <= 2) return launch_gemv_m<1, 4, 0, 2>(p, rpw, epi, st, bpc);
-        if (n == 7 && !vocab) return launch_gemv_m<1, 4, 0, 7>(p, rpw, epi, st, bpc);
-        return launch_gemv_m<1, 4, 0, 8>(p, rpw, epi, st, bpc);
-    }
-    if (xch == 3) {   // fused norm, x in registers: one batch of wave-loads covers a row
-        if (n <= 2) return launch_gemv_m<1, 3, 0, 2>(p, rpw, epi, st, bpc);
-        if (n == 7 && !vocab) return launch_gemv_m<1, 3, 0, 7>(p, rpw, epi, st, bpc);
-        return launch_gemv_m<1, 3, 0, 8>(p, rpw, epi, st, bpc);
-    }
-    if (xch == 2 && n <= 2) return launch_gemv_m<1, 2, 0, 2>(p, rpw, epi, st, bpc);
-    if (xch == 2 && n == 7 && !vocab) return launch_gemv_m<1, 2, 0, 7>(p, rpw, epi, st, bpc);
-    if (xch == 5 && (n == 9 || n == 10) && !vocab) return launch_gemv_m<1, 5, 0, 5>(p, rpw, epi, st, bpc);
-    // K <= 20,480 without a norm (Qwen3-14B O at K = 5,120: 2 x 5; down at K = 17,408: 5 x 7)
-    if (xch == 10 && ub == 5 && !vocab) return launch_gemv_m<1, 10, 0, 5>(p, rpw, epi, st, bpc);
-    if (xch == 10 && ub == 7 && !vocab) return launch_gemv_m<1, 10, 0, 7>(p, rpw, epi, st, bpc);
-    if (xch == 1 && n == 7) return launch_gemv_m<1, 1, 0, 7>(p, rpw, epi, st, bpc);
-    if (xch == 1) return launch_gemv_m<1, 1>(p, rpw, epi, st, bpc);
-    if (xch == 2) return launch_gemv_m<1, 2>(p, rpw, epi, st, bpc);
-    if (xch == 5) return launch_gemv_m<1, 5>(p, rpw, epi, st, bpc);
-    if (xch == 10) return launch_gemv_m<1, 10>(p, rpw, epi, st, bpc);
-    return launch_gemv_m<1, 0>(p, rpw, epi, st, bpc);
+    return dispatch_epi(pl.epi, [&](auto E) {
+        constexpr int EPI = decltype(E)::value;
+        return pl.rpw >= 4 ? launch_gemv_t<MT, 4, EPI, XCH, WT, UO>(p, pl, st)
+                           : launch_gemv_t<MT, 2, EPI, XCH, WT, UO>(p, pl, st);
+    });
 }
 
-int gemm(const qie_linear_args* a, hipStream_t st);
-
-static int env_int(const char* name, int dflt) { return dev_env(name, dflt); }
-
-constexpr size_t kGemvLdsCap = 96 * 1024;
-constexpr size_t kSkinnyLdsCap = 120 * 1024;
+// plan -> instantiation: every <MT, XCH, WT, UO> the library compiles (rows per wave and the
+// epilogue are launch_gemv_m's)
+constexpr int gemv_key(int mt, int xch, int wt, int uo) { return ((mt * 16 + xch) * 2 + wt) * 16 + uo; }
+static int launch_gemv(const GemvParams& p, const LinearPlan& pl, hipStream_t st) {
+#define QIE_GEMV_CASE(MT, XCH, WT, UO) \
+    case gemv_key(MT, XCH, WT, UO): return launch_gemv_m<MT, XCH, WT, UO>(p, pl, st)
+    switch (gemv_key(pl.mt, pl.xch, pl.wt, pl.uo)) {
+        // fp8 weights, and 2..8 bf16 rows: the generic prologue
+        QIE_GEMV_CASE(1, 0, 1, 0);
+        QIE_GEMV_CASE(2, 0, 1, 0);
+        QIE_GEMV_CASE(4, 0, 1, 0);
+        QIE_GEMV_CASE(8, 0, 1, 0);
+        QIE_GEMV_CASE(2, 0, 0, 0);
+        QIE_GEMV_CASE(4, 0, 0, 0);
+        QIE_GEMV_CASE(8, 0, 0, 0);
+        // one bf16 row: the x-first variants (XCH 2048-element x chunks per thread), x beside
+        // the weights (1), x in registers (3, 4); UO as gemv_uo sizes it
+        QIE_GEMV_CASE(1, 0, 0, 0);
+        QIE_GEMV_CASE(1, 1, 0, 0);
+        QIE_GEMV_CASE(1, 1, 0, 7);
+        QIE_GEMV_CASE(1, 2, 0, 0);
+        QIE_GEMV_CASE(1, 2, 0, 2);
+        QIE_GEMV_CASE(1, 2, 0, 7);
+        QIE_GEMV_CASE(1, 3, 0, 2);
+        QIE_GEMV_CASE(1, 3, 0, 7);
+        QIE_GEMV_CASE(1, 3, 0, 8);
+        QIE_GEMV_CASE(1, 4, 0, 2);
+        QIE_GEMV_CASE(1, 4, 0, 7);
+        QIE_GEMV_CASE(1, 4, 0, 8);
+        QIE_GEMV_CASE(1, 5, 0, 0);
+        QIE_GEMV_CASE(1, 5, 0, 5);
+        QIE_GEMV_CASE(1, 10, 0, 0);
+        QIE_GEMV_CASE(1, 10, 0, 5);
+        QIE_GEMV_CASE(1, 10, 0, 7);
+    }
+#undef QIE_GEMV_CASE
+    return fail(-22, "qie_linear: internal: no GEMV instantiation for MT=%d XCH=%d WT=%d UO=%d", pl.mt, pl.xch, pl.wt,
+                pl.uo);
+}
 
 template <int EPI, int WT, int XL, int NW, int UO = 0>
-static int launch_skinny_x(const GemvParams& p, hipStream_t st) {
-    constexpr int NB = EPI == QIE_EPI_SWIGLU ? 2 : 1;
+static int launch_skinny_x(const GemvParams& p, const LinearPlan& pl, hipStream_t st) {
     const void* fn = (const void*)skinny_mfma_kernel<EPI, WT, XL, NW, UO>;
-    // reduction tiles: NW - 1 partial C tiles per B tile (>= 64 floats for the norm prologue)
-    const size_t shm = (p.xlds ? (size_t)p.M * (p.K + 8) * 2 : 0) + (size_t)std::max(NW - 1, 1) * NB * 256 * 4;
-    if (shm > 65536) {
-        static bool raised = false;
-        if (!raised) {
-            QIE_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            raised = true;
-        }
-    }
-    const int64_t n_tiles = (p.N + 15) / 16;
-    // as many blocks as are resident at once (LDS-limited when the M rows are staged)
-    static size_t cached_shm = 0;
-    static int cached_nb = 0;
-    if (cached_shm != shm || cached_nb == 0) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, NW * 64, shm) != hipSuccess || nb < 1) nb = 1;
-        cached_shm = shm;
-        cached_nb = nb;
-    }
-    // dev A/B: blocks per CU (0: all resident — config 4's tiled lm_head 100.1 µs; caps 1 / 2 / 3 / 6
-    // measured 101.9 / 100.5 / 111.0 / 127.7)
-    const int cap = dev_env("QIE_SKINNY_BPC", 0);
-    const unsigned grid = (unsigned)std::max<int64_t>(
-        1, std::min<int64_t>(n_tiles, (int64_t)device_cu_count() * (cap > 0 ? cap : cached_nb)));
-    hipLaunchKernelGGL((skinny_mfma_kernel<EPI, WT, XL, NW, UO>), dim3(grid), dim3(NW * 64), shm, st, p);
+    QIE_TRY(raise_dynamic_lds(fn, gemv_lds_limit(pl.lds_bytes)));
+    const int nb = pl.needs_occupancy() ? resident_blocks_per_cu(fn, NW * 64, pl.lds_bytes, 1) : 0;
+    const LaunchGeom g = launch_geometry(pl, device_cu_count(), nb);
+    hipLaunchKernelGGL((skinny_mfma_kernel<EPI, WT, XL, NW, UO>), dim3(g.grid), dim3(NW * 64), g.lds_bytes, st, p);
     QIE_LAUNCH_CHECK();
     return 0;
 }
 // 4 waves per block: 8 (2,304 waves for Qwen2-7B QKV) measured 1-9 % slower at config 4,
 // 16 spills (128 VGPRs at 1,024 threads)
-template <int EPI, int WT>
-static int launch_skinny_t(const GemvParams& p, hipStream_t st) {
-    if constexpr (WT == 1) {
-        // fp8: 7 units per step where a wave's K range is 7 or 14 units (Qwen2-7B, K = 3,584:
-        // 2 steps of 7 instead of 4 of 4 / 2 of 8 with two dead units).  Config 4 (fp8, B = 8):
-        // gate/up 36.2 -> 35.2, O 8.4 -> 7.45, lm_head 129 -> 122 us, 2,509 -> 2,535 tok/s
-        const int64_t uw = (p.K / 64 + 3) / 4;
-        if (uw == 7 || uw == 14)
-            return p.xlds ? launch_skinny_x<EPI, WT, 1, 4, 7>(p, st) : launch_skinny_x<EPI, WT, 0, 4, 7>(p, st);
-    }
-    return p.xlds ? launch_skinny_x<EPI, WT, 1, 4>(p, st) : launch_skinny_x<EPI, WT, 0, 4>(p, st);
+static int launch_skinny(const GemvParams& p, const LinearPlan& pl, hipStream_t st) {
+    return dispatch_epi(pl.epi, [&](auto E) {
+        constexpr int EPI = decltype(E)::value;
+        if (pl.wt && pl.uo == 7)
+            return pl.xlds ? launch_skinny_x<EPI, 1, 1, 4, 7>(p, pl, st) : launch_skinny_x<EPI, 1, 0, 4, 7>(p, pl, st);
+        if (pl.wt) return pl.xlds ? launch_skinny_x<EPI, 1, 1, 4>(p, pl, st) : launch_skinny_x<EPI, 1, 0, 4>(p, pl, st);
+        return pl.xlds ? launch_skinny_x<EPI, 0, 1, 4>(p, pl, st) : launch_skinny_x<EPI, 0, 0, 4>(p, pl, st);
+    });
 }
 
-static int launch_skinny(const GemvParams& p, int epi, bool fp8w, hipStream_t st) {
-    if (fp8w) {
-        if (epi == QIE_EPI_SWIGLU) return launch_skinny_t<QIE_EPI_SWIGLU, 1>(p, st);
-        if (epi == QIE_EPI_RESIDUAL) return launch_skinny_t<QIE_EPI_RESIDUAL, 1>(p, st);
-        if (epi == QIE_EPI_F32) return launch_skinny_t<QIE_EPI_F32, 1>(p, st);
-        return launch_skinny_t<QIE_EPI_STORE, 1>(p, st);
-    }
-    if (epi == QIE_EPI_SWIGLU) return launch_skinny_t<QIE_EPI_SWIGLU, 0>(p, st);
-    if (epi == QIE_EPI_RESIDUAL) return launch_skinny_t<QIE_EPI_RESIDUAL, 0>(p, st);
-    if (epi == QIE_EPI_F32) return launch_skinny_t<QIE_EPI_F32, 0>(p, st);
-    return launch_skinny_t<QIE_EPI_STORE, 0>(p, st);
-}
-static bool K_fits(int64_t K, int xch) { return K <= 2048 * (int64_t)xch && K % 8 == 0; }
+int gemm(const qie_linear_args* a, hipStream_t st);
+int dec8_linear(const qie_linear_args* a, const LinearPlan& pl, hipStream_t st, bool* done);
 
-// RoPE for the next gemv() call only (gemv_rope); thread-local: engines on other host
-// threads (tensor-parallel ranks) enqueue concurrently
-struct RopeArgs {
-    const int32_t* pos = nullptr;
-    const float* cs = nullptr;
-    const float* sn = nullptr;
-    int hd = 0;
-    int64_t rows = 0;
-};
-static thread_local RopeArgs g_rope;
-static thread_local const PeerPush* g_push = nullptr;
-static thread_local bool g_push_taken = false;
-void set_gemv_push(const PeerPush* pp) {
-    g_push = pp;
-    g_push_taken = false;
-}
-bool gemv_push_taken() { return g_push_taken; }
-
-int gemv(const qie_linear_args* a, hipStream_t st);
-
-// Decode QKV projection (M = 1, REF numerics, no qk-norm) with the interleaved RoPE of its q
-// and k rows fused into the STORE epilogue (RoPE.cu:6-22 on the projection's bf16 output):
-// the decode attention then takes q / k as they are (qie_attention_decode, QIE_ATTN_PREROPED).
-int gemv_rope(const qie_linear_args* a, const int32_t* pos, const float* cs, const float* sn, int hd,
-              int64_t rows, hipStream_t st) {
-    QIE_REQUIRE(a->M == 1 && a->epilogue == QIE_EPI_STORE && rows % 2 == 0 && hd % 2 == 0 && pos && cs && sn,
-                "gemv_rope: M = 1 STORE projections only");
-    g_rope = RopeArgs{pos, cs, sn, hd, rows};
-    const int rc = gemv(a, st);
-    g_rope = RopeArgs{};
-    return rc;
+// true when the fp8 batched-decode kernel takes this projection (the engine then skips its
+// separate norm)
+bool dec8_applies(const qie_linear_args* a) {
+    int ku, ks, parts;
+    return dec8_plan(*a, dev_knobs(), &ku, &ks, &parts);
 }
 
-bool dec8_applies(const qie_linear_args* a);
-int dec8_linear(const qie_linear_args* a, hipStream_t st, bool* done);
-
-int gemv(const qie_linear_args* a, hipStream_t st) {
-    // fp8 weights, 2..16 rows, K a whole number of per-wave slices (or split-K): k_decode_fp8.hip
-    if (dec8_applies(a)) {
+// M <= 16: plan, fill the kernel's argument block, launch the plan's instantiation
+static int gemv(const qie_linear_args* a, const LinearExtras& ex, hipStream_t st) {
+    if (ex.push_taken) *ex.push_taken = false;
+    const Knobs k = dev_knobs();
+    const int cus = device_cu_count();
+    LinearPlan pl = plan_linear(*a, ex, cus, k);
+    if (pl.family == LinearFamily::Dec8) {
         bool done = false;
-        const int rc = dec8_linear(a, st, &done);
+        const int rc = dec8_linear(a, pl, st, &done);
         if (done) return rc;
+        pl = plan_linear(*a, ex, cus, k, false);
     }
+    switch (pl.error) {
+        case PlanError::None: break;
+        case PlanError::TiledShape:
+            return fail(-22, "qie_linear: tiled fp8 weights: the skinny kernel cannot take M=%lld K=%lld", (long long)a->M,
+                        (long long)a->K);
+        case PlanError::NormLds:
+            return fail(-22, "qie_linear: fused RMSNorm needs M*K*2 <= %zu bytes (M=%lld K=%lld)", kGemvLdsCap,
+                        (long long)a->M, (long long)a->K);
+        case PlanError::Fp8K16:
+            return fail(-22, "qie_linear: fp8 weights need K %% 16 == 0 (K=%lld)", (long long)a->K);
+        case PlanError::NormRouted:
+            return fail(-22, "qie_linear: internal: fused norm routed to a variant without one");
+    }
+    if (pl.family == LinearFamily::Gemm) return gemm(a, st);
     GemvParams p;
     p.x = (const uint16_t*)a->x;
     p.ldx = a->ldx;
@@ -1417,181 +1337,67 @@ int gemv(const qie_linear_args* a, hipStream_t st) {
     p.eps = a->norm_eps;
     p.numerics = a->numerics;
     p.M = (int)a->M;
+    p.xlds = pl.xlds;
     p.keys = (unsigned long long*)a->argmax_keys;
     p.key_col0 = a->key_col0;
-    p.dbg = 0;
-    p.rope_pos = g_rope.pos;
-    p.rope_cs = g_rope.cs;
-    p.rope_sn = g_rope.sn;
-    p.rope_hd = g_rope.hd;
-    p.rope_rows = g_rope.rows;
-    p.epre = env_int("QIE_GEMV_EPRE", 1);
-    p.mkdiv = env_int("QIE_GEMV_MKDIV", 0);
-    // 16-row tiled fp8 weights the batched-decode kernel did not take (the vocabulary
-    // projection): the skinny kernel reads them, at any 1 <= M <= 16 (qie_linear checked the shape)
-    p.t16 = (a->flags & QIE_LINEAR_FP8_T16) ? 1 : 0;
+    p.n_tasks = pl.n_tasks;
+    p.dbg = pl.dbg;
+    p.rope_pos = ex.rope.pos;
+    p.rope_cs = ex.rope.cs;
+    p.rope_sn = ex.rope.sn;
+    p.rope_hd = ex.rope.hd;
+    p.rope_rows = ex.rope.rows;
+    p.epre = k.epre;
+    p.mkdiv = k.mkdiv;
+    p.t16 = pl.t16 ? 1 : 0;
     p.push = PeerPush{};
-    g_push_taken = false;
-    if ((a->M >= 2 || p.t16) && a->M <= 16 && (p.t16 || env_int("QIE_SKINNY_MFMA", 1) != 0)) {
-        const bool fp8w = (a->flags & QIE_LINEAR_FP8) != 0;
-        const int kstep = 64;
-        const bool lds_ok = (size_t)a->M * (a->K + 8) * 2 <= kSkinnyLdsCap;
-        QIE_REQUIRE(!p.t16 || (fp8w && a->K % kstep == 0 && (lds_ok || !a->norm_w)),
-                    "qie_linear: tiled fp8 weights: the skinny kernel cannot take M=%lld K=%lld", (long long)a->M,
-                    (long long)a->K);
-        if (a->K % kstep == 0 && (lds_ok || !a->norm_w)) {
-            p.M = (int)a->M;
-            // Stage the M rows in LDS only when the norm is fused (it needs them) or a block
-            // serves several column tiles (gate/up, lm_head: the copy is amortised); with
-            // about one tile per CU (QKV, O, down) each wave loads its A fragments from L2
-            // with its weight steps instead of a 57-KB copy + barrier per block (config 4,
-            // fp8: O 9.7 -> 7.8 us, down 26.4 -> 24.6; bf16 O 11.6 -> 10.1, QKV 16.5 -> 15.3)
-            const int64_t n_tiles = (a->N + 15) / 16;
-            p.xlds = lds_ok && (a->norm_w || n_tiles > 2 * (int64_t)device_cu_count()) ? 1 : 0;
-            // Without a fused norm the staged copy is only an optimisation: keep the launch's
-            // dynamic LDS within the default 64 KiB (no raised kernel attribute).  r02's config-4
-            // gate/up node (8 rows x 3,592 + two 4-KiB reduction tiles per wave = 65,664 B) was
-            // the one decode-graph node above it, and rocprofv3's kernel trace crashed on that
-            // graph only; with NW - 1 reduction tiles it is 63,616 B and stays staged.
-            const size_t staged = (size_t)a->M * (a->K + 8) * 2 + (a->epilogue == QIE_EPI_SWIGLU ? 2 : 1) * 3072;
-            if (p.xlds && !a->norm_w && staged > 65536 && env_int("QIE_SKINNY_LDS64", 1) != 0) p.xlds = 0;
-            const int fx = env_int("QIE_SKINNY_XL", -1);
-            if (fx >= 0) p.xlds = fx && lds_ok ? 1 : 0;
-            p.dbg = env_int("QIE_SKINNY_DBG", 0);
-            return launch_skinny(p, a->epilogue, fp8w, st);
-        }
+    if (pl.push) {
+        p.push = *ex.push;
+        if (ex.push_taken) *ex.push_taken = true;
     }
-    if (a->M > 8) return gemm(a, st);   // 9..16 rows the skinny kernel could not take
-    if (g_push && a->M == 1 && a->epilogue == QIE_EPI_F32) {   // every M = 1 launch below is gemv_kernel
-        p.push = *g_push;
-        g_push_taken = true;
-    }
-    p.dbg = a->M == 1 ? env_int("QIE_GEMV_DBG", 0) : 0;   // dev timing experiments (1 no norm, 2 no bias)
-    const int MT = a->M <= 1 ? 1 : a->M <= 2 ? 2 : a->M <= 4 ? 4 : 8;
-    p.xlds = ((size_t)MT * a->K * 2 <= kGemvLdsCap) ? 1 : 0;
-    QIE_REQUIRE(p.xlds || !p.norm_w,
-                "qie_linear: fused RMSNorm needs M*K*2 <= %zu bytes (M=%lld K=%lld)", kGemvLdsCap,
-                (long long)a->M, (long long)a->K);
-    // Rows per wave: 4 while the grid still has >= 2 waves per SIMD of work.
-    const int cus = device_cu_count();
-    const int64_t rows = a->epilogue == QIE_EPI_SWIGLU ? 2 * a->N : a->N;
-    // Rows per wave: 2 (measured faster than 4 for every Qwen2-7B decode GEMV on
-    // MI355X: down 23.7 vs 28.0 us, qkv 9.7 vs 10.9, o 6.6 vs 7.7, gate/up 42.9 vs 43.8).
-    int rpw = env_int("QIE_GEMV_RPW", 2);
-    // (dev A/B) vocabulary rows: 4 rows per wave measured 165.9 vs 164.8 µs at Qwen2-7B,
-    // 53.4 vs 48.7 at Qwen2-0.5B
-    if (MT == 1 && rows >= 65536) rpw = env_int("QIE_GEMV_RPW_LM", rpw);
-    if (rpw != 2 && rpw != 4) rpw = 2;
-    p.n_tasks = (rows + rpw - 1) / rpw;
-    // Grid (QIE_GEMV_BLOCKS_PER_CU): default (auto) = one block per CU with ceil(tasks / CUs)
-    // waves where 4..9 tasks per CU (Qwen2-7B QKV, O, down), else the occupancy-balanced
-    // persistent grid (lm_head 169 vs 183 us, gate/up 43.1 vs 43.5 against a cap of 8 blocks
-    // per CU); 0 = always the occupancy grid; N > 0 = cap of N blocks per CU.
-    int bpc = env_int("QIE_GEMV_BLOCKS_PER_CU", -1);
-    // x-first prologue + cross-task weight prefetch (QIE_GEMV_XFIRST, MT = 1).  A first
-    // attempt that issued the weights BEFORE x was slower everywhere (qkv 11.4 vs 9.4 us):
-    // x then queued behind the weights in the in-order vmcnt.
-    if (a->flags & QIE_LINEAR_FP8) {
-        QIE_REQUIRE(a->K % 16 == 0, "qie_linear: fp8 weights need K %% 16 == 0 (K=%lld)", (long long)a->K);
-        switch (MT) {
-            case 1: return launch_gemv_m<1, 0, 1>(p, rpw, a->epilogue, st, bpc);
-            case 2: return launch_gemv_m<2, 0, 1>(p, rpw, a->epilogue, st, bpc);
-            case 4: return launch_gemv_m<4, 0, 1>(p, rpw, a->epilogue, st, bpc);
-            default: return launch_gemv_m<8, 0, 1>(p, rpw, a->epilogue, st, bpc);
-        }
-    }
-    int xch = 0;
-    // The x-first variants with a fused RMSNorm are XCH 2 and 5 (the norm weights ride along
-    // with x); XCH 10 (down, K = 18,944) stages x only — a fused norm there would be dropped,
-    // so a normed K > 10,240 takes the generic prologue.
-    if (MT == 1 && p.xlds && p.M == 1 && env_int("QIE_GEMV_XFIRST", 1) != 0) {
-        if (p.norm_w) xch = K_fits(a->K, 2) ? 2 : (K_fits(a->K, 5) ? 5 : 0);
-        else xch = K_fits(a->K, 2) ? 2 : (K_fits(a->K, 10) ? 10 : 0);
-    }
-    // Fused norm with a per-wave sum of squares (XCH 3) where one batch of <= 8 wave-loads
-    // covers a row (K <= 4,096, K % 8 == 0: Qwen2-7B QKV / gate/up / lm_head at K = 3,584,
-    // Qwen2-0.5B at 896): no block reduction, one barrier before the weight stream.
-    // Measured (tools/ubench.py, Qwen2-7B): lm_head 175.3 -> 167.4 us; QKV (9.14 vs 9.67) and
-    // gate/up (42.7 vs 43.8) are faster with the x-first prologue's one-chunk-per-thread x
-    // loads, so only the vocabulary projection takes it.
-    const bool vocab_rows = rows >= 65536;
-    if (MT == 1 && p.M == 1 && p.norm_w && a->K % 8 == 0 && a->K <= 4096 &&
-        env_int("QIE_GEMV_XREG", vocab_rows ? 1 : 0) != 0) {
-        xch = 3;
-    }
-    // Normalised x in every wave's registers (XCH 4): no LDS image, no barrier.  Default for
-    // gate/up (5 row tasks per wave reuse it): 361.5 -> 362.7 tok/s at Qwen2-7B; the QKV
-    // projection (one task per wave) pays the per-wave divisions on its critical path:
-    // 9.98 -> 14.6 us (dev knobs QIE_GEMV_XREG4 / _LM / _SW)
-    if (MT == 1 && p.M == 1 && p.norm_w && a->K % 8 == 0 && a->K <= 4096 &&
-        env_int(a->epilogue == QIE_EPI_SWIGLU ? "QIE_GEMV_XREG4_SW" : (vocab_rows ? "QIE_GEMV_XREG4_LM" : "QIE_GEMV_XREG4"),
-                a->epilogue == QIE_EPI_SWIGLU ? 1 : 0) != 0) {
-        xch = 4;
-        p.xlds = 0;
-    }
-    // gate/up grid: full residency, grid-stride (-2, launch_gemv_t); QIE_GEMV_SWIGLU_BPC = N > 0
-    // caps N blocks per CU, -1 the balanced grid (dev A/B)
-    //
-    // Round 5, grid caps measured per shape (same box, interleaved, in the graph: tools/ab_decode.py;
-    // outputs bit-identical — the grid only changes which wave takes which row task):
-    //  * gate/up, Qwen2-7B (K 3,584, 74 row tasks per CU; 198 VGPRs, 2 resident blocks per CU):
-    //    6 blocks per CU 42.7 -> 41.3 µs, 361.8 -> 366.7 tok/s — a sharp optimum (5: 357.4,
-    //    8: 358.1, 10: 343.2; the full-residency grid, 2 per CU, 361.8);
-    //  * gate/up, Qwen2-0.5B (K 896, 19 tasks per CU; 62 VGPRs): 3 per CU 6.48 -> 5.22 µs,
-    //    1,484 -> 1,542 tok/s (2: 1,543, 4: 1,511, 5: 1,483);
-    //  * lm_head (vocabulary rows, occupancy-balanced grid otherwise): K 896 5 per CU
-    //    53.4 -> 48.8 µs; K 3,584 2 per CU 167.3 -> 164.7 µs.
-    // Shapes outside those ranges keep the former grids (unmeasured there).
-    if (a->epilogue == QIE_EPI_SWIGLU && MT == 1 && bpc < 0) {
-        const int64_t tpc = p.n_tasks / cus;
-        int dflt = -2;
-        if (a->K <= 1024 && tpc <= 32) dflt = 3;
-        else if (a->K >= 3072 && a->K <= 4096 && tpc >= 64 && tpc <= 96) dflt = 6;
-        bpc = env_int("QIE_GEMV_SWIGLU_BPC", dflt);
-    }
-    if (vocab_rows && MT == 1 && bpc < 0)
-        bpc = env_int("QIE_GEMV_LM_BPC", a->K <= 1024 ? 5 : (a->K <= 4096 ? 2 : -1));
-    // The normed STORE projection (QKV), Qwen2-7B (K 3,584, 9 row tasks per CU): 2 blocks of 4
-    // waves per CU instead of one 9-wave block, 9.77 -> 9.26 µs, 367.4 -> 369.4 tok/s (1: 357.2,
-    // 3: 364.8, 4: 364.8).  The fused norm's sum of squares is then reduced over 256 threads
-    // instead of 576 (another fp32 order of the same sum; the parity tests bound it).
-    // Qwen2-0.5B's QKV: equal at 1-3 per CU, kept.
-    // (dev A/B) residual projections (O, down): caps 3 / 5 / 6 / 8 per CU all ran Qwen2-7B at
-    // 363.4-363.5 vs 369.6 tok/s on their one-block-per-CU layout; 0.5B equal
+    return pl.family == LinearFamily::Skinny ? launch_skinny(p, pl, st) : launch_gemv(p, pl, st);
+}
 
-    if (MT == 1 && a->epilogue == QIE_EPI_RESIDUAL && bpc < 0) bpc = env_int("QIE_GEMV_RES_BPC", -1);
-    if (!vocab_rows && MT == 1 && p.norm_w && a->epilogue == QIE_EPI_STORE && bpc < 0) {
-        const int64_t tpc = p.n_tasks / cus;
-        bpc = env_int("QIE_GEMV_QKV_BPC", a->K >= 3072 && a->K <= 4096 && tpc >= 6 && tpc <= 12 ? 2 : -1);
+// qie_linear behind its C entry: validates, then routes.  Callers inside the library pass what
+// the public argument block cannot hold in `ex`: the decode QKV projection's fused RoPE (M = 1,
+// REF numerics, no qk-norm: the interleaved RoPE of its q and k rows in the STORE epilogue,
+// RoPE.cu:6-22 on the projection's bf16 output — the decode attention then takes q / k as they
+// are, QIE_ATTN_PREROPED) and the row-parallel projections' peer push.
+int linear(const qie_linear_args* a, const LinearExtras& ex, hipStream_t st) {
+    QIE_REQUIRE(a && a->x && a->y && a->w[0] && a->M > 0 && a->K > 0 && a->N > 0, "qie_linear: bad arguments");
+    QIE_REQUIRE(a->K % 8 == 0 && a->ldx >= a->K && a->ldx % 8 == 0, "qie_linear: K and ldx must be multiples of 8");
+    QIE_REQUIRE(((uintptr_t)a->x % 16) == 0, "qie_linear: x must be 16-byte aligned");
+    for (int i = 0; i < 3; i++)
+        QIE_REQUIRE(((uintptr_t)a->w[i] % 16) == 0, "qie_linear: weight segment %d must be 16-byte aligned", i);
+    if (a->epilogue == QIE_EPI_SWIGLU) {
+        QIE_REQUIRE(a->w[1] && a->seg_rows[0] == a->N && a->seg_rows[1] == a->N && a->ldy >= a->N,
+                    "qie_linear: SWIGLU needs w[0]=gate, w[1]=up with N rows each");
+    } else {
+        QIE_REQUIRE(a->seg_rows[0] + a->seg_rows[1] + a->seg_rows[2] == a->N && a->ldy >= a->N,
+                    "qie_linear: seg_rows must sum to N");
+        QIE_REQUIRE(a->seg_rows[1] == 0 || a->w[1], "qie_linear: missing weight segment 1");
+        QIE_REQUIRE(a->seg_rows[2] == 0 || a->w[2], "qie_linear: missing weight segment 2");
     }
-    // Batch-1 GEMVs without a fused norm on the one-block-per-CU grid (one row task per
-    // wave: Qwen2-7B O, down) read x from L2 beside each weight chunk (XCH = 1) instead of
-    // staging it in LDS behind a barrier: Qwen2-7B decode 355 -> 358 tok/s (two A/B rounds),
-    // in-graph down 24.5 -> 23.5 us, O 7.3 -> 7.05.  Where a wave walks several row tasks
-    // (Qwen3-14B O / down, 10 per CU; Qwen2-0.5B) x would be re-read per task: O 13.1 ->
-    // 16.5, down 32.9 -> 39.7 us at 14B, so those keep the staged copy.
-    // (the condition is launch_gemv_t's one-block-per-CU grid)
-    if (MT == 1 && p.M == 1 && !p.norm_w && !(a->flags & QIE_LINEAR_FP8) && a->epilogue != QIE_EPI_SWIGLU &&
-        a->K % 8 == 0 && bpc < 0 && p.n_tasks > 4 * (int64_t)cus &&
-        p.n_tasks <= (kGemvBalancedThreads / 64) * (int64_t)cus && env_int_gemv("QIE_GEMV_BALANCED", 1) != 0) {
-        xch = 1;
-        p.xlds = 0;
-        // one row per wave, up to 16 waves per CU, where x is short (each wave re-reads all of x
-        // from L2): Qwen2-7B O 6.68 -> 6.45 us; down (x 37.9 KB, K = 18,944) doubled its L2
-        // traffic for x that way (23.3 -> 25.1 us), so it keeps two rows per wave
-        if ((a->epilogue == QIE_EPI_RESIDUAL || a->epilogue == QIE_EPI_STORE) && rows <= 16 * (int64_t)cus &&
-            a->K <= 4096 && env_int("QIE_GEMV_RPW1", 1) != 0) {
-            rpw = 1;
-            p.n_tasks = rows;
-        }
-    }
-    QIE_REQUIRE(!(xch == 10 && p.norm_w), "qie_linear: internal: fused norm routed to a variant without one");
-    switch (MT) {
-        case 1: return launch_gemv_1(p, rpw, a->epilogue, st, bpc, xch);
-        case 2: return launch_gemv_m<2, 0>(p, rpw, a->epilogue, st, bpc);
-        case 4: return launch_gemv_m<4, 0>(p, rpw, a->epilogue, st, bpc);
-        default: return launch_gemv_m<8, 0>(p, rpw, a->epilogue, st, bpc);
-    }
+    QIE_REQUIRE(a->epilogue >= 0 && a->epilogue <= 3, "qie_linear: bad epilogue");
+    QIE_REQUIRE(a->epilogue != QIE_EPI_F32 || (a->bias[0] == nullptr && a->bias[1] == nullptr && a->bias[2] == nullptr),
+                "qie_linear: F32 (partial-sum) epilogue takes no bias");
+    QIE_REQUIRE(a->argmax_keys == nullptr || a->epilogue == QIE_EPI_STORE, "qie_linear: arg-max needs STORE");
+    QIE_REQUIRE(!(ex.rope.pos || ex.rope.rows) ||
+                    (a->M == 1 && a->epilogue == QIE_EPI_STORE && ex.rope.rows % 2 == 0 && ex.rope.hd % 2 == 0 &&
+                     ex.rope.pos && ex.rope.cs && ex.rope.sn),
+                "qie_linear: fused RoPE: M = 1 STORE projections only");
+    if (ex.push_taken) *ex.push_taken = false;
+    if (a->flags & QIE_LINEAR_ACT_FP8) return gemm(a, st);   // fp8 activations: the block-scaled MFMA GEMM at every M
+    QIE_REQUIRE(!(a->flags & QIE_LINEAR_FP8_T16) ||
+                    ((a->flags & QIE_LINEAR_FP8) && a->M >= 1 && a->M <= 16 && a->K % 64 == 0 &&
+                     (a->epilogue == QIE_EPI_SWIGLU ? a->N % 16 == 0
+                                                    : a->seg_rows[0] % 16 == 0 && a->seg_rows[1] % 16 == 0 &&
+                                                          a->seg_rows[2] % 16 == 0)),
+                "qie_linear: 16-row tiled fp8 weights are read by the batched-decode kernels only (M <= 16, K %% 64 == 0, "
+                "segments of whole 16-row tiles) and, with fp8 activations, the block-scaled GEMM");
+    if (a->M <= 16) return gemv(a, ex, st);   // GEMV (M = 1..8) or the skinny MFMA kernel (2..16)
+    return gemm(a, st);
 }
 
 }  // namespace qie
+

@@ -10,12 +10,15 @@
 //   residual_add           layers/src/residual_add.cu:7-18
 //   kv_copy_layer_to_cache_{prefill,decode} layers/src/include_cuda.cu:165-279
 #include "qie_common.hpp"
+#include "launch_util.hpp"
 #include "../../include/qie/qie_ops.h"
 
 #include <cmath>
 #include <cstdarg>
 #include <cstring>
+#include <map>
 #include <mutex>
+#include <tuple>
 #include <vector>
 
 #ifdef _OPENMP
@@ -52,6 +55,37 @@ int device_cu_count() {
     return cus[dev];
 }
 
+// ------------------------------------------------------------ launch_util.hpp
+// hipFuncSetAttribute and the occupancy query apply to the current device, and engines on
+// other host threads (tensor-parallel ranks) launch concurrently: one mutex, keys with the device.
+namespace {
+std::mutex g_launch_mu;
+std::map<std::pair<int, const void*>, size_t> g_lds_limit;
+std::map<std::tuple<int, const void*, int, size_t>, int> g_resident;
+}  // namespace
+
+int raise_dynamic_lds(const void* fn, size_t bytes) {
+    if (bytes <= 65536) return 0;
+    int dev = 0;
+    QIE_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_launch_mu);
+    size_t& limit = g_lds_limit[{dev, fn}];
+    if (limit >= bytes) return 0;
+    QIE_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    limit = bytes;
+    return 0;
+}
+
+int resident_blocks_per_cu(const void* fn, int threads, size_t shm, int fallback) {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return fallback;
+    std::lock_guard<std::mutex> lk(g_launch_mu);
+    int& nb = g_resident[{dev, fn, threads, shm}];
+    if (nb == 0 && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, threads, shm) != hipSuccess || nb < 1))
+        nb = fallback;
+    return nb;
+}
+
 // ------------------------------------------------------------ embedding
 // One block per token row, 16-byte copies (the reference copies one bf16 at a
 // time from pinned host memory with one thread per row).
@@ -79,28 +113,6 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
     return t;
 }
 
-__device__ __forceinline__ uint4 rms_apply8(uint4 xv, uint4 wv, float rms, float inv, int numerics) {
-#pragma clang fp contract(off)
-    uint32_t xs[4] = {xv.x, xv.y, xv.z, xv.w};
-    uint32_t ws[4] = {wv.x, wv.y, wv.z, wv.w};
-    uint32_t o[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        float a0 = bf_lo(xs[j]), a1 = bf_hi(xs[j]);
-        float w0 = bf_lo(ws[j]), w1 = bf_hi(ws[j]);
-        float y0, y1;
-        if (numerics == QIE_NUMERICS_HF) {
-            y0 = w0 * rbf(a0 * inv);
-            y1 = w1 * rbf(a1 * inv);
-        } else {
-            y0 = (a0 / rms) * w0;
-            y1 = (a1 / rms) * w1;
-        }
-        o[j] = pack2(y0, y1);
-    }
-    return make_uint4(o[0], o[1], o[2], o[3]);
-}
-
 __global__ __launch_bounds__(256) void rmsnorm_kernel(const uint4* __restrict__ x,
                                                       const uint4* __restrict__ w,
                                                       uint4* __restrict__ y, int64_t H, float eps,
@@ -122,7 +134,7 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const uint4* __restrict__ 
     ss = block_sum_256(ss, red);
     const float rms = sqrtf((ss / (float)H) + eps);
     const float inv = 1.0f / rms;
-    for (int64_t i = threadIdx.x; i < H8; i += 256) yr[i] = rms_apply8(xr[i], w[i], rms, inv, numerics);
+    for (int64_t i = threadIdx.x; i < H8; i += 256) yr[i] = rms_apply8(xr[i], w[i], rms, inv, numerics == QIE_NUMERICS_HF);
 }
 
 // H <= 2048 V: the row and the norm weights stay in registers, both loaded up front (one
@@ -159,7 +171,7 @@ __global__ __launch_bounds__(256) void rmsnorm_reg_kernel(const uint4* __restric
 #pragma unroll
     for (int c = 0; c < V; c++) {
         const int64_t i = threadIdx.x + 256 * c;
-        if (i < H8) yr[i] = rms_apply8(xv[c], wv[c], rms, inv, numerics);
+        if (i < H8) yr[i] = rms_apply8(xv[c], wv[c], rms, inv, numerics == QIE_NUMERICS_HF);
     }
 }
 

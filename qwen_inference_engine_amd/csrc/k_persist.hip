@@ -35,6 +35,7 @@
 //     (error word), the block gives up, the grid drains, and the engine's next synchronising
 //     call fails with the error word (engine.hip pk_check) — never a hang.
 #include "attn_decode.hpp"
+#include "launch_util.hpp"
 
 #include <cstddef>
 #include <vector>
@@ -755,12 +756,7 @@ int persist_decode_launch(const qie_model_spec& s, const qie_layer_weights* d_la
     p.xw_even = dev_env("QIE_PK_XW", 100);
     const size_t shm = persist_lds_bytes(p.H, p.I, p.QD, p.KD, p.nq / p.nkv, p.hd);
     const void* fn = s.head_dim == 128 ? (const void*)pk::decode_layers_kernel<128> : (const void*)pk::decode_layers_kernel<64>;
-    static bool raised[2] = {false, false};
-    bool& r = raised[s.head_dim == 128 ? 1 : 0];
-    if (!r) {
-        QIE_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm + 4096));
-        r = true;
-    }
+    QIE_TRY(raise_dynamic_lds(fn, shm + 4096));
     if (s.head_dim == 128)
         hipLaunchKernelGGL(pk::decode_layers_kernel<128>, dim3((unsigned)device_cu_count()), dim3(64 * pk::waves_for<128>()),
                            shm, st, p);

@@ -13,6 +13,7 @@
 //   * softmax + draw on one lane with the reference's sequential order and a
 //     cuRAND-XORWOW restatement (curand_init(seed, 0, 0); curand_uniform).
 #include "qie_common.hpp"
+#include "launch_util.hpp"
 #include "../../include/qie/qie_ops.h"
 
 namespace qie {
@@ -203,14 +204,7 @@ int qie_sample(const void* logits, int64_t M, int64_t V, int64_t ld, const qie_s
     const int n2 = pow2_at_least(nb * k);
     const size_t shm = (size_t)n2 * 8;
     QIE_REQUIRE(shm <= 160 * 1024, "qie_sample: top-k merge exceeds LDS (V=%lld k=%d)", (long long)V, k);
-    if (shm > 65536) {
-        static bool raised = false;
-        if (!raised) {
-            QIE_HIP(hipFuncSetAttribute((const void*)topk_merge_sample_kernel,
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            raised = true;
-        }
-    }
+    if (shm > 65536) QIE_TRY(raise_dynamic_lds((const void*)topk_merge_sample_kernel, 160 * 1024));
     hipLaunchKernelGGL(topk_merge_sample_kernel, dim3((unsigned)M), dim3(256), shm, st, cand, nb, k, n2,
                        s->temperature, s->top_p, (uint64_t)s->seed, step_dev, out_ids);
     QIE_LAUNCH_CHECK();

@@ -10,6 +10,7 @@
 #include "../../include/qie/qie_types.h"
 
 struct qie_kv_cache;
+struct qie_linear_args;
 
 namespace qie {
 
@@ -81,6 +82,36 @@ typedef __bf16 qie_bf16x2_t __attribute__((ext_vector_type(2)));
 typedef float qie_f32x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
     return __builtin_bit_cast(uint32_t, __builtin_convertvector((qie_f32x2_t{lo, hi}), qie_bf16x2_t));
+}
+
+// ------------------------------------------------------------- RMSNorm step
+// Eight elements of a normed row, packed to bf16 (REF parity is bit-exact on this expression):
+//   REF: y = bf16((x / rms) * w)              normalization.cu:18-23
+//   HF : y = bf16(w * bf16(x * (1 / rms)))    (inv = 1 / rms)
+// qie_rmsnorm's kernels (k_misc.hip) call it.  The fused prologues of gemv_kernel,
+// skinny_mfma_kernel and the persistent step (k_persist.hip normalize) spell the same step out
+// in place: calling this helper there changed their register allocation (compared on the
+// gfx950 disassembly), so they are to be moved only together with a measurement.
+__device__ __forceinline__ uint4 rms_apply8(uint4 xv, uint4 wv, float rms, float inv, bool hf) {
+#pragma clang fp contract(off)
+    uint32_t xs[4] = {xv.x, xv.y, xv.z, xv.w};
+    uint32_t ws[4] = {wv.x, wv.y, wv.z, wv.w};
+    uint32_t o[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        float a0 = bf_lo(xs[j]), a1 = bf_hi(xs[j]);
+        float w0 = bf_lo(ws[j]), w1 = bf_hi(ws[j]);
+        float y0, y1;
+        if (hf) {
+            y0 = w0 * rbf(a0 * inv);
+            y1 = w1 * rbf(a1 * inv);
+        } else {
+            y0 = (a0 / rms) * w0;
+            y1 = (a1 / rms) * w1;
+        }
+        o[j] = pack2(y0, y1);
+    }
+    return make_uint4(o[0], o[1], o[2], o[3]);
 }
 
 // ------------------------------------------------------ fp8 (OCP e4m3fn) weights
@@ -284,10 +315,11 @@ struct PeerPush {
 __device__ __forceinline__ uint64_t* peer_tag_slot(char* tb, unsigned e, int src) {
     return reinterpret_cast<uint64_t*>(tb + (int64_t)((e & 1) * kPeerTagMaxWorld + src) * kPeerTagCap);
 }
-// The M = 1 GEMV launches of this host thread push their F32-epilogue outputs (null: none);
-// gemv_push_taken() reports whether the last launch did.
-void set_gemv_push(const PeerPush* pp);
-bool gemv_push_taken();
+
+// qie_linear for callers inside the library (k_gemv.hip): the same validation and routing, plus
+// what the public argument block cannot hold (linear_plan.hpp LinearExtras)
+struct LinearExtras;
+int linear(const qie_linear_args* a, const LinearExtras& ex, hipStream_t st);
 
 // Device properties cached per process (CU count for persistent grids).
 int device_cu_count();

@@ -59,6 +59,20 @@ def test_persistent_equals_launches(spec, P, steps):
     assert not bad, f"logits differ at steps {bad[:8]} (of {len(bad)})"
 
 
+def test_persistent_narrow_then_wide_model():
+    """Two models of one head_dim share the persistent kernel, whose dynamic LDS (beyond the
+    default limit) grows with the model's widths: the kernel's limit must follow the widest
+    launch so far, not stay at the first model's (launch_util.hpp raise_dynamic_lds).  The
+    narrow model first, then the wide one, in this process: each equals mode 0 bit for bit."""
+    for spec, syn in ((QWEN3_T, SYN), (S.QWEN2_7B.replace(n_layers=2), W.SynthParams(seed=0))):
+        eng = Q.Engine(spec, max_ctx=64).init_synthetic(syn)
+        prompt = [int(t) for t in rng(11).integers(0, spec.vocab, 24)]
+        a = _gen(eng.batch(1, 64), prompt, 8, 0)
+        b = _gen(eng.batch(1, 64), prompt, 8, 1)
+        assert a[0] == b[0], spec.name
+        assert np.array_equal(a[1], b[1]), spec.name
+
+
 def test_persistent_mode_switch_and_refusals():
     """Switching modes mid-sequence continues the same sequence bit for bit (the graph is
     re-captured); batches the persistent step does not cover are refused with a reason."""

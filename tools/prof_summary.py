@@ -35,9 +35,6 @@ ROLE = {
     "gemm8_kernel<1>": "prefill down GEMM (phase-interleaved 256x256, split-K 2, +residual)",
     "gemm8_kernel<0>": "prefill QKV GEMM (phase-interleaved 256x256, +bias)",
     "attn_decode_mfma2_kernel<128, false, 4, false, 128>": "decode attention (fused RoPE/KV append, speculative K/V step, split-K, in-launch combine)",
-    "dec8r_kernel<2, 8, 7, 8>": "fp8 decode gate/up, A in LDS + 4-step ring  [dominant]",
-    "dec8r_kernel<0, 8, 7, 8>": "fp8 decode QKV, A in LDS + 4-step ring",
-    "dec8r_kernel<1, 8, 7, 8>": "fp8 decode O-proj, A in LDS + 4-step ring",
     "gemv_kernel<1, 2, 0, 8, 1, 0, 576> [g 256 x 448]": "bench live timing of down (store epilogue)",
     "gemv_kernel<1, 2, 0, 7, 1, 0, 576> [g 256 x 448]": "bench live timing of O-proj (store epilogue)",
     "synth_kernel": "synthetic weight fill (setup)",
