@@ -1,9 +1,17 @@
-// k_gemm.hip — MFMA bf16 GEMM for the prefill projections (M = prompt rows).
+// k_gemm.hip — MFMA GEMMs for the prefill projections (M = prompt rows).
 //
 // Replaces matrix_mul (layers/src/matrix_mul.cu:165-288) for M > 8: the
 // reference computes one 16x16 WMMA tile per warp with scalar 2-byte loads into
 // per-warp smem and no pipelining.  Here (gfx950):
 //   C[M, N] = A[M, K] . W[N, K]^T   (both operands K-contiguous, "NT")
+// Five kernels, chosen by plan_gemm() (gemm_plan.hpp); gemm() at the end of the file validates,
+// plans, gets the split-K workspace and launches the plan's instantiation:
+//   gemm_kernel      generic 128x128 tile, any K % 8 == 0, bf16 or fp8 weights (below)
+//   gemm_big_kernel  256x256 / 256x128 tile, LDS-DMA into a ring of four 32-deep k-tiles
+//   gemm8_kernel     256x256 tile, phase-interleaved (gemm8_tile.hpp), optional split-K
+//   gemm8sk_kernel   the same tile pipeline over stream-K ranges
+//   gemm8mx_kernel   the same schedule on block-scaled e4m3 operands (fp8 activations)
+// All of them end in gemm_epilogue() (bias / residual / SwiGLU / fp32).  The generic kernel:
 //   * 128x128 block tile, BK = 64, 4 waves as 2x2, 64x64 per wave =
 //     4x4 v_mfma_f32_16x16x32_bf16 accumulators (fp32);
 //   * 16-byte global loads staged through registers into a double-buffered,
@@ -16,15 +24,14 @@
 //     adjacent in dispatch order (weights streamed ~once, activations L2/MALL).
 #include "qie_common.hpp"
 #include "launch_util.hpp"
+#include "gemm_plan.hpp"
+#include "gemm8_tile.hpp"
 #include "../../include/qie/qie_ops.h"
 
 #include <map>
 #include <mutex>
 
 namespace qie {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct GemmParams {
     const uint16_t* A;
@@ -81,6 +88,74 @@ __device__ __forceinline__ uint4 fp8x8_to_bf16(uint2 q, float sc) {
     fp8x4_to_f32(q.y, f + 4);
     return make_uint4(pack2(f[0] * sc, f[1] * sc), pack2(f[2] * sc, f[3] * sc), pack2(f[4] * sc, f[5] * sc),
                       pack2(f[6] * sc, f[7] * sc));
+}
+
+// ---------------- epilogue of every GEMM kernel.  A wave holds NI x NJ accumulator fragments
+// (16x16 each; C/D map: col = lane & 15 = fr, row = 4 * (lane >> 4) + r = 4 fq + r) of the rows
+// from m0 (tile) + wrow (wave) and the weight rows (tile columns) from col0.  SWIGLU: fragment
+// jj is the gate and jj + NJ / 2 the up row of output column swcol0 + 16 jj + fr; STORE adds the
+// bias of the column's segment (b0 / b1 / b2, each may be null).
+struct EpiOut {
+    uint16_t* C;
+    int64_t ldc, M, N, n0, n01;
+};
+template <class P>
+__device__ __forceinline__ EpiOut epi_out(const P& p) {
+    return EpiOut{p.C, p.ldc, p.M, p.N, p.n0, p.n01};
+}
+
+template <int EPI, int NI, int NJ>
+__device__ __forceinline__ void gemm_epilogue(const f32x4 (&acc)[NI][NJ], const EpiOut& o, int64_t m0, int wrow, int64_t col0,
+                                              int64_t swcol0, int fr, int fq, const uint16_t* b0, const uint16_t* b1,
+                                              const uint16_t* b2) {
+#pragma clang fp contract(off)
+    if constexpr (EPI == QIE_EPI_SWIGLU) {
+#pragma unroll
+        for (int i = 0; i < NI; i++) {
+#pragma unroll
+            for (int jj = 0; jj < NJ / 2; jj++) {
+                const int64_t col = swcol0 + 16 * jj + fr;
+                if (col >= o.N) continue;
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int64_t row = m0 + wrow + i * 16 + fq * 4 + r;
+                    if (row >= o.M) continue;
+                    const float g = rbf(acc[i][jj][r]);
+                    const float u = rbf(acc[i][jj + NJ / 2][r]);
+                    const float av = rbf(g * (1.0f / (1.0f + expf(-g))));
+                    o.C[row * o.ldc + col] = f2bf(u * av);
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < NJ; j++) {
+            const int64_t col = col0 + j * 16 + fr;
+            if (col >= o.N) continue;
+            float bias = 0.f;
+            if constexpr (EPI == QIE_EPI_STORE) {
+                const uint16_t* b = col < o.n0 ? b0 : (col < o.n01 ? b1 : b2);
+                if (b) bias = bf2f(b[col < o.n0 ? col : (col < o.n01 ? col - o.n0 : col - o.n01)]);
+            }
+#pragma unroll
+            for (int i = 0; i < NI; i++) {
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    const int64_t row = m0 + wrow + i * 16 + fq * 4 + r;
+                    if (row >= o.M) continue;
+                    if constexpr (EPI == QIE_EPI_F32) {
+                        reinterpret_cast<float*>(o.C)[row * o.ldc + col] = acc[i][j][r];
+                        continue;
+                    }
+                    uint16_t* dst = o.C + row * o.ldc + col;
+                    if constexpr (EPI == QIE_EPI_RESIDUAL)
+                        *dst = f2bf(bf2f(*dst) + rbf(acc[i][j][r]));
+                    else
+                        *dst = f2bf(acc[i][j][r] + bias);
+                }
+            }
+        }
+    }
 }
 
 template <int EPI, int WT>
@@ -190,54 +265,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
         cur ^= 1;
     }
 
-    // ---------------- epilogue.  C/D map: col = lane & 15, row = 4*(lane >> 4) + r.
-    if constexpr (EPI == QIE_EPI_SWIGLU) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-#pragma unroll
-            for (int jj = 0; jj < 2; jj++) {
-                const int64_t col = nblk * 64 + 32 * wc + 16 * jj + fr;
-                if (col >= p.N) continue;
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int64_t row = m0 + wr * 64 + i * 16 + fq * 4 + r;
-                    if (row >= p.M) continue;
-                    float g = rbf(acc[i][jj][r]);
-                    float u = rbf(acc[i][jj + 2][r]);
-                    float av = rbf(g * (1.0f / (1.0f + expf(-g))));
-                    p.C[row * p.ldc + col] = f2bf(u * av);
-                }
-            }
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int64_t col = nblk * BN + wc * 64 + j * 16 + fr;
-            if (col >= p.N) continue;
-            float bias = 0.f;
-            if constexpr (EPI == QIE_EPI_STORE) {
-                const uint16_t* b = col < p.n0 ? p.b0 : (col < p.n01 ? p.b1 : p.b2);
-                if (b) bias = bf2f(b[col < p.n0 ? col : (col < p.n01 ? col - p.n0 : col - p.n01)]);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int64_t row = m0 + wr * 64 + i * 16 + fq * 4 + r;
-                    if (row >= p.M) continue;
-                    if constexpr (EPI == QIE_EPI_F32) {
-                        reinterpret_cast<float*>(p.C)[row * p.ldc + col] = acc[i][j][r];
-                        continue;
-                    }
-                    uint16_t* dst = p.C + row * p.ldc + col;
-                    if constexpr (EPI == QIE_EPI_RESIDUAL)
-                        *dst = f2bf(bf2f(*dst) + rbf(acc[i][j][r]));
-                    else
-                        *dst = f2bf(acc[i][j][r] + bias);
-                }
-            }
-        }
-    }
+    gemm_epilogue<EPI, 4, 4>(acc, epi_out(p), m0, wr * 64, nblk * BN + wc * 64, nblk * 64 + 32 * wc, fr, fq, p.b0, p.b1, p.b2);
 }
 
 // ---------------------------------------------------------------------------
@@ -262,10 +290,6 @@ constexpr int slot_bytes(int bn) { return (BM + bn) * BK * 2; }
 // rows fr (and chunk g) of a 16-row fragment land on 16 distinct bank slots.
 __device__ __forceinline__ int big_swz(int r) { return ((r >> 2) & 1) * 3; }
 
-__device__ __forceinline__ void glds16(const void* src, void* lds) {
-    __builtin_amdgcn_global_load_lds((__attribute__((address_space(1))) void*)(src),
-                                     (__attribute__((address_space(3))) void*)(lds), 16, 0, 0);
-}
 
 // weight row feeding tile column c (0..255) of column tile nt; SwiGLU tiles interleave
 // 32 gate rows and the 32 up rows of the same outputs per 64-column wave slice
@@ -380,325 +404,55 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(GemmParams p, int n_mt) {
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
     }
 
-    // ---------------- epilogue.  C/D map: col = lane & 15, row = 4*(lane >> 4) + r.
-    if constexpr (EPI == QIE_EPI_SWIGLU) {
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-#pragma unroll
-            for (int jj = 0; jj < NJ / 2; jj++) {
-                const int64_t col = nt * (BNT / 2) + (BNT / 8) * wn + 16 * jj + fr;
-                if (col >= p.N) continue;
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int64_t row = m0 + wm * 128 + i * 16 + g * 4 + r;
-                    if (row >= p.M) continue;
-                    const float gg = rbf(acc[i][jj][r]);
-                    const float uu = rbf(acc[i][jj + NJ / 2][r]);
-                    const float av = rbf(gg * (1.0f / (1.0f + expf(-gg))));
-                    p.C[row * p.ldc + col] = f2bf(uu * av);
-                }
-            }
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < NJ; j++) {
-            const int64_t col = nt * BNT + wn * (BNT / 4) + j * 16 + fr;
-            if (col >= p.N) continue;
-            float bias = 0.f;
-            if constexpr (EPI == QIE_EPI_STORE) {
-                const uint16_t* b = col < p.n0 ? p.b0 : (col < p.n01 ? p.b1 : p.b2);
-                if (b) bias = bf2f(b[col < p.n0 ? col : (col < p.n01 ? col - p.n0 : col - p.n01)]);
-            }
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int64_t row = m0 + wm * 128 + i * 16 + g * 4 + r;
-                    if (row >= p.M) continue;
-                    if constexpr (EPI == QIE_EPI_F32) {
-                        reinterpret_cast<float*>(p.C)[row * p.ldc + col] = acc[i][j][r];
-                        continue;
-                    }
-                    uint16_t* dst = p.C + row * p.ldc + col;
-                    if constexpr (EPI == QIE_EPI_RESIDUAL)
-                        *dst = f2bf(bf2f(*dst) + rbf(acc[i][j][r]));
-                    else
-                        *dst = f2bf(acc[i][j][r] + bias);
-                }
-            }
-        }
-    }
+    gemm_epilogue<EPI, 8, NJ>(acc, epi_out(p), m0, wm * 128, nt * BNT + wn * (BNT / 4), nt * (BNT / 2) + (BNT / 8) * wn, fr, g, p.b0,
+                              p.b1, p.b2);
 }
 
 // ---------------------------------------------------------------------------
-// Prefill GEMM, phase-interleaved (round 4; cdna_hip_programming.md §5 "The 256² 8-phase
-// template", written for this NT layout).  256x256 block tile, BK = 64, 8 waves as 2 (M) x 4
-// (N), 128x64 per wave = 8x4 accumulators; LDS = two 64-KB k-tile buffers (A rows then W
-// rows, 128-B rows, 16-B chunk c of row r at c ^ ((r >> 1) & 7): conflict-free
-// ds_read_b128 for the 16x16x32 fragments).  A k-tile is consumed in FOUR phases, one C
-// quadrant (64 x 32 per wave, 16 MFMAs) each:
-//   P1 (qa0, qb0) reads A[qa0] + B[qb0]    P2 (qa0, qb1) reads B[qb1]
-//   P3 (qa1, qb1) reads A[qa1]             P4 (qa1, qb0) (B[qb0] kept in registers)
-// and the k-tile is staged as four 16-KB units in the order it is read: UA0 (the qa0 A rows
-// of both M halves), UB0, UB1, UA1 (2 LDS-DMA instructions per wave each).  Phase P3 of tile
-// t stages UA0(t+2), P4 UB0(t+2), P1 of t+1 UB1(t+2), P2 of t+1 UA1(t+2): every unit lands in
-// its buffer >= 2 phases after the last read of what it overwrites, and is read 5-6 phases
-// after it was issued.  Each phase = [fragment reads, one unit's DMAs, the counted wait]
-// s_barrier [lgkmcnt(0), 16 MFMAs] s_barrier; the wait is vmcnt(8) at the end of P4, P1,
-// P2 (the unit read next phase has landed; 4 units stay in flight), never 0 before the
-// last two tiles.  Waves 4-7 run one barrier behind waves 0-3 (an extra s_barrier before the
-// loop, waves 0-3 one after it), so on every SIMD one wave's MFMAs overlap the other
-// wave's reads and DMA issue.  Accumulation order per output = k order (as gemm_big).
-typedef unsigned int u32x4_g8 __attribute__((ext_vector_type(4)));
-namespace g8 {
-constexpr int BM = 256, BN = 256, BK = 64;
-constexpr int BUF = (BM + BN) * BK * 2;   // 64 KB: A rows [0, 256) then W rows, 128 B each
-}  // namespace g8
+// Prefill GEMM, phase-interleaved: the tile pipeline, its layout and schedule, and the split-K
+// hand-off are in gemm8_tile.hpp.  A kernel chooses its tile and k range, runs the pipeline,
+// optionally merges split-K parts, and runs the epilogue.
 
-__device__ __forceinline__ int g8_swz(int r) { return (r >> 1) & 7; }
+// DMA sources of a bf16 tile: A rows from m0, weight rows of column tile nt
+template <int EPI>
+__device__ __forceinline__ void g8_set_tile(G8Bf16& op, const GemmParams& p, const G8Lane& l, int64_t m0, int64_t nt) {
+    op.map(l, [&](int u, int i, int r, int cs) {
+        if (u == 0 || u == 3) {
+            int64_t ar = m0 + r;
+            ar = ar < p.M ? ar : p.M - 1;   // rows past M: re-read row M-1, never stored
+            op.src[u][i] = p.A + ar * p.lda + cs * 8;
+        } else {
+            op.src[u][i] = big_wrow<EPI, 256>(p, nt, r) + cs * 8;
+        }
+    });
+}
 
-// Split-K (tiles < CUs: Qwen2-7B O / down at 2,048 rows have 112 256x256 tiles, QKV 144): the
-// k-tiles of a tile are cut into `splitk` consecutive parts, one workgroup each (the remap
-// keeps a tile's parts on one XCD).  Every part stores its fp32 accumulators write-through
-// (sc1) into its slab [tile][part] (256 KB, each lane's 16-B accumulator quads in fragment
-// order), drains, and adds to the tile's ticket; the part whose add comes last sums the slabs
-// in PART order (sc1 loads: cdna_hip_programming.md §5 'Projection GEMM' item 2), so the result
-// does not depend on arrival order, runs the epilogue and resets the ticket.
-struct G8Split {
-    int splitk;
-    float* slab;       // [tiles][splitk][256 * 256] fp32
-    unsigned* cnt;     // [tiles], zero at rest
-};
+// epilogue of a 256x256 tile held as 8x4 fragments per wave (as gemm_big_kernel at BNT = 256)
+template <int EPI>
+__device__ __forceinline__ void g8_epilogue(const f32x4 (&acc)[8][4], const EpiOut& o, const G8Lane& l, int64_t m0, int64_t nt,
+                                            const uint16_t* b0, const uint16_t* b1, const uint16_t* b2) {
+    gemm_epilogue<EPI, 8, 4>(acc, o, m0, l.wm * 128, nt * 256 + l.wn * 64, nt * 128 + 32 * l.wn, l.fr, l.g, b0, b1, b2);
+}
 
 template <int EPI>
 __global__ __launch_bounds__(512) void gemm8_kernel(GemmParams p, int n_mt, G8Split sk) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 2, wn = wave & 3;
-    const int fr = lane & 15, g = lane >> 4;
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-    const int wid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+    const G8Lane l = g8_lane();
+    const int wid = xcd_major_wid();
     const int tile = wid / sk.splitk, part = wid % sk.splitk;
     const int64_t mt = tile % n_mt, nt = tile / n_mt;
     const int64_t m0 = mt * g8::BM;
 
-    // DMA sources: unit u (0 UA0, 1 UB0, 2 UB1, 3 UA1), instruction i of this wave moves the
-    // 8-row block b = 2 wave + i of the unit; lane -> row + (lane >> 3), LDS chunk lane & 7
-    // (holding source chunk (lane & 7) ^ swz(row))
-    const uint16_t* src[4][2];
-    int dst_row[4][2];   // tile row of the block (A: 0..255, W: 0..255), wave-uniform
-#pragma unroll
-    for (int u = 0; u < 4; u++)
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            const int b = 2 * wave + i;
-            int row0;
-            if (u == 0 || u == 3) row0 = (b < 8 ? 8 * b : 128 + 8 * (b - 8)) + (u == 3 ? 64 : 0);
-            else row0 = 64 * (b >> 2) + 8 * (b & 3) + (u == 2 ? 32 : 0);
-            dst_row[u][i] = row0;
-            const int r = row0 + (lane >> 3);
-            const int cs = (lane & 7) ^ g8_swz(r);
-            if (u == 0 || u == 3) {
-                int64_t ar = m0 + r;
-                ar = ar < p.M ? ar : p.M - 1;   // rows past M: re-read row M-1, never stored
-                src[u][i] = p.A + ar * p.lda + cs * 8;
-            } else {
-                src[u][i] = big_wrow<EPI, 256>(p, nt, r) + cs * 8;
-            }
-        }
+    G8Bf16 op;
+    g8_set_tile<EPI>(op, p, l, m0, nt);
     const int nk_all = (int)(p.K / g8::BK);
-    const int kb = (int)((int64_t)part * nk_all / sk.splitk);        // this part's k-tiles [kb, kb + nk)
-    const int nk = (int)((int64_t)(part + 1) * nk_all / sk.splitk) - kb;
-    auto stage = [&](int u, int kt) {   // unit u of local k-tile kt into buffer kt & 1
-        unsigned char* buf = smem + (kt & 1) * g8::BUF + ((u == 0 || u == 3) ? 0 : g8::BM * 128);
-        const int64_t k0 = (int64_t)(kb + kt) * g8::BK;
-#pragma unroll
-        for (int i = 0; i < 2; i++) glds16(src[u][i] + k0, buf + dst_row[u][i] * 128);
-    };
-
+    op.kb = (int)((int64_t)part * nk_all / sk.splitk);        // this part's k-tiles [kb, kb + nk)
+    const int nk = (int)((int64_t)(part + 1) * nk_all / sk.splitk) - op.kb;
     f32x4 acc[8][4];
-#pragma unroll
-    for (int i = 0; i < 8; i++)
-#pragma unroll
-        for (int j = 0; j < 4; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    bf16x8 fa[4][2], fb0[2][2], fb1[2][2];
-
-    auto read_a = [&](const unsigned char* buf, int qa) {
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; s2++) {
-                const int row = 128 * wm + 64 * qa + 16 * i + fr;
-                fa[i][s2] = *reinterpret_cast<const bf16x8*>(buf + row * 128 + (((4 * s2 + g) ^ g8_swz(row)) * 16));
-            }
-    };
-    auto read_b = [&](const unsigned char* buf, int qb, bf16x8 (&fb)[2][2]) {
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; s2++) {
-                const int row = 64 * wn + 32 * qb + 16 * j + fr;
-                fb[j][s2] = *reinterpret_cast<const bf16x8*>(buf + g8::BM * 128 + row * 128 +
-                                                             (((4 * s2 + g) ^ g8_swz(row)) * 16));
-            }
-    };
-    auto mfma_q = [&](int qa, int qb, const bf16x8 (&fb)[2][2]) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int s2 = 0; s2 < 2; s2++)
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-#pragma unroll
-                for (int j = 0; j < 2; j++)
-                    acc[4 * qa + i][2 * qb + j] =
-                        __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][s2], fb[j][s2], acc[4 * qa + i][2 * qb + j], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto bar = [&]() {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto wait8 = [&](bool tail) {
-        if (tail) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    };
-
-    // prologue: UA0(0) UB0(0) UB1(0) UA1(0) UA0(1) UB0(1); P1(0) reads UA0(0), UB0(0)
-    stage(0, 0); stage(1, 0); stage(2, 0); stage(3, 0);
-    stage(0, 1); stage(1, 1);
-    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    bar();
-    if (wm == 1) bar();   // waves 4-7 one barrier behind
-    for (int t = 0; t < nk; t++) {
-        const unsigned char* buf = smem + (t & 1) * g8::BUF;
-        const bool tail = t >= nk - 2;
-        // ---- P1 (qa0, qb0): reads A[qa0], B[qb0]; stages UB1(t+1); retires UB1(t)
-        read_b(buf, 0, fb0);
-        __builtin_amdgcn_sched_barrier(0);
-        read_a(buf, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (t + 1 < nk) stage(2, t + 1);
-        wait8(tail);
-        bar();
-        mfma_q(0, 0, fb0);
-        bar();
-        // ---- P2 (qa0, qb1): reads B[qb1]; stages UA1(t+1); retires UA1(t)
-        read_b(buf, 1, fb1);
-        __builtin_amdgcn_sched_barrier(0);
-        if (t + 1 < nk) stage(3, t + 1);
-        wait8(tail);
-        bar();
-        mfma_q(0, 1, fb1);
-        bar();
-        // ---- P3 (qa1, qb1): reads A[qa1]; stages UA0(t+2)
-        read_a(buf, 1);
-        __builtin_amdgcn_sched_barrier(0);
-        if (t + 2 < nk) stage(0, t + 2);
-        bar();
-        mfma_q(1, 1, fb1);
-        bar();
-        // ---- P4 (qa1, qb0): B[qb0] from registers; stages UB0(t+2); retires UA0/UB0(t+1)
-        if (t + 2 < nk) stage(1, t + 2);
-        wait8(tail);
-        bar();
-        mfma_q(1, 0, fb0);
-        bar();
-    }
-    if (wm == 0) bar();   // balance the barrier count of the two wave groups
-
-    if (sk.splitk > 1) {   // uniform
-        // this wave's quads: slab float offset ((wave * 32 + i * 4 + j) * 64 + lane) * 4
-        const int64_t tb = (int64_t)tile * sk.splitk;
-        const auto rs = __builtin_amdgcn_make_buffer_rsrc(sk.slab + (tb + part) * 65536, (short)0, 65536 * 4, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < 8; i++)
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_g8, acc[i][j]), rs,
-                                                       ((wave * 32 + i * 4 + j) * 64 + lane) * 16, 0, 16);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wave drains
-        __syncthreads();
-        int* flag = reinterpret_cast<int*>(smem);   // the staging array is free (one LDS object)
-        if (tid == 0) {
-            const unsigned old = __hip_atomic_fetch_add(sk.cnt + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            *flag = old == (unsigned)sk.splitk - 1 ? 1 : 0;
-        }
-        __syncthreads();
-        if (*flag == 0) return;   // uniform
-#pragma unroll
-        for (int i = 0; i < 8; i++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int q = 0; q < sk.splitk; q++) {   // part order: independent of who arrived last
-            const auto rq = __builtin_amdgcn_make_buffer_rsrc(sk.slab + (tb + q) * 65536, (short)0, 65536 * 4, 0x00020000);
-#pragma unroll
-            for (int i = 0; i < 8; i++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                                  rq, ((wave * 32 + i * 4 + j) * 64 + lane) * 16, 0, 16));
-                    acc[i][j] = q == 0 ? v : acc[i][j] + v;
-                }
-        }
-        if (tid == 0) __hip_atomic_store(sk.cnt + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-
-    // ---------------- epilogue (as gemm_big_kernel at BNT = 256)
-    constexpr int NJ = 4;
-    if constexpr (EPI == QIE_EPI_SWIGLU) {
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-#pragma unroll
-            for (int jj = 0; jj < NJ / 2; jj++) {
-                const int64_t col = nt * 128 + 32 * wn + 16 * jj + fr;
-                if (col >= p.N) continue;
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int64_t row = m0 + wm * 128 + i * 16 + g * 4 + r;
-                    if (row >= p.M) continue;
-                    const float gg = rbf(acc[i][jj][r]);
-                    const float uu = rbf(acc[i][jj + NJ / 2][r]);
-                    const float av = rbf(gg * (1.0f / (1.0f + expf(-gg))));
-                    p.C[row * p.ldc + col] = f2bf(uu * av);
-                }
-            }
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < NJ; j++) {
-            const int64_t col = nt * 256 + wn * 64 + j * 16 + fr;
-            if (col >= p.N) continue;
-            float bias = 0.f;
-            if constexpr (EPI == QIE_EPI_STORE) {
-                const uint16_t* b = col < p.n0 ? p.b0 : (col < p.n01 ? p.b1 : p.b2);
-                if (b) bias = bf2f(b[col < p.n0 ? col : (col < p.n01 ? col - p.n0 : col - p.n01)]);
-            }
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int64_t row = m0 + wm * 128 + i * 16 + g * 4 + r;
-                    if (row >= p.M) continue;
-                    if constexpr (EPI == QIE_EPI_F32) {
-                        reinterpret_cast<float*>(p.C)[row * p.ldc + col] = acc[i][j][r];
-                        continue;
-                    }
-                    uint16_t* dst = p.C + row * p.ldc + col;
-                    if constexpr (EPI == QIE_EPI_RESIDUAL)
-                        *dst = f2bf(bf2f(*dst) + rbf(acc[i][j][r]));
-                    else
-                        *dst = f2bf(acc[i][j][r] + bias);
-                }
-            }
-        }
-    }
+    g8_pipeline<false>(op, l, smem, nk, acc);   // nk >= 4 (plan_gemm)
+    if (sk.splitk > 1 && !g8_splitk_merge(sk, tile, part, smem, l, acc)) return;   // uniform
+    g8_epilogue<EPI>(acc, epi_out(p), l, m0, nt, p.b0, p.b1, p.b2);
 }
 
 // Stream-K form of gemm8 (one workgroup per CU, a fixed grid).  Tile quantisation costs the
@@ -724,203 +478,26 @@ template <int EPI>
 __global__ __launch_bounds__(512) void gemm8sk_kernel(GemmParams p, int n_mt, G8Stream sk) {
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 2, wn = wave & 3;
-    const int fr = lane & 15, g = lane >> 4;
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    // XCD-major workgroup index: consecutive indices (consecutive tiles, which share a weight
-    // tile) sit on one XCD's L2
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = orig & 7;
-    const int wid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+    const G8Lane l = g8_lane();
+    const int nwg = gridDim.x, wid = xcd_major_wid();
     const int nk_all = (int)(p.K / g8::BK);
 
     int64_t m0 = 0, nt = 0;
-    const uint16_t* src[4][2];
-    int dst_row[4][2];
-    auto set_tile = [&](int tile) {
-        const int64_t mt = tile % n_mt;
-        nt = tile / n_mt;
-        m0 = mt * g8::BM;
-#pragma unroll
-        for (int u = 0; u < 4; u++)
-#pragma unroll
-            for (int i = 0; i < 2; i++) {
-                const int b = 2 * wave + i;
-                int row0;
-                if (u == 0 || u == 3) row0 = (b < 8 ? 8 * b : 128 + 8 * (b - 8)) + (u == 3 ? 64 : 0);
-                else row0 = 64 * (b >> 2) + 8 * (b & 3) + (u == 2 ? 32 : 0);
-                dst_row[u][i] = row0;
-                const int r = row0 + (lane >> 3);
-                const int cs = (lane & 7) ^ g8_swz(r);
-                if (u == 0 || u == 3) {
-                    int64_t ar = m0 + r;
-                    ar = ar < p.M ? ar : p.M - 1;
-                    src[u][i] = p.A + ar * p.lda + cs * 8;
-                } else {
-                    src[u][i] = big_wrow<EPI, 256>(p, nt, r) + cs * 8;
-                }
-            }
-    };
-    int kb = 0;
-    auto stage = [&](int u, int kt) {
-        unsigned char* buf = smem + (kt & 1) * g8::BUF + ((u == 0 || u == 3) ? 0 : g8::BM * 128);
-        const int64_t k0 = (int64_t)(kb + kt) * g8::BK;
-#pragma unroll
-        for (int i = 0; i < 2; i++) glds16(src[u][i] + k0, buf + dst_row[u][i] * 128);
-    };
-
+    G8Bf16 op;
     f32x4 acc[8][4];
-    bf16x8 fa[4][2], fb0[2][2], fb1[2][2];
-    auto read_a = [&](const unsigned char* buf, int qa) {
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; s2++) {
-                const int row = 128 * wm + 64 * qa + 16 * i + fr;
-                fa[i][s2] = *reinterpret_cast<const bf16x8*>(buf + row * 128 + (((4 * s2 + g) ^ g8_swz(row)) * 16));
-            }
+    // k-tiles [kb, kb + nk) of `tile` into acc
+    auto run = [&](int tile, int kb, int nk) {
+        nt = tile / n_mt;
+        m0 = (int64_t)(tile % n_mt) * g8::BM;
+        g8_set_tile<EPI>(op, p, l, m0, nt);
+        op.kb = kb;
+        g8_pipeline<true>(op, l, smem, nk, acc);
     };
-    auto read_b = [&](const unsigned char* buf, int qb, bf16x8 (&fb)[2][2]) {
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-#pragma unroll
-            for (int s2 = 0; s2 < 2; s2++) {
-                const int row = 64 * wn + 32 * qb + 16 * j + fr;
-                fb[j][s2] = *reinterpret_cast<const bf16x8*>(buf + g8::BM * 128 + row * 128 +
-                                                             (((4 * s2 + g) ^ g8_swz(row)) * 16));
-            }
-    };
-    auto mfma_q = [&](int qa, int qb, const bf16x8 (&fb)[2][2]) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int s2 = 0; s2 < 2; s2++)
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-#pragma unroll
-                for (int j = 0; j < 2; j++)
-                    acc[4 * qa + i][2 * qb + j] =
-                        __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][s2], fb[j][s2], acc[4 * qa + i][2 * qb + j], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto bar = [&]() {
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto wait8 = [&](bool tail) {
-        if (tail) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    };
-
-    // k-tiles [kb_, kb_ + nk) of the current tile into acc (gemm8_kernel's main loop)
-    auto run = [&](int kb_, int nk) {
-        kb = kb_;
-#pragma unroll
-        for (int i = 0; i < 8; i++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        stage(0, 0); stage(1, 0); stage(2, 0); stage(3, 0);
-        if (nk > 1) {   // uniform
-            stage(0, 1); stage(1, 1);
-            asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        bar();
-        if (wm == 1) bar();
-        for (int t = 0; t < nk; t++) {
-            const unsigned char* buf = smem + (t & 1) * g8::BUF;
-            const bool tail = t >= nk - 2;
-            read_b(buf, 0, fb0);
-            __builtin_amdgcn_sched_barrier(0);
-            read_a(buf, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (t + 1 < nk) stage(2, t + 1);
-            wait8(tail);
-            bar();
-            mfma_q(0, 0, fb0);
-            bar();
-            read_b(buf, 1, fb1);
-            __builtin_amdgcn_sched_barrier(0);
-            if (t + 1 < nk) stage(3, t + 1);
-            wait8(tail);
-            bar();
-            mfma_q(0, 1, fb1);
-            bar();
-            read_a(buf, 1);
-            __builtin_amdgcn_sched_barrier(0);
-            if (t + 2 < nk) stage(0, t + 2);
-            bar();
-            mfma_q(1, 1, fb1);
-            bar();
-            if (t + 2 < nk) stage(1, t + 2);
-            wait8(tail);
-            bar();
-            mfma_q(1, 0, fb0);
-            bar();
-        }
-        if (wm == 0) bar();
-    };
-
-    auto epilogue = [&]() {
-        constexpr int NJ = 4;
-        if constexpr (EPI == QIE_EPI_SWIGLU) {
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-#pragma unroll
-                for (int jj = 0; jj < NJ / 2; jj++) {
-                    const int64_t col = nt * 128 + 32 * wn + 16 * jj + fr;
-                    if (col >= p.N) continue;
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        const int64_t row = m0 + wm * 128 + i * 16 + g * 4 + r;
-                        if (row >= p.M) continue;
-                        const float gg = rbf(acc[i][jj][r]);
-                        const float uu = rbf(acc[i][jj + NJ / 2][r]);
-                        const float av = rbf(gg * (1.0f / (1.0f + expf(-gg))));
-                        p.C[row * p.ldc + col] = f2bf(uu * av);
-                    }
-                }
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < NJ; j++) {
-                const int64_t col = nt * 256 + wn * 64 + j * 16 + fr;
-                if (col >= p.N) continue;
-                float bias = 0.f;
-                if constexpr (EPI == QIE_EPI_STORE) {
-                    const uint16_t* b = col < p.n0 ? p.b0 : (col < p.n01 ? p.b1 : p.b2);
-                    if (b) bias = bf2f(b[col < p.n0 ? col : (col < p.n01 ? col - p.n0 : col - p.n01)]);
-                }
-#pragma unroll
-                for (int i = 0; i < 8; i++) {
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        const int64_t row = m0 + wm * 128 + i * 16 + g * 4 + r;
-                        if (row >= p.M) continue;
-                        if constexpr (EPI == QIE_EPI_F32) {
-                            reinterpret_cast<float*>(p.C)[row * p.ldc + col] = acc[i][j][r];
-                            continue;
-                        }
-                        uint16_t* dst = p.C + row * p.ldc + col;
-                        if constexpr (EPI == QIE_EPI_RESIDUAL)
-                            *dst = f2bf(bf2f(*dst) + rbf(acc[i][j][r]));
-                        else
-                            *dst = f2bf(acc[i][j][r] + bias);
-                    }
-                }
-            }
-        }
-    };
+    auto epilogue = [&]() { g8_epilogue<EPI>(acc, epi_out(p), l, m0, nt, p.b0, p.b1, p.b2); };
 
     // ---- whole tiles
     for (int r = 0; r < sk.dp_rounds; r++) {
-        set_tile(r * nwg + wid);
-        run(0, nk_all);
+        run(r * nwg + wid, 0, nk_all);
         epilogue();
         __syncthreads();   // the next tile's DMA reuses the buffers
     }
@@ -933,178 +510,28 @@ __global__ __launch_bounds__(512) void gemm8sk_kernel(GemmParams p, int n_mt, G8
         const int tile = (int)(u / nk_all);
         const int k0 = (int)(u % nk_all);
         const int k1 = (int)(uend - u < (int64_t)(nk_all - k0) ? k0 + (uend - u) : nk_all);
-        set_tile(tile);
-        run(k0, k1 - k0);
+        run(tile, k0, k1 - k0);
         bool emit = true;
         if (k0 != 0 || k1 != nk_all) {   // uniform: a shared tile
             const int slot = u == ustart ? 0 : 1;
-            const auto rs = __builtin_amdgcn_make_buffer_rsrc(sk.slab + ((int64_t)wid * 2 + slot) * 65536, (short)0,
-                                                              65536 * 4, 0x00020000);
-#pragma unroll
-            for (int i = 0; i < 8; i++)
-#pragma unroll
-                for (int j = 0; j < 4; j++)
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_g8, acc[i][j]), rs,
-                                                           ((wave * 32 + i * 4 + j) * 64 + lane) * 16, 0, 16);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every storing wave drains
-            __syncthreads();
+            g8_slab_store(sk.slab + ((int64_t)wid * 2 + slot) * kG8SlabFloats, l, acc);
             // the tile's segments: ranges wf..wl
             const int64_t tu0 = (int64_t)tile * nk_all - base;
             const int wf = (int)(tu0 / sk.chunk), wl = (int)((tu0 + nk_all - 1) / sk.chunk);
-            int* flag = reinterpret_cast<int*>(smem);
-            if (tid == 0) {
-                const unsigned old = __hip_atomic_fetch_add(sk.cnt + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                *flag = old == (unsigned)(wl - wf) ? 1 : 0;
-            }
-            __syncthreads();
-            emit = *flag != 0;
+            emit = g8_ticket_last(sk.cnt + tile, (unsigned)(wl - wf), smem, l);
             if (emit) {
                 for (int w2 = wf; w2 <= wl; w2++) {   // segment (k) order
                     const int64_t s2 = base + (int64_t)w2 * sk.chunk;
                     const int slot2 = s2 / nk_all == tile ? 0 : 1;
-                    const auto rq = __builtin_amdgcn_make_buffer_rsrc(sk.slab + ((int64_t)w2 * 2 + slot2) * 65536,
-                                                                      (short)0, 65536 * 4, 0x00020000);
-#pragma unroll
-                    for (int i = 0; i < 8; i++)
-#pragma unroll
-                        for (int j = 0; j < 4; j++) {
-                            const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                                          rq, ((wave * 32 + i * 4 + j) * 64 + lane) * 16, 0, 16));
-                            acc[i][j] = w2 == wf ? v : acc[i][j] + v;
-                        }
+                    g8_slab_sum(sk.slab + ((int64_t)w2 * 2 + slot2) * kG8SlabFloats, w2 == wf, l, acc);
                 }
-                if (tid == 0) __hip_atomic_store(sk.cnt + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                g8_ticket_reset(sk.cnt + tile, l);
             }
         }
         if (emit) epilogue();
         u += k1 - k0;
         __syncthreads();
     }
-}
-
-template <int EPI>
-static int launch_gemm8_t(const GemmParams& p, int n_mt, int n_tiles, const G8Split& sk, hipStream_t st) {
-    const void* fn = (const void*)gemm8_kernel<EPI>;
-    constexpr size_t shm = 2 * (size_t)g8::BUF;
-    QIE_TRY(raise_dynamic_lds(fn, shm));
-    hipLaunchKernelGGL((gemm8_kernel<EPI>), dim3((unsigned)(n_tiles * sk.splitk)), dim3(512), shm, st, p, n_mt, sk);
-    QIE_LAUNCH_CHECK();
-    return 0;
-}
-static int launch_gemm8(int epi, const GemmParams& p, int n_mt, int n_tiles, const G8Split& sk, hipStream_t st) {
-    return dispatch_epi(epi, [&](auto E) { return launch_gemm8_t<decltype(E)::value>(p, n_mt, n_tiles, sk, st); });
-}
-
-// Split-K slabs + tickets, one set per stream (streams of one device may run GEMMs at the same
-// time: tensor-parallel ranks on one GPU in the tests), grown on demand outside graph capture.
-struct G8Ws {
-    float* slab = nullptr;
-    unsigned* cnt = nullptr;
-    size_t slab_bytes = 0, cnt_n = 0;
-};
-static std::mutex g8_mu;
-static std::map<hipStream_t, G8Ws> g8_ws;
-
-static int g8_workspace(hipStream_t st, int slabs, int tiles, G8Split* out) {
-    std::lock_guard<std::mutex> lk(g8_mu);
-    G8Ws& w = g8_ws[st];
-    const size_t need = (size_t)slabs * 65536 * 4;
-    if (need > w.slab_bytes || (size_t)tiles > w.cnt_n) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return 1;   // no split
-        QIE_HIP(hipStreamSynchronize(st));
-        const size_t sb = std::max(need, w.slab_bytes), cn = std::max((size_t)tiles, w.cnt_n);   // never shrink
-        if (w.slab) hipFree(w.slab);
-        if (w.cnt) hipFree(w.cnt);
-        w = G8Ws{};
-        QIE_HIP(hipMalloc((void**)&w.slab, sb));
-        QIE_HIP(hipMalloc((void**)&w.cnt, cn * 4));
-        QIE_HIP(hipMemsetAsync(w.cnt, 0, cn * 4, st));   // ordered before this stream's GEMMs
-        w.slab_bytes = sb;
-        w.cnt_n = cn;
-    }
-    out->slab = w.slab;
-    out->cnt = w.cnt;
-    return 0;
-}
-
-template <int EPI>
-static int launch_gemm8sk_t(const GemmParams& p, int n_mt, int grid, const G8Stream& sk, hipStream_t st) {
-    const void* fn = (const void*)gemm8sk_kernel<EPI>;
-    constexpr size_t shm = 2 * (size_t)g8::BUF;
-    QIE_TRY(raise_dynamic_lds(fn, shm));
-    hipLaunchKernelGGL((gemm8sk_kernel<EPI>), dim3((unsigned)grid), dim3(512), shm, st, p, n_mt, sk);
-    QIE_LAUNCH_CHECK();
-    return 0;
-}
-
-// Stream-K plan + workspace (the split-K one: slab [grid][2] tiles, tickets [tiles]);
-// *launched = false: a workspace would have to grow during a graph capture
-static int launch_gemm8sk(int epi, const GemmParams& p, int n_mt, int tiles, hipStream_t st, bool* launched) {
-    *launched = false;
-    const int gk = dev_env("QIE_GEMM8_SK_GRID", 0);   // dev A/B: workgroups (default one per CU)
-    const int grid = gk > 0 ? gk : (int)device_cu_count();
-    const int nk = (int)(p.K / g8::BK);
-    G8Stream sk;
-    sk.tiles = tiles;
-    sk.dp_rounds = tiles / grid;
-    const int64_t rest = (int64_t)(tiles - sk.dp_rounds * grid) * nk;
-    sk.chunk = (int)std::max<int64_t>(1, (rest + grid - 1) / grid);
-    G8Split ws{1, nullptr, nullptr};
-    if (rest > 0 && g8_workspace(st, 2 * grid, tiles, &ws) != 0) return 0;
-    sk.slab = ws.slab;
-    sk.cnt = ws.cnt;
-    *launched = true;
-    return dispatch_epi(epi, [&](auto E) { return launch_gemm8sk_t<decltype(E)::value>(p, n_mt, grid, sk, st); });
-}
-
-// parts per tile: the fewest rounds of (tile, part) items over the CUs, in units of a tile
-// (112 tiles: 2 parts = one round of half tiles; 144 tiles: 3 parts, two rounds of thirds)
-// (short parts lose: QKV at 3 x 19 and O at 2 x 28 k-tiles measured 108 -> 112 and 71 -> 69 us,
-// the last arriver's serial slab read and the per-part pipeline fill eat the gain; down at
-// 2 x 148: 309 -> 247 us), so a part keeps >= 64 k-tiles
-static int g8_splitk(int64_t tiles, int64_t cus, int nk) {
-    int best = 1;
-    double best_t = 1e30;
-    // k-tiles per part at least QIE_GEMM8_SK_MINK (dev A/B; default 64: K >= 4,096 per part).
-    // Round 5: split-K 2 for the O projection at P = 2,048 (112 tiles -> 224, K = 3,584) ran
-    // 94-98 vs 84 µs for the 256x128 kernel; QKV at 3 parts 114 vs 89 — the slab round trip
-    // costs more than the idle CUs at this K
-    const int mink = std::max(4, dev_env("QIE_GEMM8_SK_MINK", 64));
-    for (int s = 1; s <= 4 && nk / s >= mink; s++) {
-        const double t = (double)((tiles * s + cus - 1) / cus) / s;
-        if (t < best_t - 1e-9) {
-            best_t = t;
-            best = s;
-        }
-    }
-    return best;
-}
-
-template <int EPI, int BNT>
-static int launch_gemm_big_t(const GemmParams& p, int n_mt, int n_tiles, hipStream_t st) {
-    const void* fn = (const void*)gemm_big_kernel<EPI, BNT>;
-    constexpr size_t shm = (size_t)big::SLOTS * big::slot_bytes(BNT);
-    QIE_TRY(raise_dynamic_lds(fn, shm));
-    hipLaunchKernelGGL((gemm_big_kernel<EPI, BNT>), dim3((unsigned)n_tiles), dim3(512), shm, st, p, n_mt);
-    QIE_LAUNCH_CHECK();
-    return 0;
-}
-
-template <int BNT>
-static int launch_gemm_big(int epi, const GemmParams& p, int n_mt, int n_tiles, hipStream_t st) {
-    return dispatch_epi(epi, [&](auto E) { return launch_gemm_big_t<decltype(E)::value, BNT>(p, n_mt, n_tiles, st); });
-}
-
-template <int WT>
-static int launch_gemm(int epi, unsigned gm, const GemmParams& p, size_t shm, hipStream_t st) {
-    return dispatch_epi(epi, [&](auto E) {
-        constexpr int EPI = decltype(E)::value;
-        const unsigned gn = (unsigned)cdiv(p.N, EPI == QIE_EPI_SWIGLU ? 64 : BN);   // SwiGLU: 64 outputs per tile
-        hipLaunchKernelGGL((gemm_kernel<EPI, WT>), dim3(gm, gn), dim3(256), shm, st, p);
-        QIE_LAUNCH_CHECK();
-        return 0;
-    });
 }
 
 // ---------------------------------------------------------------------------
@@ -1122,13 +549,14 @@ static int launch_gemm(int epi, unsigned gm, const GemmParams& p, size_t shm, hi
 // same 128-B LDS rows as gemm8's 64 bf16, so the buffers, unit schedule, swizzle and waits are
 // unchanged; a fragment is 32 codes (chunks 2g, 2g + 1 of the row: k = 32 g + [0, 32), the
 // 16x16x128 lane map) and a phase issues 8 MFMAs of twice the cycles instead of 16.
+//   This kernel keeps its OWN copy of the unit map and the phase loop (g8_pipeline's text with
+// the scaled-MFMA fragments): moved onto the shared pipeline behind an operand policy, its
+// prologue compiled differently and the unsplit launches measured 0.6-1 % slower (QKV at 2,048
+// rows 64.1 -> 64.8 us), so only the split-K hand-off and the epilogue are shared.  Change
+// the schedule in gemm8_tile.hpp and here together.
 // Tiled weights (QIE_LINEAR_FP8_T16) are gathered straight from their 1-KiB blocks by the
 // per-lane DMA addresses (chunk c of row r: block (r / 16, c / 4), bytes 16 ((r % 16) +
 // 16 (c % 4))), so the decode layout is the prefill's too — no bf16 copy is read.
-namespace mx {
-constexpr int BK = 128;   // codes per k-tile row (128 B)
-}
-
 struct MxParams {
     const uint8_t* A;     // [M][lda] e4m3 codes
     int64_t lda;          // bytes
@@ -1159,8 +587,6 @@ __device__ __forceinline__ int mx_wrow(const MxParams& p, int64_t nt, int c, int
         return 2;
     }
 }
-
-typedef int i32x8_mx __attribute__((ext_vector_type(8)));
 
 template <int EPI, bool T16>
 __global__ __launch_bounds__(512) void gemm8mx_kernel(MxParams p, int n_mt, G8Split sk, int dbg) {
@@ -1342,113 +768,66 @@ __global__ __launch_bounds__(512) void gemm8mx_kernel(MxParams p, int n_mt, G8Sp
     }
     if (wm == 0) bar();
 
-    if (sk.splitk > 1) {   // uniform (gemm8's split-K hand-off, part order)
-        const int64_t tb = (int64_t)tile * sk.splitk;
-        const auto rs = __builtin_amdgcn_make_buffer_rsrc(sk.slab + (tb + part) * 65536, (short)0, 65536 * 4, 0x00020000);
-#pragma unroll
-        for (int i = 0; i < 8; i++)
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_g8, acc[i][j]), rs,
-                                                       ((wave * 32 + i * 4 + j) * 64 + lane) * 16, 0, 16);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        int* flag = reinterpret_cast<int*>(smem);
-        if (tid == 0) {
-            const unsigned old = __hip_atomic_fetch_add(sk.cnt + tile, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            *flag = old == (unsigned)sk.splitk - 1 ? 1 : 0;
-        }
-        __syncthreads();
-        if (*flag == 0) return;
-#pragma unroll
-        for (int i = 0; i < 8; i++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int q = 0; q < sk.splitk; q++) {
-            const auto rq = __builtin_amdgcn_make_buffer_rsrc(sk.slab + (tb + q) * 65536, (short)0, 65536 * 4, 0x00020000);
-#pragma unroll
-            for (int i = 0; i < 8; i++)
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                                  rq, ((wave * 32 + i * 4 + j) * 64 + lane) * 16, 0, 16));
-                    acc[i][j] = q == 0 ? v : acc[i][j] + v;
-                }
-        }
-        if (tid == 0) __hip_atomic_store(sk.cnt + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-
-    // ---------------- epilogue (gemm8_kernel's)
-    constexpr int NJ = 4;
-    if constexpr (EPI == QIE_EPI_SWIGLU) {
-#pragma unroll
-        for (int i = 0; i < 8; i++) {
-#pragma unroll
-            for (int jj = 0; jj < NJ / 2; jj++) {
-                const int64_t col = nt * 128 + 32 * wn + 16 * jj + fr;
-                if (col >= p.N) continue;
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int64_t row = m0 + wm * 128 + i * 16 + g * 4 + r;
-                    if (row >= p.M) continue;
-                    const float gg = rbf(acc[i][jj][r]);
-                    const float uu = rbf(acc[i][jj + NJ / 2][r]);
-                    const float av = rbf(gg * (1.0f / (1.0f + expf(-gg))));
-                    p.C[row * p.ldc + col] = f2bf(uu * av);
-                }
-            }
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < NJ; j++) {
-            const int64_t col = nt * 256 + wn * 64 + j * 16 + fr;
-            if (col >= p.N) continue;
-            float bias = 0.f;
-            if constexpr (EPI == QIE_EPI_STORE) {
-                const uint16_t* b = col < p.n0 ? p.b[0] : (col < p.n01 ? p.b[1] : p.b[2]);
-                if (b) bias = bf2f(b[col < p.n0 ? col : (col < p.n01 ? col - p.n0 : col - p.n01)]);
-            }
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int64_t row = m0 + wm * 128 + i * 16 + g * 4 + r;
-                    if (row >= p.M) continue;
-                    if constexpr (EPI == QIE_EPI_F32) {
-                        reinterpret_cast<float*>(p.C)[row * p.ldc + col] = acc[i][j][r];
-                        continue;
-                    }
-                    uint16_t* dst = p.C + row * p.ldc + col;
-                    if constexpr (EPI == QIE_EPI_RESIDUAL)
-                        *dst = f2bf(bf2f(*dst) + rbf(acc[i][j][r]));
-                    else
-                        *dst = f2bf(acc[i][j][r] + bias);
-                }
-            }
-        }
-    }
+    const G8Lane l{tid, lane, wave, wm, wn, fr, g};
+    if (sk.splitk > 1 && !g8_splitk_merge(sk, tile, part, smem, l, acc)) return;   // uniform
+    gemm_epilogue<EPI, 8, 4>(acc, epi_out(p), m0, wm * 128, nt * 256 + wn * 64, nt * 128 + 32 * wn, fr, g, p.b[0], p.b[1], p.b[2]);
 }
 
-template <int EPI, bool T16>
-static int launch_gemm8mx_t(const MxParams& p, int n_mt, int n_tiles, const G8Split& sk, hipStream_t st) {
-    const void* fn = (const void*)gemm8mx_kernel<EPI, T16>;
-    constexpr size_t shm = 2 * (size_t)g8::BUF;
-    QIE_TRY(raise_dynamic_lds(fn, shm));
-    static const int dbg = dev_env("QIE_MX_DBG", 0);
-    hipLaunchKernelGGL((gemm8mx_kernel<EPI, T16>), dim3((unsigned)(n_tiles * sk.splitk)), dim3(512), shm, st, p, n_mt,
-                       sk, dbg);
+// ---------------------------------------------------------------------------
+// Split-K slabs + tickets, one set per stream (streams of one device may run GEMMs at the same
+// time: tensor-parallel ranks on one GPU in the tests), grown on demand outside graph capture.
+struct G8Ws {
+    float* slab = nullptr;
+    unsigned* cnt = nullptr;
+    size_t slab_bytes = 0, cnt_n = 0;
+};
+static std::mutex g8_mu;
+static std::map<hipStream_t, G8Ws> g8_ws;
+
+// nonzero: the workspace would have to grow during a graph capture
+static int g8_workspace(hipStream_t st, int slabs, int tiles, G8Split* out) {
+    std::lock_guard<std::mutex> lk(g8_mu);
+    G8Ws& w = g8_ws[st];
+    const size_t need = (size_t)slabs * kG8SlabFloats * 4;
+    if (need > w.slab_bytes || (size_t)tiles > w.cnt_n) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return 1;   // no split
+        QIE_HIP(hipStreamSynchronize(st));
+        const size_t sb = std::max(need, w.slab_bytes), cn = std::max((size_t)tiles, w.cnt_n);   // never shrink
+        if (w.slab) hipFree(w.slab);
+        if (w.cnt) hipFree(w.cnt);
+        w = G8Ws{};
+        QIE_HIP(hipMalloc((void**)&w.slab, sb));
+        QIE_HIP(hipMalloc((void**)&w.cnt, cn * 4));
+        QIE_HIP(hipMemsetAsync(w.cnt, 0, cn * 4, st));   // ordered before this stream's GEMMs
+        w.slab_bytes = sb;
+        w.cnt_n = cn;
+    }
+    out->slab = w.slab;
+    out->cnt = w.cnt;
+    return 0;
+}
+
+static GemmKnobs dev_gemm_knobs() {
+    GemmKnobs k;
+    k.gemm_big = dev_env("QIE_GEMM_BIG", k.gemm_big);
+    k.gemm8 = dev_env("QIE_GEMM8", k.gemm8);
+    k.sk_grid = dev_env("QIE_GEMM8_SK_GRID", k.sk_grid);
+    k.sk_mink = dev_env("QIE_GEMM8_SK_MINK", k.sk_mink);
+    k.mx_splitk_max = dev_env("QIE_MX_SPLITK_MAX", k.mx_splitk_max);
+    return k;
+}
+
+template <class... P, class... A>
+static int launch_plan(void (*kernel)(P...), const GemmPlan& pl, hipStream_t st, A... args) {
+    QIE_TRY(raise_dynamic_lds((const void*)kernel, pl.lds_bytes));
+    hipLaunchKernelGGL(kernel, dim3(pl.grid_x, pl.grid_y), dim3(pl.threads), pl.lds_bytes, st, args...);
     QIE_LAUNCH_CHECK();
     return 0;
 }
-template <bool T16>
-static int launch_gemm8mx(int epi, const MxParams& p, int n_mt, int n_tiles, const G8Split& sk, hipStream_t st) {
-    return dispatch_epi(epi, [&](auto E) { return launch_gemm8mx_t<decltype(E)::value, T16>(p, n_mt, n_tiles, sk, st); });
-}
 
-// QIE_LINEAR_ACT_FP8 (qie_ops.h): every M, one 256x256 kernel; split-K where the tiles do not
-// fill the chip once (the fewest rounds of (tile, part) items; parts of >= 8 k-tiles)
-static int gemm_mx(const qie_linear_args* a, hipStream_t st) {
-    const bool t16 = (a->flags & QIE_LINEAR_FP8_T16) != 0;
+// QIE_LINEAR_ACT_FP8: what gemm8mx_kernel needs of the arguments
+static int check_mx(const qie_linear_args* a) {
     QIE_REQUIRE((a->flags & QIE_LINEAR_FP8) && a->x_exps, "qie_linear: ACT_FP8 needs fp8 weights and x_exps");
     QIE_REQUIRE(a->K % mx::BK == 0 && a->ldx >= a->K && a->ldx % 16 == 0,
                 "qie_linear: ACT_FP8 needs K %% 128 == 0 and ldx (bytes) %% 16 == 0");
@@ -1458,124 +837,74 @@ static int gemm_mx(const qie_linear_args* a, hipStream_t st) {
     QIE_REQUIRE(((int64_t)cdiv(a->M, 256) * 256) * a->ldx < ((int64_t)1 << 32),
                 "qie_linear: ACT_FP8 with M (%lld) x ldx (%lld) >= 2^32 bytes of codes (split the rows)",
                 (long long)a->M, (long long)a->ldx);
-    if (t16)
+    if (a->flags & QIE_LINEAR_FP8_T16)
         QIE_REQUIRE(a->epilogue == QIE_EPI_SWIGLU ? a->N % 16 == 0
                                                   : a->seg_rows[0] % 16 == 0 && a->seg_rows[1] % 16 == 0 &&
                                                         a->seg_rows[2] % 16 == 0,
                     "qie_linear: tiled fp8 segments must be whole 16-row tiles");
-    MxParams p;
-    p.A = (const uint8_t*)a->x;
-    p.lda = a->ldx;
-    p.ea = a->x_exps;
-    for (int i = 0; i < 3; i++) {
-        p.w[i] = (const uint8_t*)a->w[i];
-        p.b[i] = (const uint16_t*)a->bias[i];
-    }
-    const bool sw = a->epilogue == QIE_EPI_SWIGLU;
-    p.rows[0] = sw ? a->N : a->seg_rows[0];
-    p.rows[1] = sw ? a->N : a->seg_rows[1];
-    p.rows[2] = sw ? 0 : a->seg_rows[2];
-    p.n0 = a->seg_rows[0];
-    p.n01 = a->seg_rows[0] + a->seg_rows[1];
-    p.M = a->M;
-    p.K = a->K;
-    p.N = a->N;
-    p.C = (uint16_t*)a->y;
-    p.ldc = a->ldy;
-    const int64_t cols = sw ? 2 * a->N : a->N;
-    const int64_t n_mt = cdiv(a->M, g8::BM), tiles = n_mt * cdiv(cols, 256);
-    const int64_t cus = device_cu_count();
-    const int nk = (int)(a->K / mx::BK);
-    G8Split sk{1, nullptr, nullptr};
-    // split only below half the chip (r05, same box, 2,048 rows): O (112 tiles) 91.0 unsplit
-    // vs 78.0 split 3, down (112) 307 vs 188; QKV (144 tiles) 69.4 unsplit vs 93.9 split 3
-    if (2 * tiles <= cus) {
-        int best = 1;
-        double best_t = 1e30;
-        const int smax = dev_env("QIE_MX_SPLITK_MAX", 4);
-        for (int s = 1; s <= smax && nk / s >= 8; s++) {
-            const double t = (double)((tiles * s + cus - 1) / cus) / s;
-            if (t < best_t - 1e-9) {
-                best_t = t;
-                best = s;
-            }
-        }
-        if (best > 1 && g8_workspace(st, (int)tiles * best, (int)tiles, &sk) == 0) sk.splitk = best;
-    }
-    return t16 ? launch_gemm8mx<true>(a->epilogue, p, (int)n_mt, (int)tiles, sk, st)
-               : launch_gemm8mx<false>(a->epilogue, p, (int)n_mt, (int)tiles, sk, st);
+    return 0;
 }
 
+// validate, fill the kernels' argument blocks, plan, get the workspace, launch the plan
 int gemm(const qie_linear_args* a, hipStream_t st) {
-    if (a->flags & QIE_LINEAR_ACT_FP8) return gemm_mx(a, st);
-    QIE_REQUIRE(a->norm_w == nullptr, "qie_linear: fused RMSNorm is GEMV-only (M <= 8)");
-    QIE_REQUIRE(a->argmax_keys == nullptr, "qie_linear: fused arg-max is GEMV-only (M <= 8)");
+    const bool act8 = (a->flags & QIE_LINEAR_ACT_FP8) != 0;
+    if (act8) {
+        QIE_TRY(check_mx(a));
+    } else {
+        QIE_REQUIRE(a->norm_w == nullptr, "qie_linear: fused RMSNorm is GEMV-only (M <= 8)");
+        QIE_REQUIRE(a->argmax_keys == nullptr, "qie_linear: fused arg-max is GEMV-only (M <= 8)");
+        QIE_REQUIRE(a->K % 8 == 0, "qie_linear: GEMM needs K %% 8 == 0");
+    }
+    const bool sw = a->epilogue == QIE_EPI_SWIGLU;
     GemmParams p;
+    MxParams m;
     p.A = (const uint16_t*)a->x;
-    p.lda = a->ldx;
+    m.A = (const uint8_t*)a->x;
+    m.ea = a->x_exps;
     p.w0 = (const uint16_t*)a->w[0];
     p.w1 = (const uint16_t*)a->w[1];
     p.w2 = (const uint16_t*)a->w[2];
     p.b0 = (const uint16_t*)a->bias[0];
     p.b1 = (const uint16_t*)a->bias[1];
     p.b2 = (const uint16_t*)a->bias[2];
-    p.n0 = a->seg_rows[0];
-    p.n01 = a->seg_rows[0] + a->seg_rows[1];
-    p.M = a->M;
-    p.K = a->K;
-    p.N = a->N;
-    p.wrows = 0;
-    p.C = (uint16_t*)a->y;
-    p.ldc = a->ldy;
-    const size_t shm = (size_t)2 * (BM + BN) * BK * 2;
-    const unsigned gm = (unsigned)cdiv(a->M, BM);
-    QIE_REQUIRE(a->K % 8 == 0, "qie_linear: GEMM needs K %% 8 == 0");
-    if (!(a->flags & QIE_LINEAR_FP8) && a->K % big::BK == 0 && a->ldx % 8 == 0) {
-        // LDS-DMA kernel: 256x256 tiles when they fill the chip at least once (config 4's
-        // O / down at 8,192 rows: 448 tiles; the generic 128x128 kernel took them before), else
-        // 256x128 when those fill >= 3/4 of it in one round (Qwen2-7B O and down projections
-        // at 2,048 rows: 112 vs 224 tiles on 256 CUs), else 256x256 in one round (below).
-        // args.flags QIE_LINEAR_TILE256 / TILE128 force a tile (tests; dev builds also
-        // QIE_GEMM_BIG = 1 / 2, 0 disables the kernel for A/B timing).
-        const int64_t cols = a->epilogue == QIE_EPI_SWIGLU ? 2 * a->N : a->N;
-        const int64_t n_mt = cdiv(a->M, big::BM);
-        const int64_t t256 = n_mt * cdiv(cols, 256), t128 = n_mt * cdiv(cols, 128);
-        const int64_t cus = device_cu_count();
-        const int force = (a->flags & QIE_LINEAR_TILE256) ? 1 : (a->flags & QIE_LINEAR_TILE128) ? 2
-                                                                                            : dev_env("QIE_GEMM_BIG", -1);
-        // phase-interleaved 256x256 kernel (K a multiple of 64, >= 4 k-tiles): Qwen2-7B gate/up at 2,048
-        // rows 612 -> 488 us, bit-identical to gemm_big; down split-K 2: 309 -> 247 us
-        const bool g8ok = a->K % g8::BK == 0 && a->K >= 4 * g8::BK;
-        const int g8mode = dev_env("QIE_GEMM8", 2);   // 2 (default): + split-K below; 1: full-chip grids only; 0: off
-        // stream-K (QIE_GEMM8 = 3; args.flags QIE_LINEAR_STREAMK): any tile count, one workgroup per CU
-        if (g8ok && ((a->flags & QIE_LINEAR_STREAMK) || (g8mode == 3 && force < 0 && a->M >= big::BM))) {
-            bool launched = false;
-            const int rc = launch_gemm8sk(a->epilogue, p, (int)n_mt, (int)t256, st, &launched);
-            if (rc || launched) return rc;
-        }
-        if (g8ok && g8mode != 0 && force != 2 && (force == 1 || (force < 0 && a->M >= big::BM && t256 >= cus))) {
-            G8Split sk{1, nullptr, nullptr};
-            return launch_gemm8(a->epilogue, p, (int)n_mt, (int)t256, sk, st);
-        }
-        if (g8ok && g8mode == 2 && force < 0 && a->M >= big::BM && t256 < cus) {
-            const int s = g8_splitk(t256, cus, (int)(a->K / g8::BK));
-            G8Split sk{1, nullptr, nullptr};
-            // unsplit, 256x256 tiles must still cover half the chip: QKV at 144 tiles 101.7 ->
-            // 87.8 us, but O at 112 tiles 78 -> 103 us (its 256x128 kernel fills 224 CUs)
-            if ((s == 1 && 2 * t256 >= cus) || (s > 1 && g8_workspace(st, (int)t256 * s, (int)t256, &sk) == 0 && (sk.splitk = s) > 1))
-                return launch_gemm8(a->epilogue, p, (int)n_mt, (int)t256, sk, st);
-        }
-        if (force == 1 || (force < 0 && a->M >= big::BM && t256 >= cus))
-            return launch_gemm_big<256>(a->epilogue, p, (int)n_mt, (int)t256, st);
-        if (force == 2 || (force < 0 && a->M >= big::BM && t128 >= (3 * cus) / 4 && t128 <= cus))
-            return launch_gemm_big<128>(a->epilogue, p, (int)n_mt, (int)t128, st);
-        // 256-column tiles in ONE round when 128-column ones would take two (Qwen2-7B QKV at
-        // 2,048 rows: 144 vs 288 tiles on 256 CUs): 124 -> 99 us against the generic kernel
-        if (force < 0 && a->M >= big::BM && t256 >= cus / 2 && t256 <= cus && t128 > cus)
-            return launch_gemm_big<256>(a->epilogue, p, (int)n_mt, (int)t256, st);
+    for (int i = 0; i < 3; i++) {
+        m.w[i] = (const uint8_t*)a->w[i];
+        m.b[i] = (const uint16_t*)a->bias[i];
+        m.rows[i] = sw ? (i < 2 ? a->N : 0) : a->seg_rows[i];
     }
-    if (a->flags & QIE_LINEAR_FP8) return launch_gemm<1>(a->epilogue, gm, p, shm, st);
-    return launch_gemm<0>(a->epilogue, gm, p, shm, st);
+    p.lda = m.lda = a->ldx;
+    p.n0 = m.n0 = a->seg_rows[0];
+    p.n01 = m.n01 = a->seg_rows[0] + a->seg_rows[1];
+    p.M = m.M = a->M;
+    p.K = m.K = a->K;
+    p.N = m.N = a->N;
+    p.wrows = 0;
+    p.C = m.C = (uint16_t*)a->y;
+    p.ldc = m.ldc = a->ldy;
+
+    const GemmKnobs k = dev_gemm_knobs();
+    const int cus = device_cu_count();
+    GemmPlan pl = plan_gemm(*a, k, cus);
+    G8Split ws{1, nullptr, nullptr};
+    // no workspace (it would have to grow during a graph capture): what plan_gemm chooses without
+    if (pl.slabs > 0 && g8_workspace(st, pl.slabs, pl.tickets, &ws) != 0) pl = plan_gemm(*a, k, cus, false);
+    ws.splitk = pl.splitk;
+    const G8Stream sk{pl.dp_rounds, pl.tiles, pl.chunk, ws.slab, ws.cnt};
+    static const int mx_dbg = dev_env("QIE_MX_DBG", 0);
+    return dispatch_epi(a->epilogue, [&](auto E) {
+        constexpr int EPI = decltype(E)::value;
+        switch (pl.family) {
+            case GemmFamily::Generic: return launch_plan(gemm_kernel<EPI, 0>, pl, st, p);
+            case GemmFamily::GenericFp8: return launch_plan(gemm_kernel<EPI, 1>, pl, st, p);
+            case GemmFamily::Big256: return launch_plan(gemm_big_kernel<EPI, 256>, pl, st, p, pl.n_mt);
+            case GemmFamily::Big128: return launch_plan(gemm_big_kernel<EPI, 128>, pl, st, p, pl.n_mt);
+            case GemmFamily::Gemm8: return launch_plan(gemm8_kernel<EPI>, pl, st, p, pl.n_mt, ws);
+            case GemmFamily::Gemm8StreamK: return launch_plan(gemm8sk_kernel<EPI>, pl, st, p, pl.n_mt, sk);
+            case GemmFamily::Mx: return launch_plan(gemm8mx_kernel<EPI, false>, pl, st, m, pl.n_mt, ws, mx_dbg);
+            case GemmFamily::MxT16: return launch_plan(gemm8mx_kernel<EPI, true>, pl, st, m, pl.n_mt, ws, mx_dbg);
+        }
+        return fail(-22, "qie_linear: internal: unplanned GEMM family");
+    });
 }
 
 }  // namespace qie

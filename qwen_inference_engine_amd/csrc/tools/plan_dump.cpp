@@ -1,23 +1,44 @@
-// plan_dump — prints the launch plan of M <= 16 linear layers (linear_plan.hpp) without a GPU.
-// Plain host program (`make plan_dump`); tests/test_linear_plan_cpu.py compares its output with
-// a table derived by hand.
+// plan_dump — prints the launch plan of linear layers without a GPU: M <= 16 rows by
+// plan_linear (linear_plan.hpp); more rows, rows that plan hands to the GEMM, and fp8 activations
+// (QIE_LINEAR_ACT_FP8) at any M by plan_gemm (gemm_plan.hpp).  Plain host program
+// (`make plan_dump`); tests/test_linear_plan_cpu.py and tests/test_gemm_plan_cpu.py compare its
+// output with tables derived by hand.
 //
 // stdin, one shape per line:
 //   name M K N epilogue norm flags seg0,seg1,seg2 resident_blocks [knob=value ...]
 // epilogue: STORE RESIDUAL SWIGLU F32; norm: 0 / 1; flags: the QIE_LINEAR_* bits;
 // resident_blocks: what the occupancy query returns for the launch (used where the plan needs
-// it); knobs: balanced, blocks_per_cu (Knobs fields).  The device has 256 CUs.
+// it); knobs: balanced, blocks_per_cu (Knobs fields), gemm_big, gemm8, sk_grid, sk_mink,
+// mx_splitk_max (GemmKnobs fields), allow_split (plan_gemm's argument).  The device has 256 CUs.
 #include <cstdio>
 #include <cstring>
 #include <iostream>
 #include <sstream>
 #include <string>
 
+#include "../gemm_plan.hpp"
 #include "../linear_plan.hpp"
 
 using namespace qie;
 
 static const char* kEpi[] = {"STORE", "RESIDUAL", "SWIGLU", "F32"};
+
+static void print_gemm_plan(const GemmPlan& g, int epi) {
+    const char* e = kEpi[epi];
+    switch (g.family) {
+        case GemmFamily::Generic: printf(" gemm_kernel<%s,0>", e); break;
+        case GemmFamily::GenericFp8: printf(" gemm_kernel<%s,1>", e); break;
+        case GemmFamily::Big256: printf(" gemm_big_kernel<%s,256>", e); break;
+        case GemmFamily::Big128: printf(" gemm_big_kernel<%s,128>", e); break;
+        case GemmFamily::Gemm8: printf(" gemm8_kernel<%s> splitk=%d", e, g.splitk); break;
+        case GemmFamily::Gemm8StreamK: printf(" gemm8sk_kernel<%s> dp_rounds=%d chunk=%d", e, g.dp_rounds, g.chunk); break;
+        case GemmFamily::Mx: printf(" gemm8mx_kernel<%s,0> splitk=%d", e, g.splitk); break;
+        case GemmFamily::MxT16: printf(" gemm8mx_kernel<%s,1> splitk=%d", e, g.splitk); break;
+    }
+    printf(" n_mt=%d tiles=%d slabs=%d tickets=%d grid=%u", g.n_mt, g.tiles, g.slabs, g.tickets, g.grid_x);
+    if (g.grid_y != 1) printf("x%u", g.grid_y);
+    printf(" threads=%d lds=%zu\n", g.threads, g.lds_bytes);
+}
 
 int main() {
     const int cus = 256;
@@ -45,19 +66,32 @@ int main() {
         for (int s = 0; s < 3; s++) a.w[s] = a.seg_rows[s] ? dummy : nullptr;
         a.norm_w = norm ? dummy : nullptr;
         Knobs k;
+        GemmKnobs gk;
+        bool allow_split = true;
         while (in >> kv) {
             const size_t eq = kv.find('=');
             const std::string key = kv.substr(0, eq);
             const int v = atoi(kv.c_str() + eq + 1);
             if (key == "balanced") k.balanced = v;
             else if (key == "blocks_per_cu") k.blocks_per_cu = v;
+            else if (key == "gemm_big") gk.gemm_big = v;
+            else if (key == "gemm8") gk.gemm8 = v;
+            else if (key == "sk_grid") gk.sk_grid = v;
+            else if (key == "sk_mink") gk.sk_mink = v;
+            else if (key == "mx_splitk_max") gk.mx_splitk_max = v;
+            else if (key == "allow_split") allow_split = v != 0;
             else {
                 fprintf(stderr, "plan_dump: unknown knob %s\n", key.c_str());
                 return 2;
             }
         }
-        const LinearPlan pl = plan_linear(a, LinearExtras{}, cus, k);
         printf("%s:", name.c_str());
+        // qie_linear's routing: fp8 activations and M > 16 go straight to the GEMM
+        if ((a.flags & QIE_LINEAR_ACT_FP8) || a.M > 16) {
+            print_gemm_plan(plan_gemm(a, gk, cus, allow_split), a.epilogue);
+            continue;
+        }
+        const LinearPlan pl = plan_linear(a, LinearExtras{}, cus, k);
         if (pl.error != PlanError::None) {
             printf(" error %d\n", (int)pl.error);
             continue;
@@ -66,7 +100,7 @@ int main() {
             case LinearFamily::Dec8:
                 printf(" dec8 KU=%d KS=%d parts=%d\n", pl.dec8_ku, pl.dec8_ks, pl.dec8_parts);
                 continue;
-            case LinearFamily::Gemm: printf(" gemm\n"); continue;
+            case LinearFamily::Gemm: print_gemm_plan(plan_gemm(a, gk, cus, allow_split), a.epilogue); continue;
             case LinearFamily::Skinny:
                 printf(" skinny_mfma_kernel<%s,%d,%d,4,%d> t16=%d", kEpi[pl.epi], pl.wt, pl.xlds, pl.uo, (int)pl.t16);
                 break;

@@ -132,6 +132,68 @@ def test_linear_swiglu(oracle, qlib, M, K, I):
     assert not ((d > 2) & ~ill).any(), f"well-conditioned element off by {d[~ill].max()} ulps"
 
 
+def _big_gemm_case(oracle, qlib, M, K, epi, fl, n3=(200, 72, 40), n_res=320, n_sw=200, n_f32=264, runs=1):
+    """One prefill-GEMM launch per run (flags fl) against the oracle, per epilogue: "store3" three
+    segments with bias (assert_sum_close), "residual", "swiglu", "f32" (1e-5 of sum|a*w|).  Every
+    run writes a fresh output; all runs must agree bit for bit, the first is checked."""
+    x = rand_bf16(oracle, (M, K), seed=M + K)
+    dx = G.dev(x)
+
+    def launches(fresh, launch):
+        ys = []
+        for _ in range(runs):
+            y = fresh()
+            launch(y)
+            ys.append(G.host(y) if epi == "f32" else G.host_bf16(y))
+        for other in ys[1:]:
+            assert np.array_equal(ys[0], other), f"{epi}: two launches differ"
+        return ys[0]
+
+    if epi == "store3":
+        n = n3
+        ws = [rand_bf16(oracle, (r, K), 0.05, seed=30 + i) for i, r in enumerate(n)]
+        bs = [rand_bf16(oracle, (r,), 0.1, seed=40 + i) for i, r in enumerate(n)]
+        N = sum(n)
+        want = np.concatenate([oracle.matmul(x, w, b) for w, b in zip(ws, bs)], axis=1)
+        segs, dbs = [(G.dev(w), r) for w, r in zip(ws, n)], [G.dev(b) for b in bs]
+        got = launches(lambda: G.zeros_bf16(M, N),
+                       lambda y: _linear(qlib, dx, segs, dbs, M, K, N, y, _lib.QIE_EPI_STORE, flags=fl))
+        scale = np.concatenate([_abs_scale(oracle, x, w) for w in ws], axis=1)
+        G.assert_sum_close(got, want, scale, what=f"big store M={M} K={K}")
+    elif epi == "residual":
+        N = n_res
+        w = rand_bf16(oracle, (N, K), 0.02, seed=4)
+        res = rand_bf16(oracle, (M, N), seed=5)
+        want = oracle.resadd(res, oracle.matmul(x, w))
+        dw = G.dev(w)
+        got = launches(lambda: G.dev(res),
+                       lambda y: _linear(qlib, dx, [(dw, N)], [], M, K, N, y, _lib.QIE_EPI_RESIDUAL, flags=fl))
+        acc = G.bf(oracle.matmul(x, w)).astype(np.float64)
+        tol = 2.0 ** -7 * (np.abs(acc) + np.abs(G.bf(want))) + 1e-5 * _abs_scale(oracle, x, w)
+        assert (np.abs(G.bf(got).astype(np.float64) - G.bf(want)) <= tol).all()
+    elif epi == "swiglu":
+        I = n_sw
+        wg = rand_bf16(oracle, (I, K), 0.08, seed=7)
+        wu = rand_bf16(oracle, (I, K), 0.08, seed=8)
+        want = oracle.silu_mul(oracle.matmul(x, wg), oracle.matmul(x, wu))
+        segs = [(G.dev(wg), I), (G.dev(wu), I)]
+        got = launches(lambda: G.zeros_bf16(M, I),
+                       lambda y: _linear(qlib, dx, segs, [], M, K, I, y, _lib.QIE_EPI_SWIGLU, flags=fl))
+        d = G.ulp_diff(got, want)
+        gs = G.bf(oracle.matmul(x, wg)).astype(np.float64)
+        u = np.abs(G.bf(oracle.matmul(x, wu)).astype(np.float64))
+        ill = (np.abs(gs) < 1e-2 * _abs_scale(oracle, x, wg)) | (u < 1e-2 * _abs_scale(oracle, x, wu)) | (gs < -4)
+        assert (d == 0).mean() > 0.97 and not ((d > 2) & ~ill).any()
+    else:
+        N = n_f32
+        w = rand_bf16(oracle, (N, K), 0.05, seed=9)
+        dw = G.dev(w)
+        got = launches(lambda: G.zeros((M, N), np.float32),
+                       lambda y: _linear(qlib, dx, [(dw, N)], [], M, K, N, y, _lib.QIE_EPI_F32, flags=fl))
+        want = oracle.bf16_to_f32(x).astype(np.float64) @ oracle.bf16_to_f32(w).astype(np.float64).T
+        assert np.abs(got - want).max() <= 1e-5 * _abs_scale(oracle, x, w).max() + 1e-6
+
+
 @pytest.mark.parametrize("M,K", [(256, 896), (300, 96), (520, 32), (257, 3584)])
 @pytest.mark.parametrize("epi", ["store3", "residual", "swiglu", "f32"])
 @pytest.mark.parametrize("tile", ["1", "2", "sk"])
@@ -142,48 +204,19 @@ def test_linear_big_gemm(oracle, qlib, M, K, epi, tile):
     "sk" the stream-K form (QIE_LINEAR_STREAMK, K % 64 == 0 and >= 256 only): at these sizes
     every workgroup gets ONE k-tile, so each tile is summed from 14 or 56 segments."""
     fl = {"1": _lib.QIE_LINEAR_TILE256, "2": _lib.QIE_LINEAR_TILE128, "sk": _lib.QIE_LINEAR_STREAMK}[tile]
-    x = rand_bf16(oracle, (M, K), seed=M + K)
-    if epi == "store3":
-        n = (200, 72, 40)
-        ws = [rand_bf16(oracle, (r, K), 0.05, seed=30 + i) for i, r in enumerate(n)]
-        bs = [rand_bf16(oracle, (r,), 0.1, seed=40 + i) for i, r in enumerate(n)]
-        N = sum(n)
-        want = np.concatenate([oracle.matmul(x, w, b) for w, b in zip(ws, bs)], axis=1)
-        y = G.zeros_bf16(M, N)
-        _linear(qlib, G.dev(x), [(G.dev(w), r) for w, r in zip(ws, n)], [G.dev(b) for b in bs], M, K, N, y,
-                _lib.QIE_EPI_STORE, flags=fl)
-        scale = np.concatenate([_abs_scale(oracle, x, w) for w in ws], axis=1)
-        G.assert_sum_close(G.host_bf16(y), want, scale, what=f"big store M={M} K={K}")
-    elif epi == "residual":
-        N = 320
-        w = rand_bf16(oracle, (N, K), 0.02, seed=4)
-        res = rand_bf16(oracle, (M, N), seed=5)
-        want = oracle.resadd(res, oracle.matmul(x, w))
-        y = G.dev(res)
-        _linear(qlib, G.dev(x), [(G.dev(w), N)], [], M, K, N, y, _lib.QIE_EPI_RESIDUAL, flags=fl)
-        acc = G.bf(oracle.matmul(x, w)).astype(np.float64)
-        tol = 2.0 ** -7 * (np.abs(acc) + np.abs(G.bf(want))) + 1e-5 * _abs_scale(oracle, x, w)
-        assert (np.abs(G.bf(G.host_bf16(y)).astype(np.float64) - G.bf(want)) <= tol).all()
-    elif epi == "swiglu":
-        I = 200
-        wg = rand_bf16(oracle, (I, K), 0.08, seed=7)
-        wu = rand_bf16(oracle, (I, K), 0.08, seed=8)
-        want = oracle.silu_mul(oracle.matmul(x, wg), oracle.matmul(x, wu))
-        y = G.zeros_bf16(M, I)
-        _linear(qlib, G.dev(x), [(G.dev(wg), I), (G.dev(wu), I)], [], M, K, I, y, _lib.QIE_EPI_SWIGLU, flags=fl)
-        got = G.host_bf16(y)
-        d = G.ulp_diff(got, want)
-        gs = G.bf(oracle.matmul(x, wg)).astype(np.float64)
-        u = np.abs(G.bf(oracle.matmul(x, wu)).astype(np.float64))
-        ill = (np.abs(gs) < 1e-2 * _abs_scale(oracle, x, wg)) | (u < 1e-2 * _abs_scale(oracle, x, wu)) | (gs < -4)
-        assert (d == 0).mean() > 0.97 and not ((d > 2) & ~ill).any()
-    else:
-        N = 264
-        w = rand_bf16(oracle, (N, K), 0.05, seed=9)
-        y = G.zeros((M, N), np.float32)
-        _linear(qlib, G.dev(x), [(G.dev(w), N)], [], M, K, N, y, _lib.QIE_EPI_F32, flags=fl)
-        want = oracle.bf16_to_f32(x).astype(np.float64) @ oracle.bf16_to_f32(w).astype(np.float64).T
-        assert np.abs(G.host(y) - want).max() <= 1e-5 * _abs_scale(oracle, x, w).max() + 1e-6
+    _big_gemm_case(oracle, qlib, M, K, epi, fl)
+
+
+@pytest.mark.parametrize("epi", ["store3", "residual", "swiglu", "f32"])
+def test_linear_gemm8_splitk(oracle, qlib, epi):
+    """The bf16 split-K hand-off of the phase-interleaved 256x256 GEMM, through qie_linear's own
+    launch choice (no flag): M = 257, K = 8,192 and 264 output columns are the smallest shape
+    that splits by default (2 x 2 tiles, or 2 x 3 for SwiGLU's 528 weight rows, of 128 k-tiles:
+    2 parts of 64 per tile; tests/test_gemm_plan_cpu.py pins the choice), ragged in M and N.
+    Each epilogue against the oracle with test_linear_big_gemm's bounds, and two launches into
+    fresh outputs bit-equal: the tickets reset, and the sum does not depend on which part
+    arrives last."""
+    _big_gemm_case(oracle, qlib, 257, 8192, epi, 0, n3=(200, 40, 24), n_res=264, n_sw=264, n_f32=264, runs=2)
 
 
 @pytest.mark.parametrize("M", [1, 3, 8])

@@ -71,8 +71,10 @@ ROWS = [
     # 4 bf16 rows: the skinny kernel, 224 column tiles (< 256 CUs: the grid is the tile count)
     (("m4_o", 4, 3584, 3584, "RESIDUAL", 0, 0, "3584,0,0", 1, ""),
      "skinny_mfma_kernel<RESIDUAL,0,0,4,0> t16=0 grid=224 threads=256 lds=3072"),
-    # 12 rows, K no multiple of 64: the tiled GEMM
-    (("m12_k3592", 12, 3592, 3584, "STORE", 0, 0, "3584,0,0", 1, ""), "gemm"),
+    # 12 rows, K no multiple of 64: the tiled GEMM (gemm_plan.hpp; tests/test_gemm_plan_cpu.py) —
+    # K no multiple of 32 either, so its generic 128x128 kernel, one row tile x 28 column tiles
+    (("m12_k3592", 12, 3592, 3584, "STORE", 0, 0, "3584,0,0", 1, ""),
+     "gemm_kernel<STORE,0> n_mt=1 tiles=28 slabs=0 tickets=0 grid=1x28 threads=256 lds=65536"),
     # a fused norm at K > 10,240: no x-first variant holds it (XCH 5 ends at 10,240, XCH 10 has
     # no norm), so the generic prologue — on the one-block-per-CU grid (9 row tasks per CU)
     (("k10248_norm", 1, 10248, 4608, "STORE", 1, 0, "4608,0,0", 1, ""),
