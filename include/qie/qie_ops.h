@@ -105,6 +105,11 @@ typedef struct qie_linear_args {
 } qie_linear_args;
 
 int qie_linear(const qie_linear_args* args, void* stream);
+/* Test probe: the launch qie_linear would make of *args on the current device (its CU count,
+ * this library's knobs), as one line of text: the kernel instantiation, then its grid
+ * ("grid=?" where that depends on an occupancy query).  Launches nothing.  out holds cap
+ * bytes; -22 if the line does not fit. */
+int qie_debug_linear_plan(const qie_linear_args* args, char* out, int cap);
 
 /* --------------------------------------------- q/k post-projection + KV append
  * Replaces launch_qknorm (helpers.cuh:140-142, qk_norm.cu:43-79), launch_rope /

@@ -108,6 +108,7 @@ SIGNATURES = [
     ("qie_embedding", C.c_int, [_P, _P, _P, _I64, _I64, _P]),
     ("qie_rmsnorm", C.c_int, [_P, _P, _P, _I64, _I64, _F, _I32, _P]),
     ("qie_linear", C.c_int, [C.POINTER(LinearArgsC), _P]),
+    ("qie_debug_linear_plan", C.c_int, [C.POINTER(LinearArgsC), C.c_char_p, C.c_int]),
     ("qie_qkv_post", C.c_int, [_P, _I64, _P, _I32, _P, _P, _P, _P, _I32, C.POINTER(KvCacheC),
                                _I32, _F, _I32, _P, _P]),
     ("qie_attention_workspace_bytes", C.c_int64, [_I64, _I32, _I32, _I32]),

@@ -1959,4 +1959,6 @@ int qie_batch_debug_step(qie_batch* b, const qie_sampling* smp, int32_t* next_id
 
 int qie_linear(const qie_linear_args* a, void* stream) { return linear(a, LinearExtras{}, (hipStream_t)stream); }
 
+int qie_debug_linear_plan(const qie_linear_args* a, char* out, int cap) { return linear_plan_text(a, out, cap); }
+
 }  // extern "C"

@@ -808,7 +808,7 @@ static int g8_workspace(hipStream_t st, int slabs, int tiles, G8Split* out) {
     return 0;
 }
 
-static GemmKnobs dev_gemm_knobs() {
+GemmKnobs dev_gemm_knobs() {   // (qie_common.hpp: also k_gemv.hip's linear_plan_text)
     GemmKnobs k;
     k.gemm_big = dev_env("QIE_GEMM_BIG", k.gemm_big);
     k.gemm8 = dev_env("QIE_GEMM8", k.gemm8);

@@ -17,9 +17,11 @@
 #include "qie_common.hpp"
 #include "launch_util.hpp"
 #include "linear_plan.hpp"
+#include "plan_format.hpp"
 #include "../../include/qie/qie_ops.h"
 
 #include <cstdlib>
+#include <cstring>
 
 namespace qie {
 
@@ -1290,6 +1292,18 @@ int dec8_linear(const qie_linear_args* a, const LinearPlan& pl, hipStream_t st, 
 bool dec8_applies(const qie_linear_args* a) {
     int ku, ks, parts;
     return dec8_plan(*a, dev_knobs(), &ku, &ks, &parts);
+}
+
+// qie_debug_linear_plan: the launch qie_linear would make of *a on the current device (its CU
+// count, this library's knobs), in plan_format.hpp's wording.  No launch and no occupancy query:
+// a grid that depends on one prints as "grid=?".  (A split-K workspace that cannot be had
+// during a graph capture makes gemv() / gemm() plan again without one; this is the first plan.)
+int linear_plan_text(const qie_linear_args* a, char* out, int cap) {
+    QIE_REQUIRE(a && out && cap > 0, "qie_debug_linear_plan: bad arguments");
+    const std::string s = format_linear_plan(*a, dev_knobs(), dev_gemm_knobs(), device_cu_count(), 0);
+    QIE_REQUIRE((size_t)cap > s.size(), "qie_debug_linear_plan: %zu bytes needed", s.size() + 1);
+    memcpy(out, s.c_str(), s.size() + 1);
+    return 0;
 }
 
 // M <= 16: plan, fill the kernel's argument block, launch the plan's instantiation

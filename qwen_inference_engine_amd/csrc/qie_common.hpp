@@ -320,6 +320,11 @@ __device__ __forceinline__ uint64_t* peer_tag_slot(char* tb, unsigned e, int src
 // what the public argument block cannot hold (linear_plan.hpp LinearExtras)
 struct LinearExtras;
 int linear(const qie_linear_args* a, const LinearExtras& ex, hipStream_t st);
+// qie_debug_linear_plan (k_gemv.hip): the plan of that launch as text, with both halves' dev
+// knobs (k_gemm.hip dev_gemm_knobs; gemm_plan.hpp GemmKnobs)
+struct GemmKnobs;
+GemmKnobs dev_gemm_knobs();
+int linear_plan_text(const qie_linear_args* a, char* out, int cap);
 
 // Device properties cached per process (CU count for persistent grids).
 int device_cu_count();

@@ -1,8 +1,9 @@
 // plan_dump — prints the launch plan of linear layers without a GPU: M <= 16 rows by
 // plan_linear (linear_plan.hpp); more rows, rows that plan hands to the GEMM, and fp8 activations
-// (QIE_LINEAR_ACT_FP8) at any M by plan_gemm (gemm_plan.hpp).  Plain host program
-// (`make plan_dump`); tests/test_linear_plan_cpu.py and tests/test_gemm_plan_cpu.py compare its
-// output with tables derived by hand.
+// (QIE_LINEAR_ACT_FP8) at any M by plan_gemm (gemm_plan.hpp), in plan_format.hpp's wording.
+// Plain host program (`make plan_dump`); tests/test_linear_plan_cpu.py and
+// tests/test_gemm_plan_cpu.py compare its output with tables derived by hand,
+// tests/test_linear_variants_cpu.py with the instantiations tests/linear_cases.py declares.
 //
 // stdin, one shape per line:
 //   name M K N epilogue norm flags seg0,seg1,seg2 resident_blocks [knob=value ...]
@@ -16,29 +17,9 @@
 #include <sstream>
 #include <string>
 
-#include "../gemm_plan.hpp"
-#include "../linear_plan.hpp"
+#include "../plan_format.hpp"
 
 using namespace qie;
-
-static const char* kEpi[] = {"STORE", "RESIDUAL", "SWIGLU", "F32"};
-
-static void print_gemm_plan(const GemmPlan& g, int epi) {
-    const char* e = kEpi[epi];
-    switch (g.family) {
-        case GemmFamily::Generic: printf(" gemm_kernel<%s,0>", e); break;
-        case GemmFamily::GenericFp8: printf(" gemm_kernel<%s,1>", e); break;
-        case GemmFamily::Big256: printf(" gemm_big_kernel<%s,256>", e); break;
-        case GemmFamily::Big128: printf(" gemm_big_kernel<%s,128>", e); break;
-        case GemmFamily::Gemm8: printf(" gemm8_kernel<%s> splitk=%d", e, g.splitk); break;
-        case GemmFamily::Gemm8StreamK: printf(" gemm8sk_kernel<%s> dp_rounds=%d chunk=%d", e, g.dp_rounds, g.chunk); break;
-        case GemmFamily::Mx: printf(" gemm8mx_kernel<%s,0> splitk=%d", e, g.splitk); break;
-        case GemmFamily::MxT16: printf(" gemm8mx_kernel<%s,1> splitk=%d", e, g.splitk); break;
-    }
-    printf(" n_mt=%d tiles=%d slabs=%d tickets=%d grid=%u", g.n_mt, g.tiles, g.slabs, g.tickets, g.grid_x);
-    if (g.grid_y != 1) printf("x%u", g.grid_y);
-    printf(" threads=%d lds=%zu\n", g.threads, g.lds_bytes);
-}
 
 int main() {
     const int cus = 256;
@@ -59,7 +40,7 @@ int main() {
         a.M = M, a.K = K, a.N = N, a.ldx = K, a.ldy = N, a.flags = flags;
         a.x = a.y = (void*)dummy;
         for (int e = 0; e < 4; e++)
-            if (epi == kEpi[e]) a.epilogue = e;
+            if (epi == epi_name(e)) a.epilogue = e;
         long long s0 = 0, s1 = 0, s2 = 0;
         sscanf(segs.c_str(), "%lld,%lld,%lld", &s0, &s1, &s2);
         a.seg_rows[0] = s0, a.seg_rows[1] = s1, a.seg_rows[2] = s2;
@@ -85,34 +66,7 @@ int main() {
                 return 2;
             }
         }
-        printf("%s:", name.c_str());
-        // qie_linear's routing: fp8 activations and M > 16 go straight to the GEMM
-        if ((a.flags & QIE_LINEAR_ACT_FP8) || a.M > 16) {
-            print_gemm_plan(plan_gemm(a, gk, cus, allow_split), a.epilogue);
-            continue;
-        }
-        const LinearPlan pl = plan_linear(a, LinearExtras{}, cus, k);
-        if (pl.error != PlanError::None) {
-            printf(" error %d\n", (int)pl.error);
-            continue;
-        }
-        switch (pl.family) {
-            case LinearFamily::Dec8:
-                printf(" dec8 KU=%d KS=%d parts=%d\n", pl.dec8_ku, pl.dec8_ks, pl.dec8_parts);
-                continue;
-            case LinearFamily::Gemm: print_gemm_plan(plan_gemm(a, gk, cus, allow_split), a.epilogue); continue;
-            case LinearFamily::Skinny:
-                printf(" skinny_mfma_kernel<%s,%d,%d,4,%d> t16=%d", kEpi[pl.epi], pl.wt, pl.xlds, pl.uo, (int)pl.t16);
-                break;
-            case LinearFamily::Gemv:
-                printf(" gemv_kernel<%d,%d,%s,%d,%d,%d>", pl.mt, pl.rpw, kEpi[pl.epi],
-                       pl.uo ? pl.uo : (pl.rpw >= 4 ? 4 : 8), pl.xch, pl.wt);
-                if (pl.block_waves) printf(" LB=%d", pl.rpw == 1 ? 1024 : kGemvBalancedThreads);
-                printf(" xlds=%d tasks=%lld bpc=%d", pl.xlds, (long long)pl.n_tasks, pl.bpc);
-                break;
-        }
-        const LaunchGeom g = launch_geometry(pl, cus, nb);
-        printf(" grid=%u threads=%d lds=%zu\n", g.grid, g.threads, g.lds_bytes);
+        printf("%s: %s\n", name.c_str(), format_linear_plan(a, k, gk, cus, nb, allow_split).c_str());
     }
     return 0;
 }

@@ -48,9 +48,10 @@ def test_rmsnorm(oracle, qlib, rows, H, num):
 
 
 # --------------------------------------------------------------------------- linear
-def _linear(qlib, x, segs, biases, M, K, N, y, epi, norm_w=None, eps=1e-4, num=0, keys=None, ldy=None, flags=0):
+def _linear_args(x, segs, biases, M, K, N, y, epi, norm_w=None, eps=1e-4, num=0, keys=None, ldy=None, flags=0,
+                 ldx=None, key_col0=0):
     a = LinearArgsC()
-    a.x, a.ldx = G.p(x), K
+    a.x, a.ldx = G.p(x), ldx or K
     for i, s in enumerate(segs):
         a.w[i] = G.p(s[0])
         a.seg_rows[i] = s[1]
@@ -62,12 +63,22 @@ def _linear(qlib, x, segs, biases, M, K, N, y, epi, norm_w=None, eps=1e-4, num=0
     a.norm_w = G.p(norm_w) if norm_w is not None else None
     a.norm_eps, a.numerics = eps, num
     a.argmax_keys = G.p(keys) if keys is not None else None
+    a.key_col0 = key_col0
     a.flags = flags
+    return a
+
+
+def _linear(qlib, x, segs, biases, M, K, N, y, epi, **kw):
+    """One qie_linear launch; **kw: norm_w, eps, num, keys, ldy, flags, ldx, key_col0 (_linear_args)."""
+    a = _linear_args(x, segs, biases, M, K, N, y, epi, **kw)
     G.check(qlib.qie_linear(C.byref(a), None), "qie_linear")
 
 
 def _abs_scale(oracle, x, w):
-    return np.abs(oracle.bf16_to_f32(x).astype(np.float64)) @ np.abs(oracle.bf16_to_f32(w).astype(np.float64)).T
+    """sum_k |x[m, k] * w[n, k]| in float64 (weight rows in slabs: a vocabulary has 65 k of them)."""
+    ax = np.abs(oracle.bf16_to_f32(x).astype(np.float64))
+    return np.concatenate([ax @ np.abs(oracle.bf16_to_f32(w[r:r + 8192]).astype(np.float64)).T
+                           for r in range(0, len(w), 8192)], axis=-1)
 
 
 @pytest.mark.parametrize("M", [1, 2, 3, 5, 8, 9, 64, 130, 300])
@@ -132,6 +143,32 @@ def test_linear_swiglu(oracle, qlib, M, K, I):
     assert not ((d > 2) & ~ill).any(), f"well-conditioned element off by {d[~ill].max()} ulps"
 
 
+# The per-epilogue bounds, shared by the linear tests (this file, test_gpu_linear_variants.py).
+def assert_residual_close(got, want, acc, scale):
+    """test_linear_residual's bound: y = bf16(res + bf16(acc)), the inner bf16(acc) 1 ulp of |acc|
+    (fp32 summation order), one more rounding at |y|, plus 1e-5 of sum|a*w|.  acc: the oracle's
+    bf16 product (bits); scale: sum|a*w|."""
+    acc = G.bf(acc).astype(np.float64)
+    tol = 2.0 ** -7 * (np.abs(acc) + np.abs(G.bf(want))) + 1e-5 * scale
+    assert (np.abs(G.bf(got).astype(np.float64) - G.bf(want)) <= tol).all()
+
+
+def assert_swiglu_close(got, want, gate, up, scale_g, scale_u):
+    """test_linear_swiglu's rule: > 97 % of the elements exact, and an element off by more than
+    2 ulps is ill-conditioned (a gate or up sum below 1 % of sum|x*w|, or a gate < -4).  gate,
+    up: the oracle's bf16 products (bits)."""
+    d = G.ulp_diff(got, want)
+    gs = G.bf(gate).astype(np.float64)
+    u = np.abs(G.bf(up).astype(np.float64))
+    ill = (np.abs(gs) < 1e-2 * scale_g) | (u < 1e-2 * scale_u) | (gs < -4)
+    assert (d == 0).mean() > 0.97 and not ((d > 2) & ~ill).any()
+
+
+def assert_f32_close(got, want, scale):
+    """The fp32 partial sums against a float64 product: 1e-5 of the largest sum|a*w|."""
+    assert np.abs(got - want).max() <= 1e-5 * scale.max() + 1e-6
+
+
 def _big_gemm_case(oracle, qlib, M, K, epi, fl, n3=(200, 72, 40), n_res=320, n_sw=200, n_f32=264, runs=1):
     """One prefill-GEMM launch per run (flags fl) against the oracle, per epilogue: "store3" three
     segments with bias (assert_sum_close), "residual", "swiglu", "f32" (1e-5 of sum|a*w|).  Every
@@ -168,9 +205,7 @@ def _big_gemm_case(oracle, qlib, M, K, epi, fl, n3=(200, 72, 40), n_res=320, n_s
         dw = G.dev(w)
         got = launches(lambda: G.dev(res),
                        lambda y: _linear(qlib, dx, [(dw, N)], [], M, K, N, y, _lib.QIE_EPI_RESIDUAL, flags=fl))
-        acc = G.bf(oracle.matmul(x, w)).astype(np.float64)
-        tol = 2.0 ** -7 * (np.abs(acc) + np.abs(G.bf(want))) + 1e-5 * _abs_scale(oracle, x, w)
-        assert (np.abs(G.bf(got).astype(np.float64) - G.bf(want)) <= tol).all()
+        assert_residual_close(got, want, oracle.matmul(x, w), _abs_scale(oracle, x, w))
     elif epi == "swiglu":
         I = n_sw
         wg = rand_bf16(oracle, (I, K), 0.08, seed=7)
@@ -179,11 +214,8 @@ def _big_gemm_case(oracle, qlib, M, K, epi, fl, n3=(200, 72, 40), n_res=320, n_s
         segs = [(G.dev(wg), I), (G.dev(wu), I)]
         got = launches(lambda: G.zeros_bf16(M, I),
                        lambda y: _linear(qlib, dx, segs, [], M, K, I, y, _lib.QIE_EPI_SWIGLU, flags=fl))
-        d = G.ulp_diff(got, want)
-        gs = G.bf(oracle.matmul(x, wg)).astype(np.float64)
-        u = np.abs(G.bf(oracle.matmul(x, wu)).astype(np.float64))
-        ill = (np.abs(gs) < 1e-2 * _abs_scale(oracle, x, wg)) | (u < 1e-2 * _abs_scale(oracle, x, wu)) | (gs < -4)
-        assert (d == 0).mean() > 0.97 and not ((d > 2) & ~ill).any()
+        assert_swiglu_close(got, want, oracle.matmul(x, wg), oracle.matmul(x, wu), _abs_scale(oracle, x, wg),
+                            _abs_scale(oracle, x, wu))
     else:
         N = n_f32
         w = rand_bf16(oracle, (N, K), 0.05, seed=9)
@@ -191,7 +223,7 @@ def _big_gemm_case(oracle, qlib, M, K, epi, fl, n3=(200, 72, 40), n_res=320, n_s
         got = launches(lambda: G.zeros((M, N), np.float32),
                        lambda y: _linear(qlib, dx, [(dw, N)], [], M, K, N, y, _lib.QIE_EPI_F32, flags=fl))
         want = oracle.bf16_to_f32(x).astype(np.float64) @ oracle.bf16_to_f32(w).astype(np.float64).T
-        assert np.abs(got - want).max() <= 1e-5 * _abs_scale(oracle, x, w).max() + 1e-6
+        assert_f32_close(got, want, _abs_scale(oracle, x, w))
 
 
 @pytest.mark.parametrize("M,K", [(256, 896), (300, 96), (520, 32), (257, 3584)])
