@@ -192,6 +192,31 @@ int qie_prefill_batch(qie_batch* b, int32_t seq0, int32_t n_seqs, const int32_t*
  * numerics are defined for a prefill from position 0 only. */
 int qie_prefill_append(qie_batch* b, int32_t seq, const int32_t* ids, int32_t n, int32_t pos0,
                        const qie_sampling* s, int32_t* next_id);
+/* Speculative decoding: verify up to QIE_VERIFY_MAX_ROWS - 1 drafted tokens in one weight pass
+ * (DESIGN.md §16).  `seq` is a live slot of any batch (contiguous or paged, any B) at position
+ * p with a pending current token c; draft holds 0 <= n_draft <= 15 ids d1 .. dn (host).  One
+ * pass runs the M = n_draft + 1 rows c, d1 .. dn at positions p .. p+n through the decode-form
+ * layer, writes their K/V rows and picks one token t_i per row: greedy from the fused arg-max
+ * keys (the reference tie rule), sampled by qie_sample with row i's counter = the sequence's
+ * step counter + i — the id a plain qie_decode_step would draw from the same logits.  The
+ * accepted length a is the largest a with d_j == t_(j-1) for all 1 <= j <= a; out_ids (host,
+ * n_draft + 1 slots) receives t_0 .. t_a and *n_out = a + 1 >= 1.  The sequence is left exactly
+ * as after a + 1 decode steps: position p + a + 1, current token t_a, history [p+1 .. p+a+1] =
+ * t_0 .. t_a, step counter + (a + 1), qie_batch_logits row `seq` = the logits that produced
+ * t_a.  K/V rows of rejected drafts lie at or past the new position and are overwritten before
+ * anything reads them (the qie_batch_set_position rule); other slots are untouched.  The call
+ * synchronises.  With use_graph the step is captured once per (slot, rows, sampling) and
+ * replayed.  Collective under tensor parallelism, like qie_prefill.
+ * All-or-nothing, nothing launched: -22 for bad arguments, an idle or released slot, a draft
+ * id out of range, p + n_draft + 1 >= max_ctx, an engine created with prefill_fp8, a batch in
+ * decode mode 1; -28 when the page pool cannot hold positions up to p + n_draft (pages taken
+ * for rows that end up rejected stay with the slot until it is released). */
+#define QIE_VERIFY_MAX_ROWS 16   /* the M <= 16 linear planner's range */
+int qie_verify(qie_batch* b, int32_t seq, const int32_t* draft, int32_t n_draft,
+               const qie_sampling* s, int32_t* out_ids, int32_t* n_out);
+/* Logits of every row of the last qie_verify: host bf16 [n_draft + 1][V].  Works wherever
+ * qie_batch_logits does (collective under tensor parallelism). */
+int qie_verify_logits(qie_batch* b, void* host_out);
 /* One decode step for all B sequences (hipGraph replay when enabled);
  * next_ids: host [B] or NULL (then nothing is synchronised). */
 int qie_decode_step(qie_batch* b, const qie_sampling* s, int32_t* next_ids);

@@ -27,6 +27,7 @@ QIE_LINEAR_STREAMK = 8
 QIE_LINEAR_FP8_T16 = 16
 QIE_LINEAR_ACT_FP8 = 32
 QIE_ATTN_PREROPED = 0x100   # qie_attention_decode numerics flag: q / new k arrive rotated
+QIE_VERIFY_MAX_ROWS = 16    # qie_verify: the current token + at most 15 drafts
 QIE_COMM_ID_BYTES = 128
 QIE_COMM_PEER_HANDLE_BYTES = 128
 
@@ -185,6 +186,8 @@ SIGNATURES = [
     ("qie_prefill", C.c_int, [_P, _I32, _PI32, _I32, C.POINTER(SamplingC), _PI32]),
     ("qie_prefill_batch", C.c_int, [_P, _I32, _I32, _PI32, _I32, C.POINTER(SamplingC), _PI32]),
     ("qie_prefill_append", C.c_int, [_P, _I32, _PI32, _I32, _I32, C.POINTER(SamplingC), _PI32]),
+    ("qie_verify", C.c_int, [_P, _I32, _PI32, _I32, C.POINTER(SamplingC), _PI32, _PI32]),
+    ("qie_verify_logits", C.c_int, [_P, _P]),
     ("qie_decode_step", C.c_int, [_P, C.POINTER(SamplingC), _PI32]),
     ("qie_decode", C.c_int, [_P, _I32, C.POINTER(SamplingC), _PI32]),
     ("qie_batch_logits", C.c_int, [_P, _P]),

@@ -19,10 +19,12 @@
 #include "../../include/qie/qie_engine.h"
 #include "qie_index.hpp"
 #include "qie_comm.hpp"
+#include "verify.hpp"
 
 #include <chrono>
 #include <cstring>
 #include <fstream>
+#include <type_traits>
 #include <vector>
 
 namespace qie {
@@ -163,6 +165,27 @@ struct qie_batch {
     qie_layer_weights* d_layers = nullptr;
     void* d_attp = nullptr;      // the attention role's parameters per layer (persist_attn_table)
     unsigned long long* pk_ts = nullptr;   // qie_batch_pk_trace: phase timestamps [cu][layer][slots]
+    // speculative verify (qie_verify): the step's own row buffers, made once at
+    // kVerifyMaxRows rows by the first call (one allocation; a captured step holds pointers
+    // into it, never into the growable prefill scratch), and one captured step per
+    // (slot, rows, sampling)
+    struct VerifyBufs {
+        void* mem = nullptr;
+        uint16_t *x = nullptr, *xn = nullptr, *qkv = nullptr, *q = nullptr, *att = nullptr, *h = nullptr;
+        uint16_t *logits = nullptr, *logits_full = nullptr, *gather_tmp = nullptr;
+        float* part = nullptr;
+        void *attn_ws = nullptr, *samp_ws = nullptr;
+        unsigned long long* keys = nullptr;
+        int32_t *ids = nullptr, *pos = nullptr, *step = nullptr, *draft = nullptr, *res = nullptr;
+    } v;
+    struct VerifyGraph {
+        int seq, M;
+        bool greedy;
+        qie_sampling smp;
+        hipGraphExec_t exec;
+    };
+    std::vector<VerifyGraph> v_graphs;
+    int v_rows = 0;   // rows of the last qie_verify (what qie_verify_logits returns)
 };
 
 namespace qie {
@@ -171,27 +194,7 @@ namespace qie {
 // Step finalisation: chosen id -> token history, position + 1, sample step + 1,
 // next step's input row x_res[m] = E[id] (embedding_matrix_func, decode branch
 // qwen_main.cu:259-268, without the host round trip).
-// The RoPE table row of a slot's current position, kept beside the position (tagged with it)
-// so that the decode attention's prologue loads need not wait for the position
-// (DecodeAttnParams::rc).  Every kernel that sets a position also writes the row.
-struct RopeCurArgs {
-    float* rc;
-    const float* cs;
-    const float* sn;
-    int hd, rows;
-};
-__device__ __forceinline__ void write_rope_cur(const RopeCurArgs& r, int m, int p) {
-    if (!r.rc) return;
-    float* o = r.rc + (int64_t)m * rope_cur_stride(r.hd);
-    const bool ok = p >= 0 && p < r.rows;
-    const int h2 = r.hd / 2;
-    for (int t = threadIdx.x; t < h2; t += blockDim.x) {
-        o[8 + t] = ok ? r.cs[(int64_t)p * h2 + t] : 0.f;
-        o[8 + h2 + t] = ok ? r.sn[(int64_t)p * h2 + t] : 0.f;
-    }
-    if (threadIdx.x == 0) o[0] = __int_as_float(ok ? p : -1);
-}
-
+// (the slot's current-position RoPE row: RopeCurArgs / write_rope_cur, qie_common.hpp)
 __global__ __launch_bounds__(256) void finalize_kernel(int m0, unsigned long long* keys, const int32_t* ids_in,
                                                        int32_t* ids_out, int32_t* pos, int32_t* step,
                                                        int32_t* hist, int hist_stride, const uint4* E,
@@ -548,12 +551,14 @@ static int row_parallel(qie_batch* b, qie_linear_args& a, uint16_t* x, float* pa
 // skinny kernel's fused norm prologue recomputed every row's norm in every workgroup and
 // cost 13-16 us per launch at B = 8 (tools/ubench_b8.py, QIE_SKINNY_DBG); M = 1 keeps the
 // GEMV's fused x-first prologue.  QIE_PRENORM=0 restores the fused form (A/B).
-static int prenorm(qie_batch* b, qie_linear_args& a, int64_t M) {
+// xn: the [M][K] rows the norm lands in (default: the batch's decode rows, [B][H])
+static int prenorm(qie_batch* b, qie_linear_args& a, int64_t M, uint16_t* xn = nullptr) {
     static const int on = dev_env("QIE_PRENORM", 1);
     if (!on || M < 2 || M > 16 || !a.norm_w) return 0;
     if (dec8_applies(&a) && dev_env("QIE_DEC8_PRENORM", 0) == 0) return 0;   // the fp8 batched-decode kernel fuses the norm
-    QIE_TRY(qie_rmsnorm(a.x, a.norm_w, b->xn, M, a.K, a.norm_eps, a.numerics, b->e->stream));
-    a.x = b->xn;
+    if (!xn) xn = b->xn;
+    QIE_TRY(qie_rmsnorm(a.x, a.norm_w, xn, M, a.K, a.norm_eps, a.numerics, b->e->stream));
+    a.x = xn;
     a.ldx = a.K;
     a.norm_w = nullptr;
     return 0;
@@ -575,61 +580,113 @@ static int dbg_snap(qie_batch* b, int slot) {
     return 0;
 }
 
+// The M rows a decode-form layer works on: the decode step's are the batch's B slots, a
+// verify step's (qie_verify) its own M <= 16 rows of one sequence.
+struct LayerRows {
+    int64_t M;
+    uint16_t *x, *xn, *qkv, *att, *h;   // residual [M][H], normed [M][H], [M][QKVD], [M][QD], [M][I]
+    float* part;                        // [M][H] fp32 partials (exchange path only)
+};
+static LayerRows decode_rows(const qie_batch* b) {
+    return LayerRows{b->B, b->x_res, b->xn, b->qkv, b->att, b->h, b->part};
+}
+
+// The four projections of the decode-form layer: [norm + QKV (+ bias)], [O + residual],
+// [norm + gate/up + SwiGLU], [down + residual]
+static int proj_qkv(qie_batch* b, int l, const LayerRows& r, const LinearExtras& ex) {
+    qie_engine* e = b->e;
+    const qie_model_spec& s = e->spec;
+    const qie_layer_weights& L = e->layers[l];
+    const int64_t H = s.hidden, QD = (int64_t)e->sh.nq * s.head_dim, KD = (int64_t)e->sh.nkv * s.head_dim;
+    qie_linear_args a = lin_proj(e);
+    a.x = r.x; a.ldx = H;
+    a.w[0] = L.wq; a.w[1] = L.wk; a.w[2] = L.wv;
+    a.bias[0] = L.bq; a.bias[1] = L.bk; a.bias[2] = L.bv;
+    a.seg_rows[0] = QD; a.seg_rows[1] = KD; a.seg_rows[2] = KD;
+    a.M = r.M; a.K = H; a.N = QD + 2 * KD;
+    a.y = r.qkv; a.ldy = QD + 2 * KD;
+    a.epilogue = QIE_EPI_STORE;
+    a.norm_w = L.attn_norm; a.norm_eps = s.rms_eps; a.numerics = s.numerics;
+    QIE_TRY(prenorm(b, a, r.M, r.xn));
+    return linear(&a, ex, e->stream);
+}
+static int proj_o(qie_batch* b, int l, const LayerRows& r) {
+    qie_engine* e = b->e;
+    const int64_t H = e->spec.hidden, QD = (int64_t)e->sh.nq * e->spec.head_dim;
+    qie_linear_args a = lin_proj(e);
+    a.x = r.att; a.ldx = QD;
+    a.w[0] = e->layers[l].wo; a.seg_rows[0] = H;
+    a.M = r.M; a.K = QD; a.N = H;
+    a.ldy = H;
+    return row_parallel(b, a, r.x, r.part, r.M);
+}
+static int proj_gate_up(qie_batch* b, int l, const LayerRows& r) {
+    qie_engine* e = b->e;
+    const qie_model_spec& s = e->spec;
+    const qie_layer_weights& L = e->layers[l];
+    const int64_t H = s.hidden, I = e->sh.ffn;
+    qie_linear_args a = lin_proj(e);
+    a.x = r.x; a.ldx = H;
+    a.w[0] = L.w_gate; a.w[1] = L.w_up; a.seg_rows[0] = I; a.seg_rows[1] = I;
+    a.M = r.M; a.K = H; a.N = I;
+    a.y = r.h; a.ldy = I;
+    a.epilogue = QIE_EPI_SWIGLU;
+    a.norm_w = L.ffn_norm; a.norm_eps = s.rms_eps; a.numerics = s.numerics;
+    QIE_TRY(prenorm(b, a, r.M, r.xn));
+    return linear(&a, LinearExtras{}, e->stream);
+}
+static int proj_down(qie_batch* b, int l, const LayerRows& r) {
+    qie_engine* e = b->e;
+    const int64_t H = e->spec.hidden, I = e->sh.ffn;
+    qie_linear_args a = lin_proj(e);
+    a.x = r.h; a.ldx = I;
+    a.w[0] = e->layers[l].w_down; a.seg_rows[0] = H;
+    a.M = r.M; a.K = I; a.N = H;
+    a.ldy = H;
+    return row_parallel(b, a, r.x, r.part, r.M);
+}
+
 static int enqueue_layer_decode(qie_batch* b, int l) {
     qie_engine* e = b->e;
     const qie_model_spec& s = e->spec;
     const qie_layer_weights& L = e->layers[l];
-    hipStream_t st = e->stream;
-    const int64_t H = s.hidden, hd = s.head_dim, QD = (int64_t)e->sh.nq * hd, KD = (int64_t)e->sh.nkv * hd;
-    const int64_t QKVD = QD + 2 * KD, I = e->sh.ffn, B = b->B;
+    const int64_t hd = s.head_dim, QD = (int64_t)e->sh.nq * hd, KD = (int64_t)e->sh.nkv * hd;
     const qie_kv_cache cache = batch_cache(b, 0);
+    const LayerRows r = decode_rows(b);
 
-    qie_linear_args a = lin_proj(e);
-    a.x = b->x_res; a.ldx = H;
-    a.w[0] = L.wq; a.w[1] = L.wk; a.w[2] = L.wv;
-    a.bias[0] = L.bq; a.bias[1] = L.bk; a.bias[2] = L.bv;
-    a.seg_rows[0] = QD; a.seg_rows[1] = KD; a.seg_rows[2] = KD;
-    a.M = B; a.K = H; a.N = QKVD;
-    a.y = b->qkv; a.ldy = QKVD;
-    a.epilogue = QIE_EPI_STORE;
-    a.norm_w = L.attn_norm; a.norm_eps = s.rms_eps; a.numerics = s.numerics;
-    QIE_TRY(prenorm(b, a, B));
     const bool rope_in_proj = rope_in_projection(b);
     LinearExtras ex;
     if (rope_in_proj) ex.rope = RopeArgs{b->d_pos, e->rope_cos, e->rope_sin, (int)hd, QD + KD};
-    QIE_TRY(linear(&a, ex, st));
+    QIE_TRY(proj_qkv(b, l, r, ex));
 
     set_decode_rope_cur(b->d_rope_cur);
-    const int arc = qie_attention_decode(b->qkv, B, b->d_pos, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, e->sh.nq,
+    const int arc = qie_attention_decode(b->qkv, r.M, b->d_pos, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, e->sh.nq,
                                          &cache, l, s.rms_eps, s.numerics | (rope_in_proj ? QIE_ATTN_PREROPED : 0),
-                                         b->att, b->dec_ws, st);
+                                         b->att, b->dec_ws, e->stream);
     set_decode_rope_cur(nullptr);
     QIE_TRY(arc);
-    a = lin_proj(e);
-    a.x = b->att; a.ldx = QD;
-    a.w[0] = L.wo; a.seg_rows[0] = H;
-    a.M = B; a.K = QD; a.N = H;
-    a.ldy = H;
-    QIE_TRY(row_parallel(b, a, b->x_res, b->part, B));
+    QIE_TRY(proj_o(b, l, r));
     QIE_TRY(dbg_snap(b, 2 * l + 1));
-
-    a = lin_proj(e);
-    a.x = b->x_res; a.ldx = H;
-    a.w[0] = L.w_gate; a.w[1] = L.w_up; a.seg_rows[0] = I; a.seg_rows[1] = I;
-    a.M = B; a.K = H; a.N = I;
-    a.y = b->h; a.ldy = I;
-    a.epilogue = QIE_EPI_SWIGLU;
-    a.norm_w = L.ffn_norm; a.norm_eps = s.rms_eps; a.numerics = s.numerics;
-    QIE_TRY(prenorm(b, a, B));
-    QIE_TRY(linear(&a, LinearExtras{}, st));
-
-    a = lin_proj(e);
-    a.x = b->h; a.ldx = I;
-    a.w[0] = L.w_down; a.seg_rows[0] = H;
-    a.M = B; a.K = I; a.N = H;
-    a.ldy = H;
-    QIE_TRY(row_parallel(b, a, b->x_res, b->part, B));
+    QIE_TRY(proj_gate_up(b, l, r));
+    QIE_TRY(proj_down(b, l, r));
     return dbg_snap(b, 2 * l + 2);
+}
+
+// The same layer for the M rows of ONE sequence at consecutive positions (the verify step):
+// the q/k post-projection writes the rows' K/V at their device positions v.pos, and the
+// split-context MFMA attention lets each row see the cached prefix and the rows before it.
+static int enqueue_layer_verify(qie_batch* b, int l, const LayerRows& r, const qie_kv_cache& cache) {
+    qie_engine* e = b->e;
+    const qie_model_spec& s = e->spec;
+    const qie_layer_weights& L = e->layers[l];
+    hipStream_t st = e->stream;
+    QIE_TRY(proj_qkv(b, l, r, LinearExtras{}));
+    QIE_TRY(qie_qkv_post(r.qkv, r.M, b->v.pos, (int32_t)r.M, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, e->sh.nq,
+                         &cache, l, s.rms_eps, s.numerics, b->v.q, st));
+    QIE_TRY(qie_attention_extend(b->v.q, r.M, b->v.pos, (int32_t)r.M, &cache, l, e->sh.nq, r.att, b->v.attn_ws, st));
+    QIE_TRY(proj_o(b, l, r));
+    QIE_TRY(proj_gate_up(b, l, r));
+    return proj_down(b, l, r);
 }
 
 static bool is_greedy(const qie_sampling* s) { return !s || s->top_k <= 1 || !(s->temperature > 0.f); }
@@ -644,26 +701,50 @@ __global__ void unshard_rows_kernel(const uint16_t* __restrict__ tmp, uint16_t* 
     }
 }
 
-// all-gather of the vocab-parallel logits of rows [m0, m0 + M) into logits_full
-static int gather_logits(qie_batch* b, int m0, int M) {
+// What a head launch reads and writes: the batch's per-slot rows (batch_head) or a verify
+// step's own (verify_head).  logits / keys / ids / step / xn are row 0 of the rows served.
+struct HeadBufs {
+    uint16_t* logits;             // [M][Vl]
+    unsigned long long* keys;     // [M] (zero before the launch)
+    int32_t* ids;                 // [M]
+    const int32_t* step;          // [M] sampling counters
+    void* samp_ws;
+    uint16_t* xn;                 // [M][H] (prenorm)
+    uint16_t *gather_tmp, *logits_full;   // exchange path: [tp][M][Vl], [rows][V]
+    int full_row0;                // first row of logits_full the M rows land in
+};
+static HeadBufs batch_head(const qie_batch* b, int m0) {
+    return HeadBufs{b->logits + (int64_t)m0 * b->e->sh.vocab, b->d_keys + m0, b->d_ids + m0, b->d_step + m0, b->samp_ws,
+                    b->xn, b->gather_tmp, b->logits_full, m0};
+}
+static HeadBufs verify_head(const qie_batch* b) {
+    return HeadBufs{b->v.logits, b->v.keys, b->v.ids, b->v.step, b->v.samp_ws, b->v.xn, b->v.gather_tmp,
+                    b->v.logits_full, 0};
+}
+
+// all-gather of M rows of vocab-parallel logits into hb.logits_full rows [full_row0, + M)
+static int gather_rows(qie_batch* b, const HeadBufs& hb, int M) {
     qie_engine* e = b->e;
     const int64_t Vl = e->sh.vocab;
-    QIE_TRY(e->comm->allgather(b->logits + (int64_t)m0 * Vl, b->gather_tmp, (int64_t)M * Vl * 2, e->stream));
+    QIE_TRY(e->comm->allgather(hb.logits, hb.gather_tmp, (int64_t)M * Vl * 2, e->stream));
     const int64_t n = (int64_t)e->sh.tp * M * Vl;
     hipLaunchKernelGGL(unshard_rows_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)), dim3(256), 0,
-                       e->stream, b->gather_tmp, b->logits_full, e->sh.tp, M, Vl, (int64_t)e->spec.vocab, m0);
+                       e->stream, hb.gather_tmp, hb.logits_full, e->sh.tp, M, Vl, (int64_t)e->spec.vocab, hb.full_row0);
     QIE_LAUNCH_CHECK();
     return 0;
 }
+// ... of the batch's rows [m0, m0 + M)
+static int gather_logits(qie_batch* b, int m0, int M) { return gather_rows(b, batch_head(b, m0), M); }
 
 // the persistent step's words behind its granules: [0] step epoch, [1] error word
 static unsigned* pk_epoch_ptr(const qie_batch* b) {
     return (unsigned*)((unsigned long long*)b->pk_mem + persist_granule_count(b->e->spec));
 }
 
-// lm_head over rows [m0, m0+M) of x (already the residual stream), then the
-// sampler; leaves ids in d_keys (greedy) or d_ids.
-static int enqueue_head(qie_batch* b, const uint16_t* x, int64_t ldx, int m0, int M, const qie_sampling* smp) {
+// lm_head over M rows of x (already the residual stream), then the sampler; leaves the
+// choices in hb.keys (greedy) or hb.ids.
+static int enqueue_head_rows(qie_batch* b, const uint16_t* x, int64_t ldx, int M, const qie_sampling* smp,
+                             const HeadBufs& hb) {
     qie_engine* e = b->e;
     const qie_model_spec& s = e->spec;
     hipStream_t st = e->stream;
@@ -673,25 +754,35 @@ static int enqueue_head(qie_batch* b, const uint16_t* x, int64_t ldx, int m0, in
     a.x = x; a.ldx = ldx;
     a.w[0] = e->w.lm_head; a.seg_rows[0] = Vl;
     a.M = M; a.K = s.hidden; a.N = Vl;
-    a.y = b->logits + (int64_t)m0 * Vl; a.ldy = Vl;
+    a.y = hb.logits; a.ldy = Vl;
     a.epilogue = QIE_EPI_STORE;
     a.norm_w = e->w.final_norm; a.norm_eps = s.rms_eps; a.numerics = s.numerics;
-    QIE_TRY(prenorm(b, a, M));
+    QIE_TRY(prenorm(b, a, M, hb.xn));
     const bool greedy = is_greedy(smp);
     if (greedy) {
-        a.argmax_keys = (uint64_t*)(b->d_keys + m0);
+        a.argmax_keys = (uint64_t*)hb.keys;
         a.key_col0 = e->sh.vocab0;   // keys carry global vocab ids
     }
     QIE_TRY(linear(&a, LinearExtras{}, st));
-    if (greedy && use_comm(e)) QIE_TRY(e->comm->allreduce_max_u64((uint64_t*)(b->d_keys + m0), M, st));
+    if (greedy && use_comm(e)) QIE_TRY(e->comm->allreduce_max_u64((uint64_t*)hb.keys, M, st));
     if (!greedy) {
-        const uint16_t* lg = b->logits + (int64_t)m0 * Vl;
+        const uint16_t* lg = hb.logits;
         if (use_comm(e)) {   // every rank samples the same draw from the gathered row
-            QIE_TRY(gather_logits(b, m0, M));
-            lg = b->logits_full + (int64_t)m0 * s.vocab;
+            QIE_TRY(gather_rows(b, hb, M));
+            lg = hb.logits_full + (int64_t)hb.full_row0 * s.vocab;
         }
-        QIE_TRY(qie_sample(lg, M, s.vocab, s.vocab, smp, b->d_step + m0, b->d_ids + m0, b->samp_ws, st));
+        QIE_TRY(qie_sample(lg, M, s.vocab, s.vocab, smp, hb.step, hb.ids, hb.samp_ws, st));
     }
+    return 0;
+}
+
+// ... over rows [m0, m0+M) of the batch, then the step finalisation of those slots
+static int enqueue_head(qie_batch* b, const uint16_t* x, int64_t ldx, int m0, int M, const qie_sampling* smp) {
+    qie_engine* e = b->e;
+    const qie_model_spec& s = e->spec;
+    hipStream_t st = e->stream;
+    QIE_TRY(enqueue_head_rows(b, x, ldx, M, smp, batch_head(b, m0)));
+    const bool greedy = is_greedy(smp);
     hipLaunchKernelGGL(finalize_kernel, dim3(M), dim3(256), 0, st, m0, greedy ? b->d_keys : nullptr,
                        b->d_ids, b->d_ids, b->d_pos, b->d_step, b->d_hist, b->max_ctx,
                        (const uint4*)e->w.embed, (uint4*)b->x_res, (int64_t)s.hidden / 8, s.vocab, rope_cur_args(b),
@@ -1312,6 +1403,8 @@ void qie_batch_destroy(qie_batch* b) {
     if (!b) return;
     if (b->e && b->e->stream) hipStreamSynchronize(b->e->stream);
     if (b->gexec) hipGraphExecDestroy(b->gexec);
+    for (auto& g : b->v_graphs) hipGraphExecDestroy(g.exec);
+    if (b->v.mem) hipFree(b->v.mem);
     void* ps[] = {b->kc, b->vc, b->d_table, b->d_pos, b->d_rope_cur, b->d_step, b->d_hist, b->d_ids, b->d_keys, b->x_res, b->qkv, b->q,
                   b->att, b->h, b->logits, b->attn_ws, b->dec_ws, b->samp_ws, b->pf_x, b->pf_hn, b->pf_qkv, b->pf_q,
                   b->pf_att, b->pf_h, b->pf_pos, b->pf_ids, b->pf_attn_ws, b->part, b->logits_full,
@@ -1665,6 +1758,186 @@ int qie_batch_set_position(qie_batch* b, int32_t seq, int32_t pos, int32_t token
     QIE_LAUNCH_CHECK();
     QIE_HIP(hipStreamSynchronize(e->stream));
     b->h_pos[seq] = pos;
+    return 0;
+}
+
+// ------------------------------------------------------------ speculative verify
+// The step's row buffers, once per batch at kVerifyMaxRows rows: one allocation carved into
+// 256-byte aligned pieces, so a failure leaves nothing behind and captured steps keep valid
+// pointers for the batch's lifetime.
+static int ensure_verify_bufs(qie_batch* b) {
+    if (b->v.mem) return 0;
+    qie_engine* e = b->e;
+    const qie_model_spec& s = e->spec;
+    const TpShard& sh = e->sh;
+    const int64_t R = kVerifyMaxRows, H = s.hidden, QD = (int64_t)sh.nq * s.head_dim, KD = (int64_t)sh.nkv * s.head_dim;
+    const bool comm = use_comm(e);
+    qie_batch::VerifyBufs v;
+    size_t off = 0;
+    char* base = nullptr;
+    auto take = [&](auto** p, int64_t bytes) {
+        if (base) *p = reinterpret_cast<std::remove_reference_t<decltype(*p)>>(base + off);
+        off += ((size_t)std::max<int64_t>(bytes, 16) + 255) / 256 * 256;
+    };
+    auto carve = [&]() {
+        off = 0;
+        take(&v.x, R * H * 2);
+        take(&v.xn, R * H * 2);
+        take(&v.qkv, R * (QD + 2 * KD) * 2);
+        take(&v.q, R * QD * 2);
+        take(&v.att, R * QD * 2);
+        take(&v.h, R * (int64_t)sh.ffn * 2);
+        take(&v.logits, R * (int64_t)sh.vocab * 2);
+        take(&v.attn_ws, qie_attention_extend_workspace_bytes(R, sh.nq, s.head_dim, b->max_ctx + b->run_pad));
+        take(&v.samp_ws, qie_sample_workspace_bytes(R, s.vocab));
+        take(&v.keys, R * 8);
+        take(&v.ids, R * 4);
+        take(&v.pos, R * 4);
+        take(&v.step, R * 4);
+        take(&v.draft, R * 4);
+        take(&v.res, (R + 1) * 4);
+        if (comm) {
+            take(&v.part, R * H * 4);
+            take(&v.logits_full, R * (int64_t)s.vocab * 2);
+            take(&v.gather_tmp, R * (int64_t)s.vocab * 2);
+        }
+    };
+    carve();   // sizes
+    void* mem = nullptr;
+    QIE_TRY(dmalloc(&mem, off));
+    base = (char*)mem;
+    carve();   // pointers
+    v.mem = mem;
+    // key slots start zero (the commit kernel leaves them so); the fp8 batched-decode kernel's
+    // split-K workspace must exist before a capture (batch 1 never made it for M = 1)
+    hipError_t he = hipMemsetAsync(mem, 0, off, e->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
+    int rc = he == hipSuccess ? 0 : fail((int)he, "qie_verify: buffer init: %s", hipGetErrorString(he));
+    if (!rc && e->fp8) rc = dec8_reserve(e->stream);
+    if (rc) {
+        hipFree(mem);
+        return rc;
+    }
+    b->v = v;
+    return 0;
+}
+
+// rows -> layers -> head -> commit, all on device state: capturable as one linear chain
+static int enqueue_verify(qie_batch* b, int seq, int M, const qie_sampling* smp) {
+    qie_engine* e = b->e;
+    const qie_model_spec& s = e->spec;
+    hipStream_t st = e->stream;
+    const int64_t H8 = (int64_t)s.hidden / 8;
+    VerifyRowsArgs ra{seq, M, b->v.draft, s.vocab, (const uint4*)e->w.embed, (const uint4*)b->x_res, H8,
+                      b->d_pos, b->d_step, (uint4*)b->v.x, b->v.pos, b->v.step};
+    QIE_TRY(launch_verify_rows(ra, st));
+    const qie_kv_cache cache = batch_cache(b, seq);
+    const LayerRows r{M, b->v.x, b->v.xn, b->v.qkv, b->v.att, b->v.h, b->v.part};
+    for (int l = 0; l < s.n_layers; l++) QIE_TRY(enqueue_layer_verify(b, l, r, cache));
+    QIE_TRY(enqueue_head_rows(b, b->v.x, s.hidden, M, smp, verify_head(b)));
+    const bool greedy = is_greedy(smp);
+    VerifyCommitArgs ca{seq, M, greedy ? b->v.keys : nullptr, b->v.ids, b->v.draft, s.vocab, b->d_pos, b->d_step,
+                        b->d_hist, b->max_ctx, b->d_ids, (const uint4*)e->w.embed, (uint4*)b->x_res, H8,
+                        rope_cur_args(b), b->v.logits, b->logits, (int64_t)e->sh.vocab, b->v.res};
+    return launch_verify_commit(ca, st);
+}
+
+// eager, or the captured step of (seq, M, sampling): captured once on the engine's stream
+// (a linear chain, no forked branches), replayed afterwards
+static int launch_verify(qie_batch* b, int seq, int M, const qie_sampling* smp) {
+    qie_engine* e = b->e;
+    if (!e->opts.use_graph) return enqueue_verify(b, seq, M, smp);
+    const bool greedy = is_greedy(smp);
+    for (const auto& g : b->v_graphs)
+        if (g.seq == seq && g.M == M && g.greedy == greedy && (greedy || same_sampling(g.smp, smp))) {
+            QIE_HIP(hipGraphLaunch(g.exec, e->stream));
+            return 0;
+        }
+    if (b->v_graphs.size() >= 64) {   // bounded: drop the oldest captured step
+        hipGraphExecDestroy(b->v_graphs.front().exec);
+        b->v_graphs.erase(b->v_graphs.begin());
+    }
+    hipGraph_t g = nullptr;
+    QIE_HIP(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
+    const int rc = enqueue_verify(b, seq, M, smp);
+    const hipError_t he = hipStreamEndCapture(e->stream, &g);
+    if (rc) {
+        if (g) hipGraphDestroy(g);
+        return rc;
+    }
+    if (he != hipSuccess) return fail((int)he, "qie_verify: graph capture: %s", hipGetErrorString(he));
+    hipGraphExec_t exec = nullptr;
+    const hipError_t hi = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
+    hipGraphDestroy(g);
+    if (hi != hipSuccess) return fail((int)hi, "qie_verify: graph instantiate: %s", hipGetErrorString(hi));
+    b->v_graphs.push_back({seq, M, greedy, smp ? *smp : qie_sampling{1, 0.f, 1.f, 0}, exec});
+    QIE_HIP(hipGraphLaunch(exec, e->stream));
+    return 0;
+}
+
+int qie_verify(qie_batch* b, int32_t seq, const int32_t* draft, int32_t n_draft, const qie_sampling* smp,
+               int32_t* out_ids, int32_t* n_out) {
+    QIE_REQUIRE(b && out_ids && n_out && seq >= 0 && seq < b->B && n_draft >= 0 && (n_draft == 0 || draft),
+                "qie_verify: bad arguments");
+    QIE_REQUIRE(n_draft + 1 <= QIE_VERIFY_MAX_ROWS, "qie_verify: %d drafts exceed the %d rows of a step (at most %d)",
+                n_draft, QIE_VERIFY_MAX_ROWS, QIE_VERIFY_MAX_ROWS - 1);
+    qie_engine* e = b->e;
+    const qie_model_spec& s = e->spec;
+    QIE_REQUIRE(!b->idle[seq], "qie_verify: slot %d holds no live sequence", seq);
+    QIE_REQUIRE(!(e->fp8 && e->opts.prefill_fp8),
+                "qie_verify: not available on a prefill_fp8 engine (block-scaled fp8 activations are defined for a "
+                "prefill from position 0 only)");
+    QIE_REQUIRE(b->decode_mode == 0, "qie_verify: the batch is in decode mode 1 (the persistent step); verify runs "
+                                     "the five-launch layer, set mode 0 first");
+    for (int i = 0; i < n_draft; i++)
+        QIE_REQUIRE(draft[i] >= 0 && draft[i] < s.vocab, "qie_verify: draft id %d out of range", draft[i]);
+    const int p = b->h_pos[seq], M = n_draft + 1;
+    QIE_REQUIRE((int64_t)p + n_draft + 1 < b->max_ctx, "qie_verify: %d rows from position %d do not fit max_ctx %d", M,
+                p, b->max_ctx);
+    if (b->d_table) {   // all-or-nothing, before anything is allocated or launched
+        const int64_t need = ((int64_t)p + M + b->page_tokens - 1) / b->page_tokens - b->held[seq];
+        if (need > (int64_t)b->free_pages.size())
+            return fail(-28, "qie_verify: KV pool exhausted (%lld more pages needed for %d rows at position %d, %zu free)",
+                        (long long)need, M, p, b->free_pages.size());
+    }
+    QIE_TRY(ensure_verify_bufs(b));
+    QIE_TRY(ensure_pages(b, seq, (int64_t)p + M));
+    QIE_TRY(flush_table(b));
+    hipStream_t st = e->stream;
+    if (n_draft > 0) QIE_HIP(hipMemcpyAsync(b->v.draft, draft, (size_t)n_draft * 4, hipMemcpyHostToDevice, st));
+    QIE_TRY(launch_verify(b, seq, M, smp));
+    // the accepted count and the ids (and the exchange error word) in one stream-ordered batch
+    int32_t res[kVerifyMaxRows + 1] = {0};
+    QIE_HIP(hipMemcpyAsync(res, b->v.res, (size_t)(M + 1) * 4, hipMemcpyDeviceToHost, st));
+    const unsigned* ew = use_comm(e) ? e->comm->error_word() : nullptr;
+    unsigned err = 0;
+    if (ew) QIE_HIP(hipMemcpyAsync(&err, ew, sizeof(err), hipMemcpyDeviceToHost, st));
+    QIE_HIP(hipStreamSynchronize(st));
+    if (ew && err)
+        return fail(-7, "qie_verify: tensor-parallel exchange failed on the device (error word %u: a peer rank did not "
+                        "arrive within the bounded wait); the communicator is unusable", err);
+    if (!ew) QIE_TRY(comm_check(e, "qie_verify"));
+    const int n = res[0];
+    if (n < 1 || n > M) return fail(-5, "qie_verify: the step reported %d accepted rows of %d", n, M);
+    for (int i = 0; i < n; i++) out_ids[i] = res[1 + i];
+    *n_out = n;
+    b->h_pos[seq] = p + n;
+    b->v_rows = M;
+    return 0;
+}
+
+int qie_verify_logits(qie_batch* b, void* host_out) {
+    QIE_REQUIRE(b && host_out, "qie_verify_logits: bad arguments");
+    QIE_REQUIRE(b->v.mem && b->v_rows > 0, "qie_verify_logits: no qie_verify has run on this batch");
+    qie_engine* e = b->e;
+    const uint16_t* src = b->v.logits;
+    if (use_comm(e)) {   // collective: every rank calls this at the same point
+        QIE_TRY(gather_rows(b, verify_head(b), b->v_rows));
+        src = b->v.logits_full;
+    }
+    QIE_HIP(hipStreamSynchronize(e->stream));
+    QIE_TRY(comm_check(e, "qie_verify_logits"));
+    QIE_HIP(d2h(e, host_out, src, (size_t)b->v_rows * e->spec.vocab * 2));
     return 0;
 }
 

@@ -300,6 +300,26 @@ inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 __host__ __device__ constexpr int rope_cur_stride(int hd) { return 8 + hd; }
 // the decode attention launches of this host thread read this table (null: none)
 void set_decode_rope_cur(const float* rc);
+// The RoPE table row of a slot's current position, kept beside the position (tagged with it)
+// so that the decode attention's prologue loads need not wait for the position
+// (DecodeAttnParams::rc).  Every kernel that sets a position also writes the row.
+struct RopeCurArgs {
+    float* rc;
+    const float* cs;
+    const float* sn;
+    int hd, rows;
+};
+__device__ __forceinline__ void write_rope_cur(const RopeCurArgs& r, int m, int p) {
+    if (!r.rc) return;
+    float* o = r.rc + (int64_t)m * rope_cur_stride(r.hd);
+    const bool ok = p >= 0 && p < r.rows;
+    const int h2 = r.hd / 2;
+    for (int t = threadIdx.x; t < h2; t += blockDim.x) {
+        o[8 + t] = ok ? r.cs[(int64_t)p * h2 + t] : 0.f;
+        o[8 + h2 + t] = ok ? r.sn[(int64_t)p * h2 + t] : 0.f;
+    }
+    if (threadIdx.x == 0) o[0] = __int_as_float(ok ? p : -1);
+}
 
 // Peer-backend tagged exchange (comm.hip): rank r's partial of generation e sits in every
 // rank's buffer at tagged slot [e & 1][r] as 8-byte words {tag = e + 1, f32 value}, so a

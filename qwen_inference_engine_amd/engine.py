@@ -298,6 +298,31 @@ class Batch:
         _lib.check(self.lib.qie_decode(self.h, n_steps, C.byref(sc), ptr), "qie_decode")
         return out[:n_steps] if want_ids else None
 
+    def verify(self, seq: int, draft: Sequence[int], sampling: Sampling = GREEDY) -> List[int]:
+        """Speculative verify (qie_verify): `draft` holds up to 15 guesses of the tokens after
+        the sequence's pending current token.  One pass over the weights scores the current
+        token and every draft; returns the tokens the model itself picks, t_0 .. t_a, where a
+        is the number of leading drafts it agrees with (always at least t_0).  The sequence is
+        then exactly as after len(result) decode steps."""
+        n = len(draft)
+        arr = (C.c_int32 * max(n, 1))(*[int(i) for i in draft])
+        out = (C.c_int32 * (n + 1))()
+        n_out = C.c_int32(0)
+        sc = sampling.to_c()
+        _lib.check(self.lib.qie_verify(self.h, seq, arr, n, C.byref(sc), out, C.byref(n_out)), "qie_verify")
+        self._verify_rows = n + 1
+        return [int(t) for t in out[:n_out.value]]
+
+    def verify_logits(self) -> np.ndarray:
+        """bf16 logits [len(draft) + 1][V] of every row of the last verify() (row i scored
+        the token after the current token + i drafts)."""
+        rows = getattr(self, "_verify_rows", 0)
+        if rows <= 0:
+            raise _lib.QieError("verify_logits: no verify() has run on this batch")
+        out = np.zeros((rows, self.e.spec.vocab), dtype=np.uint16)
+        _lib.check(self.lib.qie_verify_logits(self.h, out.ctypes.data), "qie_verify_logits")
+        return out
+
     def logits(self) -> np.ndarray:
         out = np.zeros((self.B, self.e.spec.vocab), dtype=np.uint16)
         _lib.check(self.lib.qie_batch_logits(self.h, out.ctypes.data), "qie_batch_logits")
