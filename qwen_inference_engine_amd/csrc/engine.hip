@@ -24,6 +24,7 @@
 #include <chrono>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <type_traits>
 #include <vector>
 
@@ -281,6 +282,14 @@ static qie_kv_cache batch_cache(const qie_batch* b, int seq0) {
 // ------------------------------------------------------------ page pool
 // Host-side allocator of the paged batch.  Decisions are deterministic, so the
 // tensor-parallel ranks (each holding its own heads' pages) stay in step.
+
+// Pages slot seq still lacks to hold ntok tokens (negative: it holds more than they need; 0 on
+// a contiguous batch).  The all-or-nothing checks sum this before anything is drawn.
+static int64_t pages_missing(const qie_batch* b, int seq, int64_t ntok) {
+    if (!b->d_table) return 0;
+    return (ntok + b->page_tokens - 1) / b->page_tokens - b->held[seq];
+}
+
 static int ensure_pages(qie_batch* b, int seq, int64_t ntok) {
     if (!b->d_table) return 0;
     const int64_t need = (ntok + b->page_tokens - 1) / b->page_tokens;
@@ -345,6 +354,7 @@ static int check_align(const void* p, const char* what, int layer) {
 // own_arena: the bf16 weights live in the engine's arena (synthetic init, weights.bin), so
 // they may be rewritten with their dequantisation for prefill; caller-owned weights
 // (qie_engine_set_weights) are never written — their prefill takes the fp8 GEMM path.
+static bool dec8_takes_tiled_projections(const qie_engine* e);   // (beside the projection builders)
 static int quantize_weights_fp8(qie_engine* e, bool own_arena) {
     QIE_REQUIRE(e->sh.tp == 1, "fp8 weights with tensor parallelism are not supported yet");
     const qie_model_spec& s = e->spec;
@@ -390,18 +400,7 @@ static int quantize_weights_fp8(qie_engine* e, bool own_arena) {
     // at any batch (it is then their only reader; prefill reads the dequantised bf16 copy, so
     // the engine must own its arena).  QIE_FP8_T16=0 (dev) keeps the plain layout.
     if (own_arena && dev_env("QIE_FP8_T16", 1) != 0) {
-        auto ok = [&](int64_t K, int64_t N, int64_t s0, int64_t s1, int64_t s2, bool norm, int epi) {
-            qie_linear_args a;
-            std::memset(&a, 0, sizeof(a));
-            a.flags = QIE_LINEAR_FP8 | QIE_LINEAR_FP8_T16;
-            a.M = 1; a.K = K; a.N = N; a.ldx = K;
-            a.seg_rows[0] = s0; a.seg_rows[1] = s1; a.seg_rows[2] = s2;
-            a.norm_w = norm ? (const void*)e : nullptr;   // (only tested for presence)
-            a.epilogue = epi;
-            return dec8_applies(&a);
-        };
-        const bool all = ok(H, QD + 2 * KD, QD, KD, KD, true, QIE_EPI_STORE) && ok(QD, H, H, 0, 0, false, QIE_EPI_RESIDUAL) &&
-                         ok(H, I, I, I, 0, true, QIE_EPI_SWIGLU) && ok(I, H, H, 0, 0, false, QIE_EPI_RESIDUAL);
+        const bool all = dec8_takes_tiled_projections(e);
         // the vocabulary projection too: its readers (the decode step's and the prefill's
         // last-row heads, <= 8 rows) run the skinny kernel, which reads the tiled layout
         // (through the batched-decode kernel instead — one 7-wave block per CU, ~37 tiles
@@ -480,19 +479,16 @@ static int bind_from_index(qie_engine* e) {
 }
 
 // ------------------------------------------------------------- enqueue helpers
-// every weight linear of the engine: fp8 weights when the engine quantised them
-static qie_linear_args lin_base(const qie_engine* e) {
+static qie_linear_args lin_args(int flags) {
     qie_linear_args a;
     std::memset(&a, 0, sizeof(a));
-    a.flags = e->fp8 ? QIE_LINEAR_FP8 : 0;
+    a.flags = flags;
     return a;
 }
+// every weight linear of the engine: fp8 weights when the engine quantised them
+static int lin_flags(const qie_engine* e) { return e->fp8 ? QIE_LINEAR_FP8 : 0; }
 // the layer projections (QKV, O, gate/up, down): + the tiled-layout flag where they are tiled
-static qie_linear_args lin_proj(const qie_engine* e) {
-    qie_linear_args a = lin_base(e);
-    if (e->fp8_t16) a.flags |= QIE_LINEAR_FP8_T16;
-    return a;
-}
+static int proj_flags(const qie_engine* e) { return lin_flags(e) | (e->fp8_t16 ? QIE_LINEAR_FP8_T16 : 0); }
 
 // The exchange steps go through the communicator under tensor parallelism, and at world 1
 // when the engine was asked to (opts.comm_always: the captured-collective path on one GPU).
@@ -509,12 +505,14 @@ static hipError_t d2h(const qie_engine* e, void* dst, const void* src, size_t by
 
 // After a stream synchronisation: a device-side exchange failure (the peer backend's bounded
 // wait) makes the call fail instead of returning ids computed from a partial exchange.
+static int comm_fail(const char* who, long long err) {
+    return fail(-7, "%s: tensor-parallel exchange failed on the device (error word %lld: a peer rank did "
+                    "not arrive within the bounded wait); the communicator is unusable", who, err);
+}
 static int comm_check(const qie_engine* e, const char* who) {
     if (!use_comm(e)) return 0;
     const int err = e->comm->error_state(e->stream);
-    if (err) return fail(-7, "%s: tensor-parallel exchange failed on the device (error word %d: a peer rank did "
-                             "not arrive within the bounded wait); the communicator is unusable", who, err);
-    return 0;
+    return err ? comm_fail(who, err) : 0;
 }
 
 // Row-parallel projection epilogue under tensor parallelism: fp32 partials -> all-reduce
@@ -546,22 +544,30 @@ static int row_parallel(qie_batch* b, qie_linear_args& a, uint16_t* x, float* pa
     return e->comm->allreduce_residual_bf16(part, x, n, e->stream);   // one kernel on the peer backend
 }
 
-// Batched rows (2 <= M <= 16, the skinny MFMA kernel): RMSNorm the M rows once into b->xn
+// Batched rows (2 <= M <= 16, the skinny MFMA kernel): RMSNorm the M rows once into xn [M][K]
 // (qie_rmsnorm, normalization.cu:5-25 semantics) and feed the projection plain rows.  The
 // skinny kernel's fused norm prologue recomputed every row's norm in every workgroup and
 // cost 13-16 us per launch at B = 8 (tools/ubench_b8.py, QIE_SKINNY_DBG); M = 1 keeps the
 // GEMV's fused x-first prologue.  QIE_PRENORM=0 restores the fused form (A/B).
-// xn: the [M][K] rows the norm lands in (default: the batch's decode rows, [B][H])
-static int prenorm(qie_batch* b, qie_linear_args& a, int64_t M, uint16_t* xn = nullptr) {
+// The decision (qie_batch_time_kernel applies it without launching a norm) ...
+static bool prenorm_applies(const qie_linear_args& a) {
     static const int on = dev_env("QIE_PRENORM", 1);
-    if (!on || M < 2 || M > 16 || !a.norm_w) return 0;
-    if (dec8_applies(&a) && dev_env("QIE_DEC8_PRENORM", 0) == 0) return 0;   // the fp8 batched-decode kernel fuses the norm
-    if (!xn) xn = b->xn;
-    QIE_TRY(qie_rmsnorm(a.x, a.norm_w, xn, M, a.K, a.norm_eps, a.numerics, b->e->stream));
+    if (!on || a.M < 2 || a.M > 16 || !a.norm_w) return false;
+    return !dec8_applies(&a) || dev_env("QIE_DEC8_PRENORM", 0) != 0;   // the fp8 batched-decode kernel fuses the norm
+}
+// ... and the action: the projection reads the normed rows xn instead of norming x itself
+static void take_normed(qie_linear_args& a, const uint16_t* xn) {
     a.x = xn;
     a.ldx = a.K;
     a.norm_w = nullptr;
+}
+static int norm_rows(qie_batch* b, qie_linear_args& a, uint16_t* xn) {
+    QIE_TRY(qie_rmsnorm(a.x, a.norm_w, xn, a.M, a.K, a.norm_eps, a.numerics, b->e->stream));
+    take_normed(a, xn);
     return 0;
+}
+static int prenorm(qie_batch* b, qie_linear_args& a, uint16_t* xn) {
+    return prenorm_applies(a) ? norm_rows(b, a, xn) : 0;
 }
 
 // batch 1, REF numerics, no qk-norm (Qwen2): the decode QKV projection's epilogue rotates q
@@ -580,25 +586,27 @@ static int dbg_snap(qie_batch* b, int slot) {
     return 0;
 }
 
-// The M rows a decode-form layer works on: the decode step's are the batch's B slots, a
-// verify step's (qie_verify) its own M <= 16 rows of one sequence.
+// The M rows a layer works on: the decode step's are the batch's B slots, a verify step's
+// (qie_verify) its own M <= 16 rows of one sequence, a prefill's the prompt rows.
 struct LayerRows {
     int64_t M;
-    uint16_t *x, *xn, *qkv, *att, *h;   // residual [M][H], normed [M][H], [M][QKVD], [M][QD], [M][I]
-    float* part;                        // [M][H] fp32 partials (exchange path only)
+    uint16_t *x, *xn, *qkv, *q, *att, *h;   // residual [M][H], normed [M][H], [M][QKVD], [M][QD] x 2, [M][I]
+    float* part;                            // [M][H] fp32 partials (exchange path only)
+    const int32_t* pos;                     // [M] positions on device; consecutive runs of
+    int32_t rows_per_seq;                   //   rows_per_seq rows belong to one sequence
 };
 static LayerRows decode_rows(const qie_batch* b) {
-    return LayerRows{b->B, b->x_res, b->xn, b->qkv, b->att, b->h, b->part};
+    return LayerRows{b->B, b->x_res, b->xn, b->qkv, b->q, b->att, b->h, b->part, b->d_pos, 1};
 }
 
-// The four projections of the decode-form layer: [norm + QKV (+ bias)], [O + residual],
-// [norm + gate/up + SwiGLU], [down + residual]
-static int proj_qkv(qie_batch* b, int l, const LayerRows& r, const LinearExtras& ex) {
-    qie_engine* e = b->e;
+// The four projections of a layer, described once: [norm + QKV (+ bias)], [O], [norm + gate/up +
+// SwiGLU], [down].  L: the layer's weights (e->layers[l], or the dequantised e->layers_pf[l]);
+// flags: proj_flags(e), less the fp8 bits on the dequantised copy.  Nothing is launched; O and
+// down get their output and epilogue from row_parallel.
+static qie_linear_args qkv_args(const qie_engine* e, const qie_layer_weights& L, int flags, const LayerRows& r) {
     const qie_model_spec& s = e->spec;
-    const qie_layer_weights& L = e->layers[l];
     const int64_t H = s.hidden, QD = (int64_t)e->sh.nq * s.head_dim, KD = (int64_t)e->sh.nkv * s.head_dim;
-    qie_linear_args a = lin_proj(e);
+    qie_linear_args a = lin_args(flags);
     a.x = r.x; a.ldx = H;
     a.w[0] = L.wq; a.w[1] = L.wk; a.w[2] = L.wv;
     a.bias[0] = L.bq; a.bias[1] = L.bk; a.bias[2] = L.bv;
@@ -607,86 +615,144 @@ static int proj_qkv(qie_batch* b, int l, const LayerRows& r, const LinearExtras&
     a.y = r.qkv; a.ldy = QD + 2 * KD;
     a.epilogue = QIE_EPI_STORE;
     a.norm_w = L.attn_norm; a.norm_eps = s.rms_eps; a.numerics = s.numerics;
-    QIE_TRY(prenorm(b, a, r.M, r.xn));
-    return linear(&a, ex, e->stream);
+    return a;
 }
-static int proj_o(qie_batch* b, int l, const LayerRows& r) {
-    qie_engine* e = b->e;
+static qie_linear_args o_args(const qie_engine* e, const qie_layer_weights& L, int flags, const LayerRows& r) {
     const int64_t H = e->spec.hidden, QD = (int64_t)e->sh.nq * e->spec.head_dim;
-    qie_linear_args a = lin_proj(e);
+    qie_linear_args a = lin_args(flags);
     a.x = r.att; a.ldx = QD;
-    a.w[0] = e->layers[l].wo; a.seg_rows[0] = H;
+    a.w[0] = L.wo; a.seg_rows[0] = H;
     a.M = r.M; a.K = QD; a.N = H;
     a.ldy = H;
-    return row_parallel(b, a, r.x, r.part, r.M);
+    return a;
 }
-static int proj_gate_up(qie_batch* b, int l, const LayerRows& r) {
-    qie_engine* e = b->e;
+static qie_linear_args gate_up_args(const qie_engine* e, const qie_layer_weights& L, int flags, const LayerRows& r) {
     const qie_model_spec& s = e->spec;
-    const qie_layer_weights& L = e->layers[l];
     const int64_t H = s.hidden, I = e->sh.ffn;
-    qie_linear_args a = lin_proj(e);
+    qie_linear_args a = lin_args(flags);
     a.x = r.x; a.ldx = H;
     a.w[0] = L.w_gate; a.w[1] = L.w_up; a.seg_rows[0] = I; a.seg_rows[1] = I;
     a.M = r.M; a.K = H; a.N = I;
     a.y = r.h; a.ldy = I;
     a.epilogue = QIE_EPI_SWIGLU;
     a.norm_w = L.ffn_norm; a.norm_eps = s.rms_eps; a.numerics = s.numerics;
-    QIE_TRY(prenorm(b, a, r.M, r.xn));
-    return linear(&a, LinearExtras{}, e->stream);
+    return a;
 }
-static int proj_down(qie_batch* b, int l, const LayerRows& r) {
-    qie_engine* e = b->e;
+static qie_linear_args down_args(const qie_engine* e, const qie_layer_weights& L, int flags, const LayerRows& r) {
     const int64_t H = e->spec.hidden, I = e->sh.ffn;
-    qie_linear_args a = lin_proj(e);
+    qie_linear_args a = lin_args(flags);
     a.x = r.h; a.ldx = I;
-    a.w[0] = e->layers[l].w_down; a.seg_rows[0] = H;
+    a.w[0] = L.w_down; a.seg_rows[0] = H;
     a.M = r.M; a.K = I; a.N = H;
     a.ldy = H;
+    return a;
+}
+
+// quantize_weights_fp8: whether the fp8 batched-decode kernel takes every projection of the
+// decode step from 16-row tiled weights, already at one row (then it is their only reader)
+static bool dec8_takes_tiled_projections(const qie_engine* e) {
+    const LayerRows r{1};
+    const qie_layer_weights& L = e->layers[0];
+    const int fl = QIE_LINEAR_FP8 | QIE_LINEAR_FP8_T16;
+    qie_linear_args o = o_args(e, L, fl, r), down = down_args(e, L, fl, r);
+    o.epilogue = down.epilogue = QIE_EPI_RESIDUAL;   // as row_parallel launches them on one GPU
+    const qie_linear_args all[] = {qkv_args(e, L, fl, r), o, gate_up_args(e, L, fl, r), down};
+    for (const qie_linear_args& a : all)
+        if (!dec8_applies(&a)) return false;
+    return true;
+}
+
+// How a built projection gets its input, applied before the launch:
+//   Decode  prenorm()'s rule (2..16 rows: norm once into the rows' xn; else the fused norm)
+//   Normed  RMSNorm into xn at every row count (prefill)
+//   Fp8     Normed (no norm for O and down), then the rows quantised per row to e4m3 codes +
+//           exponents (opts.prefill_fp8: QIE_LINEAR_ACT_FP8 on the block-scaled MFMA GEMM)
+enum class InputForm { Decode, Normed, Fp8 };
+static int stage_input(qie_batch* b, InputForm form, qie_linear_args& a, const LayerRows& r) {
+    if (form == InputForm::Decode) return prenorm(b, a, r.xn);
+    if (a.norm_w) QIE_TRY(norm_rows(b, a, r.xn));
+    if (form == InputForm::Normed) return 0;
+    QIE_TRY(qie_quantize_rows_fp8(a.x, a.ldx, a.M, a.K, b->pf_q8, a.K, b->pf_e8, b->e->stream));
+    a.x = b->pf_q8; a.ldx = a.K; a.x_exps = b->pf_e8;
+    a.flags |= QIE_LINEAR_ACT_FP8;
+    return 0;
+}
+
+// Which weight table a step's projections read, with which base flags and input form
+struct LayerPath {
+    const qie_layer_weights* layers;
+    int flags;
+    InputForm in;
+};
+static LayerPath decode_path(const qie_engine* e) { return LayerPath{e->layers.data(), proj_flags(e), InputForm::Decode}; }
+
+// input stage, then the launch: QKV and gate/up as built ...
+static int run_proj(qie_batch* b, qie_linear_args a, InputForm in, const LayerRows& r,
+                    const LinearExtras& ex = LinearExtras{}) {
+    QIE_TRY(stage_input(b, in, a, r));
+    return linear(&a, ex, b->e->stream);
+}
+// ... O and down in residual or exchange form
+static int run_row_proj(qie_batch* b, qie_linear_args a, InputForm in, const LayerRows& r) {
+    QIE_TRY(stage_input(b, in, a, r));
     return row_parallel(b, a, r.x, r.part, r.M);
+}
+
+// the decode QKV projection's fused RoPE (rope_in_projection)
+static LinearExtras decode_qkv_extras(const qie_batch* b) {
+    const qie_engine* e = b->e;
+    const int64_t hd = e->spec.head_dim;
+    LinearExtras ex;
+    if (rope_in_projection(b)) ex.rope = RopeArgs{b->d_pos, e->rope_cos, e->rope_sin, (int)hd, (e->sh.nq + e->sh.nkv) * hd};
+    return ex;
+}
+// the decode step's attention of layer l into out ([B][QD]: b->att, or the timing call's scratch)
+static int attend_decode(qie_batch* b, int l, void* out) {
+    qie_engine* e = b->e;
+    const qie_model_spec& s = e->spec;
+    const qie_layer_weights& L = e->layers[l];
+    const qie_kv_cache cache = batch_cache(b, 0);
+    set_decode_rope_cur(b->d_rope_cur);
+    const int rc = qie_attention_decode(b->qkv, b->B, b->d_pos, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, e->sh.nq,
+                                        &cache, l, s.rms_eps,
+                                        s.numerics | (rope_in_projection(b) ? QIE_ATTN_PREROPED : 0), out, b->dec_ws,
+                                        e->stream);
+    set_decode_rope_cur(nullptr);
+    return rc;
 }
 
 static int enqueue_layer_decode(qie_batch* b, int l) {
     qie_engine* e = b->e;
-    const qie_model_spec& s = e->spec;
-    const qie_layer_weights& L = e->layers[l];
-    const int64_t hd = s.head_dim, QD = (int64_t)e->sh.nq * hd, KD = (int64_t)e->sh.nkv * hd;
-    const qie_kv_cache cache = batch_cache(b, 0);
+    const LayerPath p = decode_path(e);
+    const qie_layer_weights& L = p.layers[l];
     const LayerRows r = decode_rows(b);
-
-    const bool rope_in_proj = rope_in_projection(b);
-    LinearExtras ex;
-    if (rope_in_proj) ex.rope = RopeArgs{b->d_pos, e->rope_cos, e->rope_sin, (int)hd, QD + KD};
-    QIE_TRY(proj_qkv(b, l, r, ex));
-
-    set_decode_rope_cur(b->d_rope_cur);
-    const int arc = qie_attention_decode(b->qkv, r.M, b->d_pos, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, e->sh.nq,
-                                         &cache, l, s.rms_eps, s.numerics | (rope_in_proj ? QIE_ATTN_PREROPED : 0),
-                                         b->att, b->dec_ws, e->stream);
-    set_decode_rope_cur(nullptr);
-    QIE_TRY(arc);
-    QIE_TRY(proj_o(b, l, r));
+    QIE_TRY(run_proj(b, qkv_args(e, L, p.flags, r), p.in, r, decode_qkv_extras(b)));
+    QIE_TRY(attend_decode(b, l, r.att));
+    QIE_TRY(run_row_proj(b, o_args(e, L, p.flags, r), p.in, r));
     QIE_TRY(dbg_snap(b, 2 * l + 1));
-    QIE_TRY(proj_gate_up(b, l, r));
-    QIE_TRY(proj_down(b, l, r));
+    QIE_TRY(run_proj(b, gate_up_args(e, L, p.flags, r), p.in, r));
+    QIE_TRY(run_row_proj(b, down_args(e, L, p.flags, r), p.in, r));
     return dbg_snap(b, 2 * l + 2);
 }
 
-// The same layer for the M rows of ONE sequence at consecutive positions (the verify step):
-// the q/k post-projection writes the rows' K/V at their device positions v.pos, and the
-// split-context MFMA attention lets each row see the cached prefix and the rows before it.
-static int enqueue_layer_verify(qie_batch* b, int l, const LayerRows& r, const qie_kv_cache& cache) {
+// The layer of the multi-row forms (prefill, append, the verify step): the q/k post-projection
+// writes the rows' K/V at their positions r.pos, then `attend` runs over them — qie_attention
+// from position 0 (the rows are the whole context), qie_attention_extend where the rows
+// continue a cached prefix (each row sees the prefix and the rows before it).
+using AttentionFn = decltype(&qie_attention);
+static int enqueue_layer_rows(qie_batch* b, int l, const LayerRows& r, const LayerPath& p, const qie_kv_cache& cache,
+                              AttentionFn attend, void* attn_ws) {
     qie_engine* e = b->e;
     const qie_model_spec& s = e->spec;
-    const qie_layer_weights& L = e->layers[l];
+    const qie_layer_weights& L = p.layers[l];
     hipStream_t st = e->stream;
-    QIE_TRY(proj_qkv(b, l, r, LinearExtras{}));
-    QIE_TRY(qie_qkv_post(r.qkv, r.M, b->v.pos, (int32_t)r.M, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, e->sh.nq,
-                         &cache, l, s.rms_eps, s.numerics, b->v.q, st));
-    QIE_TRY(qie_attention_extend(b->v.q, r.M, b->v.pos, (int32_t)r.M, &cache, l, e->sh.nq, r.att, b->v.attn_ws, st));
-    QIE_TRY(proj_o(b, l, r));
-    QIE_TRY(proj_gate_up(b, l, r));
-    return proj_down(b, l, r);
+    QIE_TRY(run_proj(b, qkv_args(e, L, p.flags, r), p.in, r));
+    QIE_TRY(qie_qkv_post(r.qkv, r.M, r.pos, r.rows_per_seq, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, e->sh.nq,
+                         &cache, l, s.rms_eps, s.numerics, r.q, st));
+    QIE_TRY(attend(r.q, r.M, r.pos, r.rows_per_seq, &cache, l, e->sh.nq, r.att, attn_ws, st));
+    QIE_TRY(run_row_proj(b, o_args(e, L, p.flags, r), p.in, r));
+    QIE_TRY(run_proj(b, gate_up_args(e, L, p.flags, r), p.in, r));
+    return run_row_proj(b, down_args(e, L, p.flags, r), p.in, r);
 }
 
 static bool is_greedy(const qie_sampling* s) { return !s || s->top_k <= 1 || !(s->temperature > 0.f); }
@@ -741,6 +807,25 @@ static unsigned* pk_epoch_ptr(const qie_batch* b) {
     return (unsigned*)((unsigned long long*)b->pk_mem + persist_granule_count(b->e->spec));
 }
 
+// [final norm + lm_head] over M rows of x into hb.logits; greedy: + the fused arg-max into hb.keys
+static qie_linear_args head_args(const qie_engine* e, const uint16_t* x, int64_t ldx, int M, bool greedy,
+                                 const HeadBufs& hb) {
+    const qie_model_spec& s = e->spec;
+    const int64_t Vl = e->sh.vocab;
+    qie_linear_args a = lin_args(lin_flags(e) | (e->fp8_t16_head ? QIE_LINEAR_FP8_T16 : 0));
+    a.x = x; a.ldx = ldx;
+    a.w[0] = e->w.lm_head; a.seg_rows[0] = Vl;
+    a.M = M; a.K = s.hidden; a.N = Vl;
+    a.y = hb.logits; a.ldy = Vl;
+    a.epilogue = QIE_EPI_STORE;
+    a.norm_w = e->w.final_norm; a.norm_eps = s.rms_eps; a.numerics = s.numerics;
+    if (greedy) {
+        a.argmax_keys = (uint64_t*)hb.keys;
+        a.key_col0 = e->sh.vocab0;   // keys carry global vocab ids
+    }
+    return a;
+}
+
 // lm_head over M rows of x (already the residual stream), then the sampler; leaves the
 // choices in hb.keys (greedy) or hb.ids.
 static int enqueue_head_rows(qie_batch* b, const uint16_t* x, int64_t ldx, int M, const qie_sampling* smp,
@@ -748,21 +833,9 @@ static int enqueue_head_rows(qie_batch* b, const uint16_t* x, int64_t ldx, int M
     qie_engine* e = b->e;
     const qie_model_spec& s = e->spec;
     hipStream_t st = e->stream;
-    const int64_t Vl = e->sh.vocab;
-    qie_linear_args a = lin_base(e);
-    if (e->fp8_t16_head) a.flags |= QIE_LINEAR_FP8_T16;
-    a.x = x; a.ldx = ldx;
-    a.w[0] = e->w.lm_head; a.seg_rows[0] = Vl;
-    a.M = M; a.K = s.hidden; a.N = Vl;
-    a.y = hb.logits; a.ldy = Vl;
-    a.epilogue = QIE_EPI_STORE;
-    a.norm_w = e->w.final_norm; a.norm_eps = s.rms_eps; a.numerics = s.numerics;
-    QIE_TRY(prenorm(b, a, M, hb.xn));
     const bool greedy = is_greedy(smp);
-    if (greedy) {
-        a.argmax_keys = (uint64_t*)hb.keys;
-        a.key_col0 = e->sh.vocab0;   // keys carry global vocab ids
-    }
+    qie_linear_args a = head_args(e, x, ldx, M, greedy, hb);
+    QIE_TRY(prenorm(b, a, hb.xn));
     QIE_TRY(linear(&a, LinearExtras{}, st));
     if (greedy && use_comm(e)) QIE_TRY(e->comm->allreduce_max_u64((uint64_t*)hb.keys, M, st));
     if (!greedy) {
@@ -876,9 +949,6 @@ static int ensure_prefill_scratch(qie_batch* b, int64_t n, bool extend) {
     return 0;
 }
 
-// The ids and (tensor parallel, peer backend) the exchange error word come back in ONE
-// stream-ordered batch with one synchronisation — not a second blocking round trip per token
-// (ADVICE r05); a backend without the word keeps comm_check's own read.
 // The persistent step's error word (a bounded hand-off wait that gave up): the step's outputs
 // are garbage and the call fails loudly (never a hang; k_persist.hip)
 static int pk_fail(unsigned w) {
@@ -893,22 +963,25 @@ static int pk_check(qie_batch* b) {
     return w ? pk_fail(w) : 0;
 }
 
-static int sync_ids(qie_batch* b, int32_t* next_ids) {
-    if (!next_ids) return pk_check(b);
+// A step's results (the ids, a verify step's result words), the exchange error word (tensor
+// parallel, peer backend) and the persistent step's error word come back in ONE stream-ordered
+// batch with one synchronisation — not a second blocking round trip per token; a
+// backend without the word keeps comm_check's own read.
+static int read_back(qie_batch* b, void* dst, const void* src, size_t bytes, const char* who) {
     qie_engine* e = b->e;
-    QIE_HIP(hipMemcpyAsync(next_ids, b->d_ids, b->B * 4, hipMemcpyDeviceToHost, e->stream));
+    QIE_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, e->stream));
     const unsigned* ew = use_comm(e) ? e->comm->error_word() : nullptr;
     unsigned err = 0, pkw = 0;
     if (ew) QIE_HIP(hipMemcpyAsync(&err, ew, sizeof(err), hipMemcpyDeviceToHost, e->stream));
     if (b->pk_mem) QIE_HIP(hipMemcpyAsync(&pkw, pk_epoch_ptr(b) + 1, 4, hipMemcpyDeviceToHost, e->stream));
     QIE_HIP(hipStreamSynchronize(e->stream));
     if (pkw) return pk_fail(pkw);
-    if (ew) {
-        if (err) return fail(-7, "decode: tensor-parallel exchange failed on the device (error word %u: a peer rank "
-                                 "did not arrive within the bounded wait); the communicator is unusable", err);
-        return 0;
-    }
-    return comm_check(e, "decode");
+    if (ew) return err ? comm_fail(who, err) : 0;
+    return comm_check(e, who);
+}
+
+static int sync_ids(qie_batch* b, int32_t* next_ids) {
+    return next_ids ? read_back(b, next_ids, b->d_ids, (size_t)b->B * 4, "decode") : pk_check(b);
 }
 
 }  // namespace qie
@@ -1445,20 +1518,22 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
     for (int64_t i = 0; i < n; i++)
         QIE_REQUIRE(ids[i] >= 0 && ids[i] < s.vocab, "%s: token id %d out of range", who, ids[i]);
     hipStream_t st = e->stream;
-    if (append && b->d_table) {   // all-or-nothing, before anything is allocated or launched
-        const int64_t need = ((int64_t)pos0 + len + b->page_tokens - 1) / b->page_tokens - b->held[seq0];
+    if (append) {   // all-or-nothing, before anything is allocated or launched
+        const int64_t need = pages_missing(b, seq0, (int64_t)pos0 + len);
         if (need > (int64_t)b->free_pages.size())
             return fail(-28, "%s: KV pool exhausted (%lld more pages needed for %d rows at position %d, %zu free)",
                         who, (long long)need, len, pos0, b->free_pages.size());
     }
     QIE_TRY(ensure_prefill_scratch(b, n, append));
     if (b->d_table && !append) {   // all-or-nothing: the slots' own pages count, nothing is dropped on failure
-        const int64_t need = ((int64_t)len + b->page_tokens - 1) / b->page_tokens * n_seqs;
-        int64_t held = 0;
-        for (int z = 0; z < n_seqs; z++) held += b->held[seq0 + z];
-        QIE_REQUIRE(need <= (int64_t)b->free_pages.size() + held,
+        int64_t missing = 0, held = 0;
+        for (int z = 0; z < n_seqs; z++) {
+            missing += pages_missing(b, seq0 + z, len);
+            held += b->held[seq0 + z];
+        }
+        QIE_REQUIRE(missing <= (int64_t)b->free_pages.size(),
                     "%s: KV pool exhausted (%lld pages needed, %zu free + %lld held by slots %d..%d)", who,
-                    (long long)need, b->free_pages.size(), (long long)held, seq0, seq0 + n_seqs - 1);
+                    (long long)(missing + held), b->free_pages.size(), (long long)held, seq0, seq0 + n_seqs - 1);
     }
     // a prefill starts a new sequence in each slot: every target slot's pages go back to
     // the pool BEFORE any slot draws, so the check above (free + held) is exactly what the
@@ -1470,98 +1545,24 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
         b->idle[seq0 + z] = 0;
     }
     QIE_TRY(flush_table(b));
-    const TpShard& sh = e->sh;
-    const int64_t H = s.hidden, hd = s.head_dim, QD = (int64_t)sh.nq * hd, KD = (int64_t)sh.nkv * hd;
-    const int64_t QKVD = QD + 2 * KD, I = sh.ffn;
+    const int64_t H = s.hidden;
     QIE_HIP(hipMemcpyAsync(b->pf_ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b->pf_pos, (int)n, len, pos0);
     hipLaunchKernelGGL(copy_ids_kernel, dim3((len + 255) / 256, n_seqs), dim3(256), 0, st, b->pf_ids,
                        b->d_hist + (int64_t)seq0 * b->max_ctx + pos0, len, (int64_t)b->max_ctx);
     QIE_TRY(qie_embedding(e->w.embed, b->pf_ids, b->pf_x, n, H, st));
     const qie_kv_cache cache = batch_cache(b, seq0);
-    // fp8 engine, >= 256 rows: the GEMMs run on the dequantised bf16 copy (layers_pf); with
-    // tiled fp8 projections (readable by the batched-decode kernel only) every prefill of more
-    // than 16 rows does
+    const LayerRows r{n, b->pf_x, b->pf_hn, b->pf_qkv, b->pf_q, b->pf_att, b->pf_h, b->pf_part, b->pf_pos, len};
+    // opts.prefill_fp8: every projection on fp8 codes x fp8 weights (e->layers: the fp8 arena).
+    // Otherwise bf16 rows; on an fp8 engine at >= 256 rows the GEMMs run on the dequantised bf16
+    // copy (layers_pf), and with tiled fp8 projections (readable by the batched-decode kernel
+    // only) every prefill of more than 16 rows does
     const bool pf16 = e->fp8 && !e->layers_pf.empty() && (n >= 256 || (e->fp8_t16 && n > 16));
-    auto pf_base = [&]() {
-        qie_linear_args a = lin_proj(e);
-        if (pf16) a.flags &= ~(QIE_LINEAR_FP8 | QIE_LINEAR_FP8_T16);
-        return a;
-    };
-    const bool mx = prefill_mx(e);
-    // attention of the new rows: from position 0 the rows are the whole context (qie_attention's
-    // causal prefill forms); an append's rows attend to the cached prefix as well
-    auto attend = [&](int l) -> int {
-        if (append)
-            return qie_attention_extend(b->pf_q, n, b->pf_pos, len, &cache, l, sh.nq, b->pf_att, b->pf_attn_ws, st);
-        return qie_attention(b->pf_q, n, b->pf_pos, len, &cache, l, sh.nq, b->pf_att, b->pf_attn_ws, st);
-    };
-    // fp8 activations: quantise the projection input x [n][K] (bf16) into pf_q8 / pf_e8 and
-    // point the linear at the codes
-    auto mx_in = [&](qie_linear_args& a, const uint16_t* x, int64_t K) -> int {
-        QIE_TRY(qie_quantize_rows_fp8(x, K, n, K, b->pf_q8, K, b->pf_e8, st));
-        a.x = b->pf_q8; a.ldx = K; a.x_exps = b->pf_e8;
-        a.flags |= QIE_LINEAR_ACT_FP8;
-        return 0;
-    };
-    for (int l = 0; l < s.n_layers; l++) {
-        if (mx) {   // every projection on fp8 codes x fp8 weights (e->layers: the fp8 arena)
-            const qie_layer_weights& L = e->layers[l];
-            QIE_TRY(qie_rmsnorm(b->pf_x, L.attn_norm, b->pf_hn, n, H, s.rms_eps, s.numerics, st));
-            qie_linear_args a = lin_proj(e);
-            QIE_TRY(mx_in(a, b->pf_hn, H));
-            a.w[0] = L.wq; a.w[1] = L.wk; a.w[2] = L.wv;
-            a.bias[0] = L.bq; a.bias[1] = L.bk; a.bias[2] = L.bv;
-            a.seg_rows[0] = QD; a.seg_rows[1] = KD; a.seg_rows[2] = KD;
-            a.M = n; a.K = H; a.N = QKVD; a.y = b->pf_qkv; a.ldy = QKVD; a.epilogue = QIE_EPI_STORE;
-            QIE_TRY(qie_linear(&a, st));
-            QIE_TRY(qie_qkv_post(b->pf_qkv, n, b->pf_pos, len, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, sh.nq,
-                                 &cache, l, s.rms_eps, s.numerics, b->pf_q, st));
-            QIE_TRY(attend(l));
-            a = lin_proj(e);
-            QIE_TRY(mx_in(a, b->pf_att, QD));
-            a.w[0] = L.wo; a.seg_rows[0] = H;
-            a.M = n; a.K = QD; a.N = H; a.ldy = H;
-            QIE_TRY(row_parallel(b, a, b->pf_x, b->pf_part, n));
-            QIE_TRY(qie_rmsnorm(b->pf_x, L.ffn_norm, b->pf_hn, n, H, s.rms_eps, s.numerics, st));
-            a = lin_proj(e);
-            QIE_TRY(mx_in(a, b->pf_hn, H));
-            a.w[0] = L.w_gate; a.w[1] = L.w_up; a.seg_rows[0] = I; a.seg_rows[1] = I;
-            a.M = n; a.K = H; a.N = I; a.y = b->pf_h; a.ldy = I; a.epilogue = QIE_EPI_SWIGLU;
-            QIE_TRY(qie_linear(&a, st));
-            a = lin_proj(e);
-            QIE_TRY(mx_in(a, b->pf_h, I));
-            a.w[0] = L.w_down; a.seg_rows[0] = H;
-            a.M = n; a.K = I; a.N = H; a.ldy = H;
-            QIE_TRY(row_parallel(b, a, b->pf_x, b->pf_part, n));
-            continue;
-        }
-        const qie_layer_weights& L = pf16 ? e->layers_pf[l] : e->layers[l];
-        QIE_TRY(qie_rmsnorm(b->pf_x, L.attn_norm, b->pf_hn, n, H, s.rms_eps, s.numerics, st));
-        qie_linear_args a = pf_base();
-        a.x = b->pf_hn; a.ldx = H;
-        a.w[0] = L.wq; a.w[1] = L.wk; a.w[2] = L.wv;
-        a.bias[0] = L.bq; a.bias[1] = L.bk; a.bias[2] = L.bv;
-        a.seg_rows[0] = QD; a.seg_rows[1] = KD; a.seg_rows[2] = KD;
-        a.M = n; a.K = H; a.N = QKVD; a.y = b->pf_qkv; a.ldy = QKVD; a.epilogue = QIE_EPI_STORE;
-        QIE_TRY(qie_linear(&a, st));
-        QIE_TRY(qie_qkv_post(b->pf_qkv, n, b->pf_pos, len, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, sh.nq,
-                             &cache, l, s.rms_eps, s.numerics, b->pf_q, st));
-        QIE_TRY(attend(l));
-        a = pf_base();
-        a.x = b->pf_att; a.ldx = QD; a.w[0] = L.wo; a.seg_rows[0] = H;
-        a.M = n; a.K = QD; a.N = H; a.ldy = H;
-        QIE_TRY(row_parallel(b, a, b->pf_x, b->pf_part, n));
-        QIE_TRY(qie_rmsnorm(b->pf_x, L.ffn_norm, b->pf_hn, n, H, s.rms_eps, s.numerics, st));
-        a = pf_base();
-        a.x = b->pf_hn; a.ldx = H; a.w[0] = L.w_gate; a.w[1] = L.w_up; a.seg_rows[0] = I; a.seg_rows[1] = I;
-        a.M = n; a.K = H; a.N = I; a.y = b->pf_h; a.ldy = I; a.epilogue = QIE_EPI_SWIGLU;
-        QIE_TRY(qie_linear(&a, st));
-        a = pf_base();
-        a.x = b->pf_h; a.ldx = I; a.w[0] = L.w_down; a.seg_rows[0] = H;
-        a.M = n; a.K = I; a.N = H; a.ldy = H;
-        QIE_TRY(row_parallel(b, a, b->pf_x, b->pf_part, n));
-    }
+    LayerPath path{e->layers.data(), proj_flags(e), prefill_mx(e) ? InputForm::Fp8 : InputForm::Normed};
+    if (pf16 && path.in == InputForm::Normed)
+        path = LayerPath{e->layers_pf.data(), path.flags & ~(QIE_LINEAR_FP8 | QIE_LINEAR_FP8_T16), InputForm::Normed};
+    for (int l = 0; l < s.n_layers; l++)
+        QIE_TRY(enqueue_layer_rows(b, l, r, path, cache, append ? qie_attention_extend : qie_attention, b->pf_attn_ws));
     // position of each last prompt token; finalize advances it to pos0 + len (the new token).
     for (int z = 0; z < n_seqs; z++) {
         hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(64), 0, st, seq0 + z, pos0 + len - 1, 0,
@@ -1606,6 +1607,48 @@ static bool same_sampling(const qie_sampling& a, const qie_sampling* b) {
     return a.top_k == bb.top_k && a.temperature == bb.temperature && a.top_p == bb.top_p && a.seed == bb.seed;
 }
 
+// dev (QIE_GRAPH_DUMP): every node of a captured graph (type, grid, block, LDS)
+static void dump_graph(hipGraph_t g) {
+    size_t n = 0;
+    hipGraphGetNodes(g, nullptr, &n);
+    std::vector<hipGraphNode_t> nodes(n);
+    hipGraphGetNodes(g, nodes.data(), &n);
+    size_t max_shm = 0;
+    for (size_t i = 0; i < n; i++) {
+        hipGraphNodeType t;
+        hipGraphNodeGetType(nodes[i], &t);
+        if (t == hipGraphNodeTypeKernel) {
+            hipKernelNodeParams kp{};
+            hipGraphKernelNodeGetParams(nodes[i], &kp);
+            max_shm = std::max(max_shm, (size_t)kp.sharedMemBytes);
+            fprintf(stderr, "graph node %zu: kernel %p grid %u,%u,%u block %u,%u,%u dyn_lds %u\n", i, kp.func,
+                    kp.gridDim.x, kp.gridDim.y, kp.gridDim.z, kp.blockDim.x, kp.blockDim.y, kp.blockDim.z,
+                    kp.sharedMemBytes);
+        } else {
+            fprintf(stderr, "graph node %zu: type %d\n", i, (int)t);
+        }
+    }
+    fprintf(stderr, "graph: %zu nodes, max dynamic LDS %zu B\n", n, max_shm);
+}
+
+// What `enqueue` puts on the engine's stream, captured (thread-local mode) and instantiated
+// into *out; the graph is destroyed on every path.  `who` prefixes the failure messages.
+static int capture_graph(qie_engine* e, const char* who, const std::function<int()>& enqueue, hipGraphExec_t* out) {
+    hipGraph_t g = nullptr;
+    QIE_HIP(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
+    const int rc = enqueue();
+    hipError_t he = hipStreamEndCapture(e->stream, &g);
+    if (rc || he != hipSuccess) {
+        if (g) hipGraphDestroy(g);
+        return rc ? rc : fail((int)he, "%sgraph capture: %s", who, hipGetErrorString(he));
+    }
+    if (dev_env("QIE_GRAPH_DUMP", 0)) dump_graph(g);
+    he = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
+    hipGraphDestroy(g);
+    if (he != hipSuccess) return fail((int)he, "%sgraph instantiate: %s", who, hipGetErrorString(he));
+    return 0;
+}
+
 static int launch_step(qie_batch* b, const qie_sampling* smp) {
     qie_engine* e = b->e;
     if (!e->opts.use_graph) return enqueue_decode(b, smp);
@@ -1613,40 +1656,7 @@ static int launch_step(qie_batch* b, const qie_sampling* smp) {
         if (b->gexec) hipGraphExecDestroy(b->gexec);
         b->gexec = nullptr;
         b->graph_ok = false;
-        hipGraph_t g = nullptr;
-        QIE_HIP(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-        int rc = enqueue_decode(b, smp);
-        hipError_t he = hipStreamEndCapture(e->stream, &g);
-        if (rc) {
-            if (g) hipGraphDestroy(g);
-            return rc;
-        }
-        if (he != hipSuccess) return fail((int)he, "graph capture: %s", hipGetErrorString(he));
-        if (dev_env("QIE_GRAPH_DUMP", 0)) {   // dev: every node of the decode graph (type, grid, block, LDS)
-            size_t n = 0;
-            hipGraphGetNodes(g, nullptr, &n);
-            std::vector<hipGraphNode_t> nodes(n);
-            hipGraphGetNodes(g, nodes.data(), &n);
-            size_t max_shm = 0;
-            for (size_t i = 0; i < n; i++) {
-                hipGraphNodeType t;
-                hipGraphNodeGetType(nodes[i], &t);
-                if (t == hipGraphNodeTypeKernel) {
-                    hipKernelNodeParams kp{};
-                    hipGraphKernelNodeGetParams(nodes[i], &kp);
-                    max_shm = std::max(max_shm, (size_t)kp.sharedMemBytes);
-                    fprintf(stderr, "graph node %zu: kernel %p grid %u,%u,%u block %u,%u,%u dyn_lds %u\n", i, kp.func,
-                            kp.gridDim.x, kp.gridDim.y, kp.gridDim.z, kp.blockDim.x, kp.blockDim.y, kp.blockDim.z,
-                            kp.sharedMemBytes);
-                } else {
-                    fprintf(stderr, "graph node %zu: type %d\n", i, (int)t);
-                }
-            }
-            fprintf(stderr, "graph: %zu nodes, max dynamic LDS %zu B\n", n, max_shm);
-        }
-        he = hipGraphInstantiate(&b->gexec, g, nullptr, nullptr, 0);
-        hipGraphDestroy(g);
-        if (he != hipSuccess) return fail((int)he, "graph instantiate: %s", hipGetErrorString(he));
+        QIE_TRY(capture_graph(e, "", [&] { return enqueue_decode(b, smp); }, &b->gexec));
         b->gs = smp ? *smp : qie_sampling{1, 0.f, 1.f, 0};
         b->graph_ok = true;
     }
@@ -1667,7 +1677,7 @@ static int prepare_steps(qie_batch* b, int n_steps, const char* who) {
         int64_t need = 0;
         for (int m = 0; m < b->B; m++)
             if (!b->idle[m])
-                need += std::max<int64_t>(0, (b->h_pos[m] + n_steps + b->page_tokens - 1) / b->page_tokens - b->held[m]);
+                need += std::max<int64_t>(0, pages_missing(b, m, b->h_pos[m] + n_steps));
         QIE_REQUIRE(need <= (int64_t)b->free_pages.size(), "%s: KV pool exhausted (%lld pages needed, %zu free)", who,
                     (long long)need, b->free_pages.size());
         for (int m = 0; m < b->B; m++)
@@ -1832,8 +1842,10 @@ static int enqueue_verify(qie_batch* b, int seq, int M, const qie_sampling* smp)
                       b->d_pos, b->d_step, (uint4*)b->v.x, b->v.pos, b->v.step};
     QIE_TRY(launch_verify_rows(ra, st));
     const qie_kv_cache cache = batch_cache(b, seq);
-    const LayerRows r{M, b->v.x, b->v.xn, b->v.qkv, b->v.att, b->v.h, b->v.part};
-    for (int l = 0; l < s.n_layers; l++) QIE_TRY(enqueue_layer_verify(b, l, r, cache));
+    // the M rows of ONE sequence at consecutive positions v.pos, in the decode input form
+    const LayerRows r{M, b->v.x, b->v.xn, b->v.qkv, b->v.q, b->v.att, b->v.h, b->v.part, b->v.pos, M};
+    for (int l = 0; l < s.n_layers; l++)
+        QIE_TRY(enqueue_layer_rows(b, l, r, decode_path(e), cache, qie_attention_extend, b->v.attn_ws));
     QIE_TRY(enqueue_head_rows(b, b->v.x, s.hidden, M, smp, verify_head(b)));
     const bool greedy = is_greedy(smp);
     VerifyCommitArgs ca{seq, M, greedy ? b->v.keys : nullptr, b->v.ids, b->v.draft, s.vocab, b->d_pos, b->d_step,
@@ -1857,19 +1869,8 @@ static int launch_verify(qie_batch* b, int seq, int M, const qie_sampling* smp) 
         hipGraphExecDestroy(b->v_graphs.front().exec);
         b->v_graphs.erase(b->v_graphs.begin());
     }
-    hipGraph_t g = nullptr;
-    QIE_HIP(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-    const int rc = enqueue_verify(b, seq, M, smp);
-    const hipError_t he = hipStreamEndCapture(e->stream, &g);
-    if (rc) {
-        if (g) hipGraphDestroy(g);
-        return rc;
-    }
-    if (he != hipSuccess) return fail((int)he, "qie_verify: graph capture: %s", hipGetErrorString(he));
     hipGraphExec_t exec = nullptr;
-    const hipError_t hi = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
-    hipGraphDestroy(g);
-    if (hi != hipSuccess) return fail((int)hi, "qie_verify: graph instantiate: %s", hipGetErrorString(hi));
+    QIE_TRY(capture_graph(e, "qie_verify: ", [&] { return enqueue_verify(b, seq, M, smp); }, &exec));
     b->v_graphs.push_back({seq, M, greedy, smp ? *smp : qie_sampling{1, 0.f, 1.f, 0}, exec});
     QIE_HIP(hipGraphLaunch(exec, e->stream));
     return 0;
@@ -1894,12 +1895,10 @@ int qie_verify(qie_batch* b, int32_t seq, const int32_t* draft, int32_t n_draft,
     const int p = b->h_pos[seq], M = n_draft + 1;
     QIE_REQUIRE((int64_t)p + n_draft + 1 < b->max_ctx, "qie_verify: %d rows from position %d do not fit max_ctx %d", M,
                 p, b->max_ctx);
-    if (b->d_table) {   // all-or-nothing, before anything is allocated or launched
-        const int64_t need = ((int64_t)p + M + b->page_tokens - 1) / b->page_tokens - b->held[seq];
-        if (need > (int64_t)b->free_pages.size())
-            return fail(-28, "qie_verify: KV pool exhausted (%lld more pages needed for %d rows at position %d, %zu free)",
-                        (long long)need, M, p, b->free_pages.size());
-    }
+    const int64_t need = pages_missing(b, seq, (int64_t)p + M);   // all-or-nothing, before anything is allocated or launched
+    if (need > (int64_t)b->free_pages.size())
+        return fail(-28, "qie_verify: KV pool exhausted (%lld more pages needed for %d rows at position %d, %zu free)",
+                    (long long)need, M, p, b->free_pages.size());
     QIE_TRY(ensure_verify_bufs(b));
     QIE_TRY(ensure_pages(b, seq, (int64_t)p + M));
     QIE_TRY(flush_table(b));
@@ -1908,15 +1907,7 @@ int qie_verify(qie_batch* b, int32_t seq, const int32_t* draft, int32_t n_draft,
     QIE_TRY(launch_verify(b, seq, M, smp));
     // the accepted count and the ids (and the exchange error word) in one stream-ordered batch
     int32_t res[kVerifyMaxRows + 1] = {0};
-    QIE_HIP(hipMemcpyAsync(res, b->v.res, (size_t)(M + 1) * 4, hipMemcpyDeviceToHost, st));
-    const unsigned* ew = use_comm(e) ? e->comm->error_word() : nullptr;
-    unsigned err = 0;
-    if (ew) QIE_HIP(hipMemcpyAsync(&err, ew, sizeof(err), hipMemcpyDeviceToHost, st));
-    QIE_HIP(hipStreamSynchronize(st));
-    if (ew && err)
-        return fail(-7, "qie_verify: tensor-parallel exchange failed on the device (error word %u: a peer rank did not "
-                        "arrive within the bounded wait); the communicator is unusable", err);
-    if (!ew) QIE_TRY(comm_check(e, "qie_verify"));
+    QIE_TRY(read_back(b, res, b->v.res, (size_t)(M + 1) * 4, "qie_verify"));
     const int n = res[0];
     if (n < 1 || n > M) return fail(-5, "qie_verify: the step reported %d accepted rows of %d", n, M);
     for (int i = 0; i < n; i++) out_ids[i] = res[1 + i];
@@ -2123,77 +2114,47 @@ int qie_batch_time_kernel(qie_batch* b, int32_t which, int32_t iters, double* av
     QIE_TRY(dmalloc((void**)&scratch,
                     (size_t)B * std::max<int64_t>(std::max(I, V), QD + 2 * KD) * 2 + B * 8 + 64));
     const double wb = e->fp8 ? 1.0 : 2.0;   // weight bytes per element (fp8 row scales: negligible)
-    const bool batched_norm = B >= 2 && dev_env("QIE_PRENORM", 1) != 0;
-    auto args_for = [&](int l, double* by) {
-        const qie_layer_weights& L = e->layers[l];
-        qie_linear_args a = which == 4 ? lin_base(e) : lin_proj(e);
-        if (which == 4 && e->fp8_t16_head) a.flags |= QIE_LINEAR_FP8_T16;
-        if (which == 0) {
-            a.x = b->x_res; a.ldx = H; a.w[0] = L.w_gate; a.w[1] = L.w_up; a.seg_rows[0] = I; a.seg_rows[1] = I;
-            a.M = B; a.K = H; a.N = I; a.y = scratch; a.ldy = I; a.epilogue = QIE_EPI_SWIGLU;
-            a.norm_w = L.ffn_norm; a.norm_eps = s.rms_eps; a.numerics = s.numerics;
-            *by = 2.0 * I * H * wb + B * H * 2 + H * 2 + B * I * 2;
-        } else if (which == 1) {
-            a.x = b->h; a.ldx = I; a.w[0] = L.w_down; a.seg_rows[0] = H;
-            a.M = B; a.K = I; a.N = H; a.y = scratch; a.ldy = H; a.epilogue = QIE_EPI_STORE;
-            *by = (double)H * I * wb + B * I * 2 + B * H * 2;
-        } else if (which == 2) {
-            a.x = b->x_res; a.ldx = H; a.w[0] = L.wq; a.w[1] = L.wk; a.w[2] = L.wv;
-            a.bias[0] = L.bq; a.bias[1] = L.bk; a.bias[2] = L.bv;
-            a.seg_rows[0] = QD; a.seg_rows[1] = KD; a.seg_rows[2] = KD;
-            a.M = B; a.K = H; a.N = QD + 2 * KD; a.y = scratch; a.ldy = QD + 2 * KD; a.epilogue = QIE_EPI_STORE;
-            a.norm_w = L.attn_norm; a.norm_eps = s.rms_eps; a.numerics = s.numerics;
-            *by = (double)(QD + 2 * KD) * H * wb + B * H * 2 + B * (QD + 2 * KD) * 2;
-        } else if (which == 3) {
-            a.x = b->att; a.ldx = QD; a.w[0] = L.wo; a.seg_rows[0] = H;
-            a.M = B; a.K = QD; a.N = H; a.y = scratch; a.ldy = H; a.epilogue = QIE_EPI_STORE;
-            *by = (double)H * QD * wb + B * QD * 2 + B * H * 2;
-        } else if (which == 4) {
-            a.x = b->x_res; a.ldx = H; a.w[0] = e->w.lm_head; a.seg_rows[0] = V;
-            a.M = B; a.K = H; a.N = V; a.y = scratch; a.ldy = V; a.epilogue = QIE_EPI_STORE;
-            a.norm_w = e->w.final_norm; a.norm_eps = s.rms_eps; a.numerics = s.numerics;
-            a.argmax_keys = (uint64_t*)(((uintptr_t)(scratch + B * V) + 7) & ~(uintptr_t)7);   // as the greedy step runs it
-            *by = (double)V * H * wb + B * H * 2 + B * (double)V * 2;
-        }
-        // as prenorm() decides for the real step: the fp8 batched-decode kernel keeps its fused norm
-        const bool fused8 = dec8_applies(&a) && dev_env("QIE_DEC8_PRENORM", 0) == 0;
-        if (batched_norm && a.norm_w && !fused8) {
-            a.x = b->xn;   // as the batched step runs it: rows normed once by prenorm(), plain GEMV
-            a.ldx = a.K;
-            a.norm_w = nullptr;
-        }
-        return a;
-    };
     double by = 0;
-    if (which == 5) {
-        std::vector<int32_t> pos(B);
-        QIE_HIP(d2h(e, pos.data(), b->d_pos, B * 4));
-        for (int m = 0; m < B; m++) by += (double)(pos[m] + 1) * KD * 2 * 2;
-        by += (double)B * QD * 2 * 2;
-    }
-    const qie_kv_cache cache = batch_cache(b, 0);
-    const int nl = s.n_layers;
-    auto layer_of = [&](int i) { return which == 4 || nl == 1 ? 0 : 1 + i % (nl - 1); };
-    auto run = [&](int i) -> int {
-        const int l = layer_of(i);
-        const qie_layer_weights& L = e->layers[l];
-        const bool rp = rope_in_projection(b);
-        if (which == 5) {
-            set_decode_rope_cur(b->d_rope_cur);
-            const int rc = qie_attention_decode(b->qkv, B, b->d_pos, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin,
-                                                sh.nq, &cache, l, s.rms_eps, s.numerics | (rp ? QIE_ATTN_PREROPED : 0),
-                                                scratch, b->dec_ws, e->stream);
-            set_decode_rope_cur(nullptr);
-            return rc;
+    switch (which) {
+        case 0: by = 2.0 * I * H * wb + B * H * 2 + H * 2 + B * I * 2; break;
+        case 1: by = (double)H * I * wb + B * I * 2 + B * H * 2; break;
+        case 2: by = (double)(QD + 2 * KD) * H * wb + B * H * 2 + B * (QD + 2 * KD) * 2; break;
+        case 3: by = (double)H * QD * wb + B * QD * 2 + B * H * 2; break;
+        case 4: by = (double)V * H * wb + B * H * 2 + B * (double)V * 2; break;
+        default: {
+            std::vector<int32_t> pos(B);
+            QIE_HIP(d2h(e, pos.data(), b->d_pos, B * 4));
+            for (int m = 0; m < B; m++) by += (double)(pos[m] + 1) * KD * 2 * 2;
+            by += (double)B * QD * 2 * 2;
         }
-        double lb = 0;
-        qie_linear_args a = args_for(l, &lb);
-        LinearExtras ex;
-        if (which == 2 && rp)   // as the step runs it
-            ex.rope = RopeArgs{b->d_pos, e->rope_cos, e->rope_sin, (int)s.head_dim, QD + KD};
-        return linear(&a, ex, e->stream);
+    }
+    // the step's own rows and launches (the builders, prenorm()'s decision, the step's extras),
+    // with every output in scratch: gate/up and QKV through their rows, O and down as plain
+    // stores (the residual stream stays untouched), the head with its arg-max keys behind its logits
+    LayerRows r = decode_rows(b);
+    if (which == 0) r.h = scratch;
+    if (which == 2) r.qkv = scratch;
+    HeadBufs hb = batch_head(b, 0);
+    hb.logits = scratch;
+    hb.keys = (unsigned long long*)(((uintptr_t)(scratch + B * V) + 7) & ~(uintptr_t)7);
+    const LayerPath p = decode_path(e);
+    const int nl = s.n_layers;
+    auto run = [&](int i) -> int {
+        const int l = which == 4 || nl == 1 ? 0 : 1 + i % (nl - 1);
+        if (which == 5) return attend_decode(b, l, scratch);
+        const qie_layer_weights& L = p.layers[l];
+        qie_linear_args a = which == 0   ? gate_up_args(e, L, p.flags, r)
+                            : which == 1 ? down_args(e, L, p.flags, r)
+                            : which == 2 ? qkv_args(e, L, p.flags, r)
+                            : which == 3 ? o_args(e, L, p.flags, r)
+                                         : head_args(e, b->x_res, H, (int)B, true, hb);
+        if (which == 1 || which == 3) {
+            a.y = scratch;
+            a.epilogue = QIE_EPI_STORE;
+        }
+        if (prenorm_applies(a)) take_normed(a, b->xn);   // rows normed by the step's own prenorm(): no norm launch here
+        return linear(&a, which == 2 ? decode_qkv_extras(b) : LinearExtras{}, e->stream);
     };
-    if (which != 5) args_for(0, &by);
     hipEvent_t t0, t1;
     QIE_HIP(hipEventCreate(&t0));
     QIE_HIP(hipEventCreate(&t1));

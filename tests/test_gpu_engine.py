@@ -132,6 +132,43 @@ def test_graph_equals_eager_and_batch_equals_single(oracle):
     assert np.array_equal(outs[True][1], outs[False][1])
 
 
+def test_time_kernel_leaves_the_step_alone_and_counts_its_bytes():
+    """qie_batch_time_kernel (bench.py --full's per-kernel timing) between decode steps: its
+    launches write scratch only, so the steps around it give the ids and logits of the same run
+    without it, bit for bit; and every `bytes` it returns is the traffic of that projection at
+    these shapes (bf16: weights once, the B input rows, the norm weight where the launch norms,
+    the B output rows; attention: K and V of each slot's context, q in and out)."""
+    spec = CONFIGS["qwen2-bias-hd64"]
+    B, P = 2, (7, 11)
+    prompts = [list(rng(i).integers(0, spec.vocab, n)) for i, n in enumerate(P)]
+    H, I, V = spec.hidden, spec.ffn, spec.vocab
+    QD, KD = spec.n_heads * spec.head_dim, spec.n_kv_heads * spec.head_dim
+    want_bytes = [
+        2.0 * I * H * 2 + B * H * 2 + H * 2 + B * I * 2,                    # 0 gate/up
+        float(H * I * 2 + B * I * 2 + B * H * 2),                            # 1 down
+        float((QD + 2 * KD) * H * 2 + B * H * 2 + B * (QD + 2 * KD) * 2),    # 2 QKV
+        float(H * QD * 2 + B * QD * 2 + B * H * 2),                          # 3 O
+        float(V * H * 2 + B * H * 2 + B * V * 2),                            # 4 lm_head
+        float(sum((p + 2 + 1) * KD * 2 * 2 for p in P) + B * QD * 2 * 2),    # 5 attention, 2 steps after the prompts
+    ]
+    runs = []
+    for timed in (False, True):
+        eng = Q.Engine(spec, max_ctx=64).init_synthetic(SYN)
+        b = eng.batch(B, 64)
+        for i, pr in enumerate(prompts):
+            b.prefill(i, pr)
+        ids = [b.decode_step() for _ in range(2)]
+        if timed:
+            got_bytes = [b.time_kernel(which, 2)[1] for which in range(6)]
+        ids += [b.decode_step() for _ in range(2)]
+        runs.append((ids, b.logits()))
+        b.close()
+        eng.close()
+    assert runs[0][0] == runs[1][0]
+    assert np.array_equal(runs[0][1], runs[1][1])
+    assert got_bytes == want_bytes
+
+
 def test_weights_bin_loader_equals_synthetic(oracle, tmp_path):
     spec = CONFIGS["qwen3-qknorm-hd128"]
     hw = W.HostWeights.synthetic(spec, SYN)

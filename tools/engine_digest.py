@@ -1,0 +1,192 @@
+#!/usr/bin/env python3
+"""The engine's outputs per host path (tools/gemm_digest.py compares two LIBRARIES kernel by
+kernel; this does it for engine.hip's orchestration): run it once per build, selected by QIE_LIB,
+and diff the two outputs — a host-only change to the engine must reproduce every line.  One JSON
+line per case: the generated ids and a SHA-256 of every step's logits (qie_batch_logits;
+qie_verify_logits for a verify step).
+
+Cases (tests/test_gpu_engine.py's tiny CONFIGS, synthetic weights, fixed seeds):
+  * bf16 prefill (P = 5: split attention at <= 8 rows; P = 40: MFMA flash attention) + 4 decode
+    steps, graph and eager, B = 1 and B = 2 (the pre-normed rows);
+  * qie_prefill_batch: 3 prompts into slots 1-3 of 4, contiguous and paged (128-token pages);
+  * qie_prefill_append: (P0, n) = (5, 37) and (40, 9);
+  * qie_verify: 0, 7 and 15 drafts, greedy and top-k sampled, graph and eager, each step twice
+    (capture, then replay);
+  * fp8 weights, on a CONFIGS model (its widths keep the plain layout: fp8_t16 off) and on a tiny
+    model whose widths take the 16-row tiled layout (K = 896 / 2,048: the batched-decode kernel
+    reads every projection): P = 5 (fp8 codes), P = 23 (tiled: the dequantised copy), P = 300
+    (>= 256 rows: the dequantised copy), 4 decode steps at B = 8 (the batched-decode kernel's
+    fused norm where it applies), verify with 7 drafts;
+  * prefill_fp8: tests/test_gpu_fp8_mx.py's test_engine_prefill_fp8_batched_tiny configuration;
+  * comm_always at world size 1 (the exchange form of the row-parallel projections, the
+    gathered head): prefill, 4 decode steps, verify with 7 drafts, greedy and sampled;
+  * qie_batch_debug_step: a hash of the residual snapshots."""
+import hashlib
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import qwen_inference_engine_amd as Q  # noqa: E402
+from qwen_inference_engine_amd import spec as S, weights as W  # noqa: E402
+
+CONFIGS = {
+    "qwen2-bias-hd64": S.tiny("t-q2", n_layers=3, hidden=256, n_heads=4, n_kv_heads=2, head_dim=64, ffn=512,
+                              vocab=1000, bias=True),
+    "qwen3-qknorm-hd128": S.tiny("t-q3", n_layers=2, hidden=512, n_heads=8, n_kv_heads=2, head_dim=128, ffn=768,
+                                 vocab=1536, bias=False, qk_norm=True),
+    "tied-g7": S.tiny("t-tied", n_layers=2, hidden=448, n_heads=7, n_kv_heads=1, head_dim=64, ffn=640,
+                      vocab=777 * 2, tie=True, bias=True),
+}
+TILED = S.tiny("t-t16", n_layers=2, hidden=896, n_heads=14, n_kv_heads=2, head_dim=64, ffn=2048, vocab=1024, bias=True)
+MX = S.tiny("t-mx", n_layers=2, hidden=256, n_heads=4, n_kv_heads=2, head_dim=64, ffn=512, vocab=1024, bias=True)
+SYN = W.SynthParams(seed=11, w_scale=0.08, norm_scale=0.25, bias_scale=0.05)
+SAMPLED = Q.Sampling(top_k=40, temperature=0.8, top_p=0.9, seed=99)
+
+
+def ids(spec, seed, n):
+    return [int(t) for t in np.random.default_rng(seed).integers(0, spec.vocab, n)]
+
+
+def sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+class Case:
+    """Collects what one case generates; prints it as one line."""
+
+    def __init__(self, name):
+        self.rec = {"case": name, "ids": [], "logits": []}
+
+    def took(self, toks, b, rows=None):
+        """rows: the slots whose logits this step wrote (default: all of the batch)"""
+        self.rec["ids"].append([int(t) for t in np.atleast_1d(toks)])
+        self.rec["logits"].append(sha(b.logits()[rows if rows is not None else slice(None)]))
+
+    def decode(self, b, n, smp=Q.GREEDY, rows=None):
+        for _ in range(n):
+            self.took(b.decode_step(smp), b, rows)
+
+    def verify(self, b, seq, draft, smp):
+        self.rec["ids"].append(b.verify(seq, draft, smp))
+        self.rec["logits"].append(sha(b.verify_logits()))
+
+    def done(self, b=None):
+        print(json.dumps(self.rec), flush=True)
+        if b is not None:
+            b.close()
+
+
+def drafts(b_twin, spec, n, smp):
+    """n drafts for a sequence in the twin batch's state: its own next tokens, one of them wrong."""
+    if n == 0:
+        return []
+    d = [int(b_twin.decode_step(smp)[0]) for _ in range(n)]
+    d[n // 2] = (d[n // 2] + 1) % spec.vocab
+    return d
+
+
+def verify_cases(tag, eng, spec, counts, samplings, P=12):
+    for n in counts:
+        for sn, smp in samplings:
+            c = Case(f"{tag}_verify{n}_{sn}")
+            b, twin = eng.batch(1, eng.max_ctx), eng.batch(1, eng.max_ctx)
+            prompt = ids(spec, 31, P)
+            c.took(b.prefill(0, prompt, smp), b)
+            twin.prefill(0, prompt, smp)
+            d = drafts(twin, spec, n, smp)
+            c.verify(b, 0, d, smp)                                  # captures (graph engines)
+            c.verify(b, 0, ids(spec, 32, n), smp)                   # replays; junk drafts
+            c.took(b.decode_step(smp), b)
+            twin.close()
+            c.done(b)
+
+
+def main():
+    # bf16: prefill + decode, prefill_batch, append, verify, debug step
+    for name, spec in CONFIGS.items():
+        for graph in (True, False):
+            g = "graph" if graph else "eager"
+            eng = Q.Engine(spec, max_ctx=128, use_graph=graph).init_synthetic(SYN)
+            for P in (5, 40):
+                for B in (1, 2):
+                    c = Case(f"bf16_{name}_{g}_P{P}_B{B}")
+                    b = eng.batch(B, 128)
+                    for i in range(B):
+                        c.took(b.prefill(i, ids(spec, 1 + i, P)), b, slice(0, i + 1))
+                    c.decode(b, 4)
+                    c.done(b)
+            verify_cases(f"bf16_{name}_{g}", eng, spec, (0, 7, 15), (("greedy", Q.GREEDY), ("sampled", SAMPLED)))
+            if graph:
+                for paged in (False, True):
+                    for L in (5, 40):
+                        c = Case(f"bf16_{name}_prefill_batch_L{L}_{'paged' if paged else 'contig'}")
+                        b = eng.batch(4, 128, page_tokens=128 if paged else None)
+                        c.took(b.prefill_batch(1, [ids(spec, 10 + i, L) for i in range(3)]), b, slice(1, 4))
+                        c.decode(b, 2, rows=slice(1, 4))
+                        c.done(b)
+                    for P0, n in ((5, 37), (40, 9)):
+                        c = Case(f"bf16_{name}_append_{P0}_{n}_{'paged' if paged else 'contig'}")
+                        b = eng.batch(1, 128, page_tokens=128 if paged else None)
+                        c.took(b.prefill(0, ids(spec, 20, P0)), b)
+                        c.took(b.append(0, ids(spec, 21, n), P0), b)
+                        c.decode(b, 2)
+                        c.done(b)
+                c = Case(f"bf16_{name}_debug_step")
+                b = eng.batch(2, 128)
+                for i in range(2):
+                    c.took(b.prefill(i, ids(spec, 1 + i, 9)), b, slice(0, i + 1))
+                toks, xs = b.debug_step()
+                c.took(toks, b)
+                c.rec["residuals"] = sha(xs)
+                c.done(b)
+            eng.close()
+    # fp8 weights: plain layout (a CONFIGS model) and the tiled layout
+    for tag, spec in (("fp8_plain", CONFIGS["qwen2-bias-hd64"]), ("fp8_tiled", TILED)):
+        eng = Q.Engine(spec, max_ctx=384, weight_fp8=True).init_synthetic(SYN)
+        for P in (5, 23, 300):
+            c = Case(f"{tag}_P{P}")
+            b = eng.batch(1, 384)
+            c.took(b.prefill(0, ids(spec, 40, P)), b)
+            c.decode(b, 4)
+            c.done(b)
+        c = Case(f"{tag}_B8")
+        b = eng.batch(8, 384)
+        for i in range(8):
+            c.took(b.prefill(i, ids(spec, 50 + i, 5)), b, slice(0, i + 1))
+        c.decode(b, 4)
+        c.done(b)
+        verify_cases(tag, eng, spec, (7,), (("greedy", Q.GREEDY),))
+        eng.close()
+    # prefill_fp8
+    eng = Q.Engine(MX, max_ctx=96, weight_fp8=True, prefill_fp8=True).init_synthetic(SYN)
+    c = Case("prefill_fp8_batched")
+    b = eng.batch(4, 96)
+    c.took(b.prefill_batch(0, [ids(MX, 50 + i, 70) for i in range(4)]), b)
+    c.decode(b, 6)
+    c.done(b)
+    eng.close()
+    # the exchange path at world size 1
+    spec = CONFIGS["qwen2-bias-hd64"]
+    comm = Q.Comm.rccl(Q.Comm.unique_id(), 1, 0, 0)
+    for graph in (True, False):
+        g = "graph" if graph else "eager"
+        eng = Q.Engine(spec, max_ctx=128, use_graph=graph, comm=comm, comm_always=True).init_synthetic(SYN)
+        for sn, smp in (("greedy", Q.GREEDY), ("sampled", SAMPLED)):
+            for P in (5, 40):
+                c = Case(f"comm_{g}_{sn}_P{P}")
+                b = eng.batch(2, 128)
+                for i in range(2):
+                    c.took(b.prefill(i, ids(spec, 1 + i, P), smp), b, slice(0, i + 1))
+                c.decode(b, 4, smp)
+                c.done(b)
+            verify_cases(f"comm_{g}", eng, spec, (7,), ((sn, smp),))
+        eng.close()
+    comm.close()
+
+
+if __name__ == "__main__":
+    main()
