@@ -461,7 +461,11 @@ __device__ __forceinline__ bool attn_decode_mfma2_body(const DecodeAttnParams& a
                 const int c = lane + 64 * i;
                 const int r = c / CPW, ch = c % CPW;
                 const uint4 vn = *reinterpret_cast<const uint4*>(&kv_new[1][wave * DW + ch * 8]);
-                vr[i] = sel4(kb0 + r == p, vn, vr[i]);
+                // >= p, not == p: the rows past the context re-read row `last` = p of the cache,
+                // loaded before this launch's append lands — whatever bits the cache held there
+                // (NaN bits gave 0 * NaN = NaN in P.V).  They take the new row too: P = 0 there,
+                // and 0 times a finite row is the same 0 a finite stale row gave
+                vr[i] = sel4(kb0 + r >= p, vn, vr[i]);
             }
         }
         // ---- S^T for this wave's 32 keys -> LDS (raw dots)
