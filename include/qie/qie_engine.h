@@ -192,6 +192,32 @@ int qie_prefill_batch(qie_batch* b, int32_t seq0, int32_t n_seqs, const int32_t*
  * numerics are defined for a prefill from position 0 only. */
 int qie_prefill_append(qie_batch* b, int32_t seq, const int32_t* ids, int32_t n, int32_t pos0,
                        const qie_sampling* s, int32_t* next_id);
+/* Scoring: the log-probability of a given text (numerics contract in qie_ops.h,
+ * "scoring").  qie_score IS qie_prefill (pos0 == 0) or qie_prefill_append (pos0 >= 1) of the n
+ * ids in every effect on the sequence — KV rows, pages, history, position, the current token, the
+ * step counter, qie_batch_logits row `seq`, *next_id, the error codes and the all-or-nothing
+ * rules are those of the plain call, bit for bit (the same launches run; the scoring head is
+ * added after them).  In addition every row i is scored: logprobs[i] (host [n]) = the log-
+ * probability the model gives targets[i] (host [n], a token id, or -1 for "none": 0.0f) as the
+ * token after ids[0..i], and greedy_ids[i] (host [n], may be NULL) = the arg-max of row i's logits
+ * under the reference tie rule.  A target outside [-1, V) returns -22 before anything is launched.
+ * One sequence per call; the call synchronises; collective under tensor parallelism.
+ * Head path: a bf16 head with hidden % 64 == 0 and hidden >= 256 on a single-rank engine runs the
+ * fused qie_score_rows (no logit row is materialised); fp8 heads, engines on the exchange path
+ * and flags = QIE_SCORE_UNFUSED run rows [0, n - 1) in pieces of <= 16 through the head launch of
+ * decode and qie_verify (their logits, bit for bit) and qie_logprob_rows, and take row n - 1 from
+ * the logits the prefill's own head wrote (qie_batch_logits row `seq`).  That path uses the verify
+ * step's logit rows: qie_verify_logits afterwards needs a new qie_verify.  prefill_fp8 engines
+ * score at pos0 == 0 (the head reads bf16 rows there, as it does in qie_prefill). */
+#define QIE_SCORE_UNFUSED 1
+int qie_score(qie_batch* b, int32_t seq, const int32_t* ids, int32_t n, int32_t pos0,
+              const int32_t* targets, const qie_sampling* s, int32_t flags, float* logprobs,
+              int32_t* greedy_ids, int32_t* next_id);
+/* Log-probability of ids[m] (host [B]; -1 = skip: 0.0f) under the logits qie_batch_logits would
+ * return for slot m: out host float [B].  Runs qie_logprob_rows on the engine's stream, outside
+ * any captured graph; no [B][V] host copy.  Works wherever qie_batch_logits does (collective
+ * under tensor parallelism). */
+int qie_batch_logprobs(qie_batch* b, const int32_t* ids, float* out);
 /* Speculative decoding: verify up to QIE_VERIFY_MAX_ROWS - 1 drafted tokens in one weight pass
  * (DESIGN.md §16).  `seq` is a live slot of any batch (contiguous or paged, any B) at position
  * p with a pending current token c; draft holds 0 <= n_draft <= 15 ids d1 .. dn (host).  One

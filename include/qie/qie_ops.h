@@ -247,6 +247,32 @@ int qie_sample(const void* logits, int64_t M, int64_t V, int64_t ld, const qie_s
 /* Decode fused arg-max keys (see qie_linear_args.argmax_keys) into ids. */
 int qie_keys_to_ids(const uint64_t* keys, int64_t M, int32_t* out_ids, void* stream);
 
+/* ----------------------------------------------------------------- scoring
+ * Per-token log-probabilities of the vocabulary head (the reference has no such path: its head,
+ * qwen_main.cu:224-241, samples one token from the last row).  Numerics contract (DESIGN.md
+ * §17): a row's logits are what the head defines, l[j] = bf16(fp32 acc) of x_row . W[j] in some
+ * valid fp32 summation order; everything after that is fp32 arithmetic on those bf16 values,
+ *     lse = m + logf(sum_j expf(l[j] - m)),  m = max_j l[j],     logprob(t) = l[t] - lse;
+ * the row's greedy id is the maximum selection key (the reference tie rule of qie_sample).  No
+ * float atomics: partial sums are merged in a fixed index order, so two runs are bit-identical.
+ * No kernel waits on another workgroup.  Neither op allocates or synchronises.
+ *
+ * qie_logprob_rows: over M materialised bf16 logit rows [M][ld] (ld >= V, V < 2^24), one
+ *   workgroup per row.  logprobs[m] = l[targets[m]] - lse, or 0.0f where targets[m] is -1
+ *   (or outside [0, V)); ids[m] (ids_dev may be NULL) = the reference-rule arg-max.
+ * qie_score_rows: the fused form for x bf16 [M, K] (already normed, row stride ldx, ldx % 8 == 0)
+ *   and W bf16 [V, K], both 16-byte aligned; K % 64 == 0 and K >= 256, any M >= 1, any
+ *   1 <= V < 2^24 (anything else: -22).  One workgroup per 256 x 256 tile runs the prefill GEMM's
+ *   tile pipeline and reduces its rounded accumulators to one {max, sum exp} pair and one key per
+ *   (column tile, row) in ws; a second launch merges the column tiles of each row in index order.
+ *   Nothing of size M x V is written.  ws must hold qie_score_rows_workspace_bytes(M, V) bytes
+ *   (8-byte aligned) and need not be initialised. */
+int qie_logprob_rows(const void* logits, int64_t M, int64_t V, int64_t ld, const int32_t* targets_dev,
+                     float* logprobs_dev, int32_t* ids_dev, void* stream);
+int64_t qie_score_rows_workspace_bytes(int64_t M, int64_t V);
+int qie_score_rows(const void* x, int64_t ldx, const void* W, int64_t M, int64_t K, int64_t V,
+                   const int32_t* targets_dev, float* logprobs_dev, int32_t* ids_dev, void* ws, void* stream);
+
 /* ------------------------------------------------------- synthetic weights
  * Deterministic counter-based fill used for synthetic checkpoints (no weights
  * ship in this environment): element i of tensor `tensor_id` is

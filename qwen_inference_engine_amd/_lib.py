@@ -28,6 +28,7 @@ QIE_LINEAR_FP8_T16 = 16
 QIE_LINEAR_ACT_FP8 = 32
 QIE_ATTN_PREROPED = 0x100   # qie_attention_decode numerics flag: q / new k arrive rotated
 QIE_VERIFY_MAX_ROWS = 16    # qie_verify: the current token + at most 15 drafts
+QIE_SCORE_UNFUSED = 1       # qie_score flag: the <= 16-row head launches + qie_logprob_rows
 QIE_COMM_ID_BYTES = 128
 QIE_COMM_PEER_HANDLE_BYTES = 128
 
@@ -133,6 +134,9 @@ SIGNATURES = [
     ("qie_sample_workspace_bytes", C.c_int64, [_I64, _I64]),
     ("qie_sample", C.c_int, [_P, _I64, _I64, _I64, C.POINTER(SamplingC), _P, _P, _P, _P]),
     ("qie_keys_to_ids", C.c_int, [_P, _I64, _P, _P]),
+    ("qie_logprob_rows", C.c_int, [_P, _I64, _I64, _I64, _P, _P, _P, _P]),
+    ("qie_score_rows_workspace_bytes", C.c_int64, [_I64, _I64]),
+    ("qie_score_rows", C.c_int, [_P, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
     ("qie_tensor_id", C.c_uint32, [C.c_char_p]),
     ("qie_synthetic_fill", C.c_int, [_P, _I64, _U32, _U64, _F, _F, _P]),
     ("qie_synthetic_fill_host", C.c_int, [_P, _I64, _U32, _U64, _F, _F]),
@@ -186,6 +190,8 @@ SIGNATURES = [
     ("qie_prefill", C.c_int, [_P, _I32, _PI32, _I32, C.POINTER(SamplingC), _PI32]),
     ("qie_prefill_batch", C.c_int, [_P, _I32, _I32, _PI32, _I32, C.POINTER(SamplingC), _PI32]),
     ("qie_prefill_append", C.c_int, [_P, _I32, _PI32, _I32, _I32, C.POINTER(SamplingC), _PI32]),
+    ("qie_score", C.c_int, [_P, _I32, _PI32, _I32, _I32, _PI32, C.POINTER(SamplingC), _I32, _PF, _PI32, _PI32]),
+    ("qie_batch_logprobs", C.c_int, [_P, _PI32, _PF]),
     ("qie_verify", C.c_int, [_P, _I32, _PI32, _I32, C.POINTER(SamplingC), _PI32, _PI32]),
     ("qie_verify_logits", C.c_int, [_P, _P]),
     ("qie_decode_step", C.c_int, [_P, C.POINTER(SamplingC), _PI32]),

@@ -187,6 +187,14 @@ struct qie_batch {
     };
     std::vector<VerifyGraph> v_graphs;
     int v_rows = 0;   // rows of the last qie_verify (what qie_verify_logits returns)
+    // scoring (qie_score, qie_batch_logprobs): device targets, log-probabilities and
+    // greedy ids of `rows` rows, and the fused head's workspace; grown before any launch
+    struct ScoreBufs {
+        int64_t rows = 0, ws_bytes = 0;
+        int32_t *tgt = nullptr, *ids = nullptr;
+        float* lp = nullptr;
+        void* ws = nullptr;
+    } sc;
 };
 
 namespace qie {
@@ -1481,10 +1489,90 @@ void qie_batch_destroy(qie_batch* b) {
     void* ps[] = {b->kc, b->vc, b->d_table, b->d_pos, b->d_rope_cur, b->d_step, b->d_hist, b->d_ids, b->d_keys, b->x_res, b->qkv, b->q,
                   b->att, b->h, b->logits, b->attn_ws, b->dec_ws, b->samp_ws, b->pf_x, b->pf_hn, b->pf_qkv, b->pf_q,
                   b->pf_att, b->pf_h, b->pf_pos, b->pf_ids, b->pf_attn_ws, b->part, b->logits_full,
-                  b->gather_tmp, b->pf_part, b->xn, b->pf_q8, b->pf_e8, b->pk_mem, b->d_layers, b->d_attp, b->pk_ts};
+                  b->gather_tmp, b->pf_part, b->xn, b->pf_q8, b->pf_e8, b->pk_mem, b->d_layers, b->d_attp, b->pk_ts,
+                  b->sc.tgt, b->sc.ids, b->sc.lp, b->sc.ws};
     for (void* p : ps)
         if (p) hipFree(p);
     delete b;
+}
+
+// ------------------------------------------------------------ scoring
+struct ScoreReq {
+    const int32_t* targets;   // host [n], each in [0, V) or -1
+    int32_t flags;            // QIE_SCORE_*
+    float* logprobs;          // host [n]
+    int32_t* greedy_ids;      // host [n] or null
+};
+
+// The fused head (qie_score_rows) reads a bf16 lm_head of the whole vocabulary
+static bool score_fused(const qie_engine* e, int flags) {
+    return !(flags & QIE_SCORE_UNFUSED) && !e->fp8 && !use_comm(e) && e->sh.tp == 1 && e->spec.hidden % 64 == 0 &&
+           e->spec.hidden >= 256;
+}
+
+static int ensure_verify_bufs(qie_batch* b);
+
+static int ensure_score_scratch(qie_batch* b, int64_t n, bool fused) {
+    qie_batch::ScoreBufs& sc = b->sc;
+    if (n > sc.rows) {
+        void** olds[] = {(void**)&sc.tgt, (void**)&sc.ids, (void**)&sc.lp};
+        for (void** p : olds) {
+            if (*p) hipFree(*p);
+            *p = nullptr;
+        }
+        sc.rows = 0;
+        QIE_TRY(dmalloc((void**)&sc.tgt, n * 4));
+        QIE_TRY(dmalloc((void**)&sc.ids, n * 4));
+        QIE_TRY(dmalloc((void**)&sc.lp, n * 4));
+        sc.rows = n;
+    }
+    const int64_t ws = fused ? qie_score_rows_workspace_bytes(n, b->e->spec.vocab) : 0;
+    if (ws > sc.ws_bytes) {
+        if (sc.ws) hipFree(sc.ws);
+        sc.ws = nullptr;
+        sc.ws_bytes = 0;
+        QIE_TRY(dmalloc(&sc.ws, (size_t)ws));
+        sc.ws_bytes = ws;
+    }
+    return 0;
+}
+
+// The scoring head over the n rows of b->pf_x a prefill of slot `seq` has just run (after its own
+// last-row head, which is left as it is).  Fused: final norm of all rows into pf_hn (free after
+// the layer loop), then qie_score_rows.  General (fp8 heads, the exchange path, QIE_SCORE_UNFUSED):
+// rows [0, n - 1) in pieces of <= kVerifyMaxRows through the head launch of decode and qie_verify
+// into the verify step's logit rows, qie_logprob_rows on each piece; row n - 1 from the batch's
+// own logit row, which the prefill's head has just written.
+static int enqueue_score(qie_batch* b, int seq, int n, const ScoreReq& rq) {
+    qie_engine* e = b->e;
+    const qie_model_spec& s = e->spec;
+    hipStream_t st = e->stream;
+    const int64_t H = s.hidden, V = s.vocab;
+    QIE_HIP(hipMemcpyAsync(b->sc.tgt, rq.targets, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    if (score_fused(e, rq.flags)) {
+        QIE_TRY(qie_rmsnorm(b->pf_x, e->w.final_norm, b->pf_hn, n, H, s.rms_eps, s.numerics, st));
+        return qie_score_rows(b->pf_hn, H, e->w.lm_head, n, H, V, b->sc.tgt, b->sc.lp, b->sc.ids, b->sc.ws, st);
+    }
+    const HeadBufs hb = verify_head(b);
+    for (int r0 = 0; r0 < n - 1; r0 += kVerifyMaxRows) {
+        const int M = std::min(kVerifyMaxRows, n - 1 - r0);
+        qie_linear_args a = head_args(e, b->pf_x + (int64_t)r0 * H, H, M, false, hb);
+        QIE_TRY(prenorm(b, a, hb.xn));
+        QIE_TRY(linear(&a, LinearExtras{}, st));
+        const uint16_t* lg = hb.logits;
+        if (use_comm(e)) {
+            QIE_TRY(gather_rows(b, hb, M));
+            lg = hb.logits_full;
+        }
+        QIE_TRY(qie_logprob_rows(lg, M, V, V, b->sc.tgt + r0, b->sc.lp + r0, b->sc.ids + r0, st));
+    }
+    b->v_rows = 0;   // the verify step's logit rows no longer hold a qie_verify's
+    const uint16_t* last = b->logits + (int64_t)seq * e->sh.vocab;
+    if (use_comm(e)) {
+        QIE_TRY(gather_logits(b, seq, 1));
+        last = b->logits_full + (int64_t)seq * V;
+    }
+    return qie_logprob_rows(last, 1, V, V, b->sc.tgt + (n - 1), b->sc.lp + (n - 1), b->sc.ids + (n - 1), st);
 }
 
 // Prefill of n_seqs prompts of len ids each into slots seq0 .. seq0+n_seqs-1 (ids laid end
@@ -1495,10 +1583,13 @@ void qie_batch_destroy(qie_batch* b) {
 // pos0 .. pos0 + len - 1 — its pages are kept and grown, the ids land at history offset pos0,
 // and attention over the cached prefix runs qie_attention_extend; everything else (the layer
 // loop, tensor parallelism, the head) is the same code.
+// score (qie_score, n_seqs = 1): after the layer loop and the unchanged last-row head, the scoring
+// head runs over all len rows (enqueue_score); everything the plain call does is done as it does it.
 static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, int len, int pos0,
-                        const qie_sampling* smp, int32_t* next_ids, const char* who) {
+                        const qie_sampling* smp, int32_t* next_ids, const char* who, const ScoreReq* score = nullptr) {
     QIE_REQUIRE(b && ids && len > 0 && n_seqs > 0 && seq0 >= 0 && seq0 + n_seqs <= b->B && pos0 >= 0,
                 "%s: bad arguments", who);
+    QIE_REQUIRE(!score || (n_seqs == 1 && score->targets && score->logprobs), "%s: bad arguments", who);
     QIE_REQUIRE((int64_t)pos0 + len < b->max_ctx, "%s: %d tokens from position %d do not fit max_ctx %d", who, len,
                 pos0, b->max_ctx);
     const bool append = pos0 > 0;
@@ -1517,6 +1608,10 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
     QIE_REQUIRE(n <= INT32_MAX, "%s: %lld rows", who, (long long)n);
     for (int64_t i = 0; i < n; i++)
         QIE_REQUIRE(ids[i] >= 0 && ids[i] < s.vocab, "%s: token id %d out of range", who, ids[i]);
+    if (score)
+        for (int64_t i = 0; i < n; i++)
+            QIE_REQUIRE(score->targets[i] >= -1 && score->targets[i] < s.vocab,
+                        "%s: target %d of row %lld is neither -1 nor a token id", who, score->targets[i], (long long)i);
     hipStream_t st = e->stream;
     if (append) {   // all-or-nothing, before anything is allocated or launched
         const int64_t need = pages_missing(b, seq0, (int64_t)pos0 + len);
@@ -1525,6 +1620,10 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
                         who, (long long)need, len, pos0, b->free_pages.size());
     }
     QIE_TRY(ensure_prefill_scratch(b, n, append));
+    if (score) {   // the scoring head's scratch too, before anything is launched
+        QIE_TRY(ensure_score_scratch(b, n, score_fused(e, score->flags)));
+        if (!score_fused(e, score->flags)) QIE_TRY(ensure_verify_bufs(b));
+    }
     if (b->d_table && !append) {   // all-or-nothing: the slots' own pages count, nothing is dropped on failure
         int64_t missing = 0, held = 0;
         for (int z = 0; z < n_seqs; z++) {
@@ -1578,9 +1677,15 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
     }
     QIE_TRY(enqueue_head(b, last, H, seq0, n_seqs, smp));
     for (int z = 0; z < n_seqs; z++) b->h_pos[seq0 + z] = pos0 + len;
+    if (score) QIE_TRY(enqueue_score(b, seq0, len, *score));
     if (next_ids) {
         QIE_HIP(hipMemcpyAsync(next_ids, b->d_ids + seq0, (size_t)n_seqs * 4, hipMemcpyDeviceToHost, st));
         QIE_HIP(hipStreamSynchronize(st));
+        QIE_TRY(comm_check(e, who));
+    }
+    if (score) {
+        QIE_HIP(d2h(e, score->logprobs, b->sc.lp, (size_t)len * 4));
+        if (score->greedy_ids) QIE_HIP(d2h(e, score->greedy_ids, b->sc.ids, (size_t)len * 4));
         QIE_TRY(comm_check(e, who));
     }
     return 0;
@@ -1599,6 +1704,35 @@ int qie_prefill_append(qie_batch* b, int32_t seq, const int32_t* ids, int32_t n,
 int qie_prefill_batch(qie_batch* b, int32_t seq0, int32_t n_seqs, const int32_t* ids, int32_t len,
                       const qie_sampling* smp, int32_t* next_ids) {
     return prefill_rows(b, seq0, n_seqs, ids, len, 0, smp, next_ids, "qie_prefill_batch");
+}
+
+int qie_score(qie_batch* b, int32_t seq, const int32_t* ids, int32_t n, int32_t pos0, const int32_t* targets,
+              const qie_sampling* smp, int32_t flags, float* logprobs, int32_t* greedy_ids, int32_t* next_id) {
+    QIE_REQUIRE(targets && logprobs && (flags & ~QIE_SCORE_UNFUSED) == 0, "qie_score: bad arguments");
+    const ScoreReq rq{targets, flags, logprobs, greedy_ids};
+    return prefill_rows(b, seq, 1, ids, n, pos0, smp, next_id, "qie_score", &rq);
+}
+
+int qie_batch_logprobs(qie_batch* b, const int32_t* ids, float* out) {
+    QIE_REQUIRE(b && ids && out, "qie_batch_logprobs: bad arguments");
+    qie_engine* e = b->e;
+    const int64_t V = e->spec.vocab;
+    for (int m = 0; m < b->B; m++)
+        QIE_REQUIRE(ids[m] >= -1 && ids[m] < V, "qie_batch_logprobs: id %d of slot %d is neither -1 nor a token id",
+                    ids[m], m);
+    QIE_TRY(ensure_score_scratch(b, b->B, false));
+    const uint16_t* src = b->logits;
+    if (use_comm(e)) {   // collective: every rank calls this at the same point
+        QIE_TRY(gather_logits(b, 0, b->B));
+        src = b->logits_full;
+    }
+    QIE_HIP(hipMemcpyAsync(b->sc.tgt, ids, (size_t)b->B * 4, hipMemcpyHostToDevice, e->stream));
+    QIE_TRY(qie_logprob_rows(src, b->B, V, V, b->sc.tgt, b->sc.lp, nullptr, e->stream));
+    QIE_HIP(hipStreamSynchronize(e->stream));
+    QIE_TRY(comm_check(e, "qie_batch_logprobs"));
+    QIE_TRY(pk_check(b));
+    QIE_HIP(d2h(e, out, b->sc.lp, (size_t)b->B * 4));
+    return 0;
 }
 
 static bool same_sampling(const qie_sampling& a, const qie_sampling* b) {

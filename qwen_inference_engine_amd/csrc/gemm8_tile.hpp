@@ -1,6 +1,7 @@
 // gemm8_tile.hpp — the phase-interleaved 256x256 GEMM tile pipeline (gemm8_kernel,
-// gemm8sk_kernel) and the split-K hand-off (those two and gemm8mx_kernel); k_gemm.hip is the
-// only includer.  gemm8mx_kernel runs the same schedule from its own copy (see there).
+// gemm8sk_kernel; k_score.hip's score_tile_kernel) and the split-K hand-off (those two and
+// gemm8mx_kernel); k_gemm.hip and k_score.hip include it.  gemm8mx_kernel runs the same schedule
+// from its own copy (see there).
 //
 // Prefill GEMM, phase-interleaved (round 4; cdna_hip_programming.md §5 "The 256² 8-phase
 // template", written for this NT layout).  256x256 block tile, BK = 64, 8 waves as 2 (M) x 4

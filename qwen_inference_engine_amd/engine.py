@@ -272,6 +272,60 @@ class Batch:
                    "qie_prefill_append")
         return out.value
 
+    def score_rows(self, seq: int, ids: Sequence[int], targets: Sequence[int], pos0: int = 0,
+                   sampling: Sampling = GREEDY, unfused: bool = False):
+        """qie_score: prefill (pos0 == 0) or append (pos0 >= 1) of `ids` that also scores every
+        row.  targets[i] is the id whose log-probability row i reports (-1: none, 0.0).  Returns
+        (logprobs float32 [n], greedy ids int32 [n], the sampled next id)."""
+        n = len(ids)
+        if len(targets) != n:
+            raise ValueError("score_rows: one target per id")
+        arr = (C.c_int32 * max(n, 1))(*[int(i) for i in ids])
+        tgt = (C.c_int32 * max(n, 1))(*[int(t) for t in targets])
+        lp = np.zeros(max(n, 1), dtype=np.float32)
+        gr = np.zeros(max(n, 1), dtype=np.int32)
+        out = C.c_int32(-1)
+        sc = sampling.to_c()
+        _lib.check(self.lib.qie_score(self.h, seq, arr, n, int(pos0), tgt, C.byref(sc),
+                                      _lib.QIE_SCORE_UNFUSED if unfused else 0,
+                                      lp.ctypes.data_as(C.POINTER(C.c_float)), gr.ctypes.data_as(C.POINTER(C.c_int32)),
+                                      C.byref(out)), "qie_score")
+        return lp[:n], gr[:n], out.value
+
+    def score(self, seq: int, ids: Sequence[int], pos0: Optional[int] = None, sampling: Sampling = GREEDY,
+              chunk: Optional[int] = None, unfused: bool = False):
+        """Score the text `ids`: starts sequence `seq` with it (pos0 None or 0, as prefill) or
+        extends the live sequence at pos0 >= 1 (as append), and returns (logprobs float32
+        [n - 1]: the log-probability of ids[i + 1] after ids[:i + 1], greedy int32 [n]: the
+        model's own arg-max after every row, next_id: the token sampled after the last id).
+        chunk: score in pieces of at most `chunk` ids, the pieces after the first through
+        append.  unfused: the <= 16-row head launches instead of the fused scoring head."""
+        from .scheduler import score_pieces
+        lps, grs, nxt = [], [], -1
+        for pos, piece, targets in score_pieces(ids, chunk, 0 if pos0 is None else int(pos0)):
+            lp, gr, nxt = self.score_rows(seq, piece, targets, pos, sampling, unfused)
+            lps.append(lp)
+            grs.append(gr)
+        return np.concatenate(lps)[:-1], np.concatenate(grs), nxt
+
+    def perplexity(self, seq: int, ids: Sequence[int], chunk: Optional[int] = None) -> float:
+        """exp(-mean log-probability) of ids[1:] given what precedes each (float64)."""
+        lp = self.score(seq, ids, chunk=chunk)[0].astype(np.float64)
+        if lp.size == 0:
+            raise ValueError("perplexity: needs at least two ids")
+        return float(np.exp(-lp.mean()))
+
+    def logprobs(self, ids: Sequence[int]) -> np.ndarray:
+        """Log-probability of ids[m] (-1: skip, 0.0) under slot m's last logits (the rows
+        logits() returns), float32 [B]; only B floats come back to the host."""
+        if len(ids) != self.B:
+            raise ValueError("logprobs: one id per slot")
+        arr = (C.c_int32 * self.B)(*[int(i) for i in ids])
+        out = np.zeros(self.B, dtype=np.float32)
+        _lib.check(self.lib.qie_batch_logprobs(self.h, arr, out.ctypes.data_as(C.POINTER(C.c_float))),
+                   "qie_batch_logprobs")
+        return out
+
     def prefill_batch(self, seq0: int, prompts: Sequence[Sequence[int]], sampling: Sampling = GREEDY) -> List[int]:
         """Equal-length prompts into slots seq0, seq0+1, ... in one pass (qie_prefill_batch)."""
         n = len(prompts)

@@ -31,6 +31,7 @@ class Request:
     stop_ids: tuple = ()
     tokens: List[int] = dataclasses.field(default_factory=list)
     logits: list = dataclasses.field(default_factory=list)   # per token, when keep_logits
+    logprobs: List[float] = dataclasses.field(default_factory=list)   # per token, when keep_logprobs
     slot: int = -1
     pages: int = 0
     done: bool = False
@@ -63,16 +64,31 @@ def prefill_chunks(n: int, chunk: Optional[int]) -> List[tuple]:
     return [(off, min(chunk, n - off)) for off in range(0, n, chunk)]
 
 
+def score_pieces(ids: Sequence[int], chunk: Optional[int] = None, pos0: int = 0) -> List[tuple]:
+    """(position, piece ids, piece targets) calls in which Batch.score scores `ids` laid at
+    positions pos0 .. pos0+n-1: the pieces of prefill_chunks, row i of the text targeting
+    ids[i + 1] — so the last row of a middle piece targets the next piece's first id — and the
+    text's last row targeting nothing (-1)."""
+    ids = [int(t) for t in ids]
+    if pos0 < 0:
+        raise ValueError("score_pieces: pos0 must be >= 0")
+    targets = ids[1:] + [-1]
+    return [(pos0 + off, ids[off:off + n], targets[off:off + n]) for off, n in prefill_chunks(len(ids), chunk)]
+
+
 class ContinuousBatcher:
     def __init__(self, engine: Engine, slots: int = 8, max_ctx: Optional[int] = None, page_tokens: int = 128,
                  n_pages: int = 0, sampling: Sampling = GREEDY, keep_logits: bool = False,
-                 prefill_chunk: Optional[int] = None):
+                 prefill_chunk: Optional[int] = None, keep_logprobs: bool = False):
         # prefill_chunk: a prompt longer than this takes its first chunk at admission and one
         # more chunk per step() (qie_prefill_append), so an admission stalls the live slots for
         # one chunk's prefill at a time; its first token is emitted after the last chunk
         self.prefill_chunk = prefill_chunk
         self.batch: Batch = engine.batch(slots, max_ctx, page_tokens=page_tokens, n_pages=n_pages)
         self.keep_logits = keep_logits          # copy each token's logit row (tests / diagnostics)
+        # each emitted token's log-probability into Request.logprobs (Batch.logprobs: one float
+        # per slot comes back, no [B][V] host copy)
+        self.keep_logprobs = keep_logprobs
         self.max_ctx = self.batch.max_ctx
         self.sampling = sampling
         free, _, self.page_tokens = self.batch.page_stats()
@@ -104,10 +120,19 @@ class ContinuousBatcher:
         self.budget += r.pages
         r.slot = -1
 
-    def _emit(self, r: Request, tok: int, out: list, logits=None) -> None:
+    def _logprobs(self, toks: Dict[int, int]):
+        """Log-probability of toks[slot] under each of those slots' current logits (None when
+        not kept); read before anything overwrites the rows."""
+        if not self.keep_logprobs or not toks:
+            return None
+        return self.batch.logprobs([toks.get(i, -1) for i in range(len(self.slots))])
+
+    def _emit(self, r: Request, tok: int, out: list, logits=None, lps=None) -> None:
         r.tokens.append(tok)
         if self.keep_logits:
             r.logits.append((self.batch.logits() if logits is None else logits)[r.slot].copy())
+        if self.keep_logprobs:
+            r.logprobs.append(float((self._logprobs({r.slot: tok}) if lps is None else lps)[r.slot]))
         out.append((r.rid, tok))
         if len(r.tokens) >= r.max_new_tokens or tok in r.stop_ids:
             self._finish(r)
@@ -143,8 +168,9 @@ class ContinuousBatcher:
                 toks = self.batch.prefill_batch(run[0].slot, [r.prompt for r in run], self.sampling)
                 first.update((r.rid, t) for r, t in zip(run, toks))
         lg = self.batch.logits() if self.keep_logits and whole else None
+        lps = self._logprobs({r.slot: first[r.rid] for r in whole})
         for r in whole:
-            self._emit(r, first[r.rid], out, lg)
+            self._emit(r, first[r.rid], out, lg, lps)
 
     def _advance_chunks(self, out: list, fresh: set) -> None:
         """One more prompt piece for every slot still in chunked prefill (not the requests
@@ -170,10 +196,11 @@ class ContinuousBatcher:
             live = list(self.slots)
             ids = self.batch.decode_step(self.sampling)
             lg = self.batch.logits() if self.keep_logits else None
-            for i, r in enumerate(live):
-                # a slot still in chunked prefill decodes too (fixed-B step); its output is dropped
-                if r is not None and not r.done and not r.chunks:
-                    self._emit(r, int(ids[i]), out, lg)
+            # a slot still in chunked prefill decodes too (fixed-B step); its output is dropped
+            emit = [(i, r) for i, r in enumerate(live) if r is not None and not r.done and not r.chunks]
+            lps = self._logprobs({i: int(ids[i]) for i, _ in emit})
+            for i, r in emit:
+                self._emit(r, int(ids[i]), out, lg, lps)
         return out
 
     def idle(self) -> bool:
