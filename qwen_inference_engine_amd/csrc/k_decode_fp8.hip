@@ -28,6 +28,7 @@
 // epilogues round exactly as the reference's separate kernels (bf16 after each op).
 #include "qie_common.hpp"
 #include "launch_util.hpp"
+#include "linear_epilogue.hpp"
 #include "linear_plan.hpp"
 #include "../../include/qie/qie_ops.h"
 
@@ -68,7 +69,8 @@ struct Dec8Params {
     unsigned* cnt;
 };
 
-// One bf16 pair of qie_rmsnorm's rms_apply8 (qie_common.hpp, normalization.cu:18-23).
+// One bf16 pair of the RMSNorm step (normalization.cu:18-23), this kernel's own form: unlike
+// rms_apply8 with div_mk (qie_common.hpp) it has no division for out-of-range operands.
 // REF: x / rms as q = x * (1 / rms) plus one FMA residual step (Markstein) — the correctly
 // rounded quotient whenever nothing underflows, i.e. for every |x / rms| above 2^-100
 // (smaller non-zero activations may land 1 fp32 ulp off before the bf16 rounding); three
@@ -378,30 +380,7 @@ __global__ __launch_bounds__(KS * 64, SPL ? 4 : 1) void dec8_kernel(Dec8Params p
         for (int b = 0; b < NB; b++)
 #pragma unroll
             for (int r = 0; r < 4; r++) c[b][r] = sum[b][r] * scv[b];
-        if (n >= p.N) return;
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int i = 4 * g + r;
-            if (i >= M) continue;
-            uint16_t* yr = p.y + (int64_t)i * p.ldy;
-            if constexpr (EPI == QIE_EPI_SWIGLU) {
-                const float gg = rbf(c[0][r]);
-                const float uu = rbf(c[1][r]);
-                const float a = rbf(gg * (1.0f / (1.0f + expf(-gg))));
-                yr[n] = f2bf(uu * a);
-            } else if constexpr (EPI == QIE_EPI_RESIDUAL) {
-                yr[n] = f2bf(epv[r] + rbf(c[0][r]));
-            } else if constexpr (EPI == QIE_EPI_F32) {
-                reinterpret_cast<float*>(p.y)[(int64_t)i * p.ldy + n] = c[0][r];
-            } else {
-                const uint16_t o = f2bf(c[0][r] + epv[0]);
-                yr[n] = o;
-                if (p.keys) {
-                    const unsigned long long kk = sel_key(bf2f(o), (uint32_t)(n + p.key_col0));
-                    kbest[r] = kk > kbest[r] ? kk : kbest[r];
-                }
-            }
-        }
+        emit_tile16<EPI>(c, epv, p.y, p.ldy, M, p.N, n, g, p.keys, p.key_col0, kbest);
     };
     const bool half = M <= 8;                                   // rows 0..7: lanes 0..31
     // (dev A/B QIE_DEC8_DBG & 16: the per-tile hand-off everywhere; split-K needs the deferred form)

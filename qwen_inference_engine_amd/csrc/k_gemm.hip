@@ -26,6 +26,7 @@
 #include "launch_util.hpp"
 #include "gemm_plan.hpp"
 #include "gemm8_tile.hpp"
+#include "linear_epilogue.hpp"
 #include "../../include/qie/qie_ops.h"
 
 #include <map>
@@ -120,10 +121,7 @@ __device__ __forceinline__ void gemm_epilogue(const f32x4 (&acc)[NI][NJ], const 
                 for (int r = 0; r < 4; r++) {
                     const int64_t row = m0 + wrow + i * 16 + fq * 4 + r;
                     if (row >= o.M) continue;
-                    const float g = rbf(acc[i][jj][r]);
-                    const float u = rbf(acc[i][jj + NJ / 2][r]);
-                    const float av = rbf(g * (1.0f / (1.0f + expf(-g))));
-                    o.C[row * o.ldc + col] = f2bf(u * av);
+                    o.C[row * o.ldc + col] = swiglu_bf16(acc[i][jj][r], acc[i][jj + NJ / 2][r]);
                 }
             }
         }

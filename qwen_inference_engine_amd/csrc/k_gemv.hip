@@ -16,6 +16,7 @@
 // that grid-stride over row tasks, so the norm prologue runs once per block.
 #include "qie_common.hpp"
 #include "launch_util.hpp"
+#include "linear_epilogue.hpp"
 #include "linear_plan.hpp"
 #include "plan_format.hpp"
 #include "../../include/qie/qie_ops.h"
@@ -67,17 +68,6 @@ struct GemvParams {
     // straight into every rank's tagged exchange slot (push.world > 0) instead of y
     PeerPush push;
 };
-
-// REF RMSNorm quotient f / rms: the FMA-corrected product with the reciprocal (Markstein),
-// the real division outside [1e-30, 1e30] (and for 0) — see skinny_mfma_kernel's prologue
-__device__ __forceinline__ float div_mk(float f, float rms, float inv) {
-#pragma clang fp contract(off)
-    const float q = f * inv;
-    float d = fmaf(fmaf(-q, rms, f), inv, q);
-    const float af = fabsf(f);
-    if (af != 0.f && (af < 1e-30f || af > 1e30f)) d = f / rms;
-    return d;
-}
 
 // uniform loads through the scalar cache (constant address space): the RoPE coefficients
 // wait on lgkmcnt, not behind the weight stream's in-order vmcnt
@@ -348,26 +338,12 @@ __global__ __launch_bounds__(LB) void gemv_kernel(GemvParams p) {
         for (int u = 0; u < U; u++)
 #pragma unroll
         for (int c = 0; c < NWC; c++) {   // static indices into xr / nvw: no scratch
-#pragma clang fp contract(off)
             if (u != wave + c * NWv || u >= nch) continue;   // wave-uniform
             float f[8], wf[8];
-            unpack8(u32x4{xr[u].x, xr[u].y, xr[u].z, xr[u].w}, f);
+            unpack8(xr[u], f);
             unpack8(nvw[c], wf);
-            uint32_t o[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                float y0, y1;
-                if (hf) {
-                    y0 = wf[2 * j] * rbf(f[2 * j] * inv);
-                    y1 = wf[2 * j + 1] * rbf(f[2 * j + 1] * inv);
-                } else {
-                    y0 = (f[2 * j] / rms) * wf[2 * j];
-                    y1 = (f[2 * j + 1] / rms) * wf[2 * j + 1];
-                }
-                o[j] = pack2(y0, y1);
-            }
             const int64_t k = (int64_t)lane * EL + u * WS;
-            if (k < K) *reinterpret_cast<uint4*>(xs + k) = make_uint4(o[0], o[1], o[2], o[3]);
+            if (k < K) *reinterpret_cast<uint4*>(xs + k) = rms_apply8(f, wf, rms, inv, hf, false);
         }
         __syncthreads();
     } else if constexpr (XCH == 4) {
@@ -401,27 +377,10 @@ __global__ __launch_bounds__(LB) void gemv_kernel(GemvParams p) {
         const bool hf = p.numerics == QIE_NUMERICS_HF;
 #pragma unroll
         for (int u = 0; u < U; u++) {
-#pragma clang fp contract(off)
             float f[8], wf[8];
             unpack8(xa[u], f);
             unpack8(na[u], wf);
-            uint32_t o[4];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                float y0, y1;
-                if (hf) {
-                    y0 = wf[2 * j] * rbf(f[2 * j] * inv);
-                    y1 = wf[2 * j + 1] * rbf(f[2 * j + 1] * inv);
-                } else if (p.mkdiv) {
-                    y0 = div_mk(f[2 * j], rms, inv) * wf[2 * j];
-                    y1 = div_mk(f[2 * j + 1], rms, inv) * wf[2 * j + 1];
-                } else {
-                    y0 = (f[2 * j] / rms) * wf[2 * j];
-                    y1 = (f[2 * j + 1] / rms) * wf[2 * j + 1];
-                }
-                o[j] = pack2(y0, y1);
-            }
-            xq[u] = make_uint4(o[0], o[1], o[2], o[3]);
+            xq[u] = rms_apply8(f, wf, rms, inv, hf, p.mkdiv != 0);
         }
     } else if constexpr (XCH > 0) {
         // ---------------- x-first prologue (MT = 1, x staged in LDS, K <= 2048 * XCH; the
@@ -475,29 +434,9 @@ __global__ __launch_bounds__(LB) void gemv_kernel(GemvParams p) {
             const bool hf = p.numerics == QIE_NUMERICS_HF;
 #pragma unroll
             for (int c = 0; c < XCH; c++) {
-#pragma clang fp contract(off)
                 const int64_t k = (int64_t)tid * 8 + c * TS;
                 if (k >= K) continue;
-                float f[8], wf[8];
-                unpack8(u32x4{xv[c].x, xv[c].y, xv[c].z, xv[c].w}, f);
-                unpack8(u32x4{nv[c].x, nv[c].y, nv[c].z, nv[c].w}, wf);
-                uint32_t o[4];
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    float y0, y1;
-                    if (hf) {
-                        y0 = wf[2 * j] * rbf(f[2 * j] * inv);
-                        y1 = wf[2 * j + 1] * rbf(f[2 * j + 1] * inv);
-                    } else if (p.mkdiv) {
-                        y0 = div_mk(f[2 * j], rms, inv) * wf[2 * j];
-                        y1 = div_mk(f[2 * j + 1], rms, inv) * wf[2 * j + 1];
-                    } else {
-                        y0 = (f[2 * j] / rms) * wf[2 * j];
-                        y1 = (f[2 * j + 1] / rms) * wf[2 * j + 1];
-                    }
-                    o[j] = pack2(y0, y1);
-                }
-                *reinterpret_cast<uint4*>(xs + k) = make_uint4(o[0], o[1], o[2], o[3]);
+                *reinterpret_cast<uint4*>(xs + k) = rms_apply8(xv[c], nv[c], rms, inv, hf, p.mkdiv != 0);
             }
         }
         if (!staged) {
@@ -537,26 +476,9 @@ __global__ __launch_bounds__(LB) void gemv_kernel(GemvParams p) {
                 const float inv = 1.0f / rms;
                 const bool hf = p.numerics == QIE_NUMERICS_HF;
                 for (int64_t k = tid * 8; k < K; k += TS) {
-#pragma clang fp contract(off)
-                    uint4 v = *reinterpret_cast<const uint4*>(xr + k);
-                    uint4 nw = *reinterpret_cast<const uint4*>(p.norm_w + k);
-                    float f[8], wf[8];
-                    unpack8(u32x4{v.x, v.y, v.z, v.w}, f);
-                    unpack8(u32x4{nw.x, nw.y, nw.z, nw.w}, wf);
-                    uint32_t o[4];
-#pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        float y0, y1;
-                        if (hf) {
-                            y0 = wf[2 * j] * rbf(f[2 * j] * inv);
-                            y1 = wf[2 * j + 1] * rbf(f[2 * j + 1] * inv);
-                        } else {
-                            y0 = (f[2 * j] / rms) * wf[2 * j];
-                            y1 = (f[2 * j + 1] / rms) * wf[2 * j + 1];
-                        }
-                        o[j] = pack2(y0, y1);
-                    }
-                    *reinterpret_cast<uint4*>(xo + k) = make_uint4(o[0], o[1], o[2], o[3]);
+                    const uint4 v = *reinterpret_cast<const uint4*>(xr + k);
+                    const uint4 nw = *reinterpret_cast<const uint4*>(p.norm_w + k);
+                    *reinterpret_cast<uint4*>(xo + k) = rms_apply8(v, nw, rms, inv, hf, false);
                 }
             } else {
                 for (int64_t k = tid * 8; k < K; k += TS)
@@ -639,10 +561,7 @@ __global__ __launch_bounds__(LB) void gemv_kernel(GemvParams p) {
 #pragma unroll
                     for (int i = 0; i < P2; i++) {
                         if (col[i] >= p.N) continue;
-                        float g = rbf(acc[m][i]);
-                        float u = rbf(acc[m][P2 + i]);
-                        float a = rbf(g * (1.0f / (1.0f + expf(-g))));
-                        yr[col[i]] = f2bf(u * a);
+                        yr[col[i]] = swiglu_bf16(acc[m][i], acc[m][P2 + i]);
                     }
                 } else if constexpr (EPI == QIE_EPI_F32) {
                     if (p.push.world > 0) {
@@ -980,31 +899,7 @@ __global__ __launch_bounds__(NW * 64) void skinny_mfma_kernel(GemvParams p) {
 #pragma unroll
                     for (int r = 0; r < 4; r++) c[b][r] *= st.wsc[b];
             }
-            if (n < p.N) {
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int i = 4 * g + r;
-                    if (i >= M) continue;
-                    uint16_t* yr = p.y + (int64_t)i * p.ldy;
-                    if constexpr (EPI == QIE_EPI_SWIGLU) {
-                        const float gg = rbf(c[0][r]);
-                        const float uu = rbf(c[1][r]);
-                        const float av = rbf(gg * (1.0f / (1.0f + expf(-gg))));
-                        yr[n] = f2bf(uu * av);
-                    } else if constexpr (EPI == QIE_EPI_RESIDUAL) {
-                        yr[n] = f2bf(st.ep[r] + rbf(c[0][r]));
-                    } else if constexpr (EPI == QIE_EPI_F32) {
-                        reinterpret_cast<float*>(p.y)[(int64_t)i * p.ldy + n] = c[0][r];
-                    } else {
-                        const uint16_t o = f2bf(c[0][r] + st.ep[0]);
-                        yr[n] = o;
-                        if (p.keys) {
-                            const unsigned long long kk = sel_key(bf2f(o), (uint32_t)(n + p.key_col0));
-                            kbest[r] = kk > kbest[r] ? kk : kbest[r];
-                        }
-                    }
-                }
-            }
+            emit_tile16<EPI>(c, st.ep, p.y, p.ldy, M, p.N, n, g, p.keys, p.key_col0, kbest);
         }
 #pragma unroll
         for (int b = 0; b < NB; b++) acc[b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
@@ -1058,9 +953,7 @@ __global__ __launch_bounds__(NW * 64) void skinny_mfma_kernel(GemvParams p) {
                 inv[m] = 1.0f / rms[m];
             }
             // pass 2: all rows of a chunk at once (loads unconditional and clamped; the
-            // per-row math under uniform branches).  REF's f / rms uses the FMA-corrected
-            // quotient (Markstein): correctly rounded, i.e. equal to the division, for
-            // normal operands — |f| outside [1e-30, 1e30] takes the real division.
+            // per-row math under uniform branches).  REF's f / rms is div_mk (qie_common.hpp).
             for (int64_t k = tid * 8; k < K; k += NW * 512) {
                 const uint4 nw = *reinterpret_cast<const uint4*>(p.norm_w + k);
                 uint4 v[16];
@@ -1073,26 +966,8 @@ __global__ __launch_bounds__(NW * 64) void skinny_mfma_kernel(GemvParams p) {
                 for (int m = 0; m < 16; m++) {
                     if (m >= M) continue;
                     float f[8];
-                    unpack8(u32x4{v[m].x, v[m].y, v[m].z, v[m].w}, f);
-                    uint32_t o[4];
-                    if (hf) {
-#pragma unroll
-                        for (int j = 0; j < 4; j++)
-                            o[j] = pack2(wf[2 * j] * rbf(f[2 * j] * inv[m]), wf[2 * j + 1] * rbf(f[2 * j + 1] * inv[m]));
-                    } else {
-                        float y[8];
-#pragma unroll
-                        for (int j = 0; j < 8; j++) {
-                            const float q = f[j] * inv[m];
-                            float d = fmaf(fmaf(-q, rms[m], f[j]), inv[m], q);
-                            const float af = fabsf(f[j]);
-                            if (af != 0.f && (af < 1e-30f || af > 1e30f)) d = f[j] / rms[m];
-                            y[j] = d * wf[j];
-                        }
-#pragma unroll
-                        for (int j = 0; j < 4; j++) o[j] = pack2(y[2 * j], y[2 * j + 1]);
-                    }
-                    *reinterpret_cast<uint4*>(xs + (int64_t)m * KP + k) = make_uint4(o[0], o[1], o[2], o[3]);
+                    unpack8(v[m], f);
+                    *reinterpret_cast<uint4*>(xs + (int64_t)m * KP + k) = rms_apply8(f, wf, rms[m], inv[m], hf, true);
                 }
             }
         } else {
@@ -1157,8 +1032,6 @@ static Knobs dev_knobs() {
     k.epre = dev_env("QIE_GEMV_EPRE", k.epre);
     k.mkdiv = dev_env("QIE_GEMV_MKDIV", k.mkdiv);
     k.gemv_dbg = dev_env("QIE_GEMV_DBG", k.gemv_dbg);
-    k.rpw = dev_env("QIE_GEMV_RPW", k.rpw);
-    k.rpw_lm = dev_env("QIE_GEMV_RPW_LM", k.rpw);
     k.blocks_per_cu = dev_env("QIE_GEMV_BLOCKS_PER_CU", k.blocks_per_cu);
     k.xfirst = dev_env("QIE_GEMV_XFIRST", k.xfirst);
     k.xreg = dev_env("QIE_GEMV_XREG", k.xreg);
@@ -1188,7 +1061,7 @@ static size_t gemv_lds_limit(size_t shm) { return shm > 65536 ? 160 * 1024 : 0; 
 
 template <int MT, int RPW, int EPI, int XCH, int WT, int UO = 0>
 static int launch_gemv_t(const GemvParams& p, const LinearPlan& pl, hipStream_t st) {
-    constexpr int U = UO ? UO : ((RPW >= 4) ? 4 : 8);
+    constexpr int U = UO ? UO : 8;
     const void* fn = (const void*)gemv_kernel<MT, RPW, EPI, U, XCH, WT>;
     if (pl.block_waves) {   // one block per CU: the instantiation bounded at its block size
         if constexpr (MT == 1 && WT == 0 && EPI != QIE_EPI_SWIGLU) {
@@ -1217,8 +1090,7 @@ static int launch_gemv_m(const GemvParams& p, const LinearPlan& pl, hipStream_t 
     }
     return dispatch_epi(pl.epi, [&](auto E) {
         constexpr int EPI = decltype(E)::value;
-        return pl.rpw >= 4 ? launch_gemv_t<MT, 4, EPI, XCH, WT, UO>(p, pl, st)
-                           : launch_gemv_t<MT, 2, EPI, XCH, WT, UO>(p, pl, st);
+        return launch_gemv_t<MT, 2, EPI, XCH, WT, UO>(p, pl, st);
     });
 }
 

@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256) void rmsnorm_kernel(const uint4* __restrict__ 
     ss = block_sum_256(ss, red);
     const float rms = sqrtf((ss / (float)H) + eps);
     const float inv = 1.0f / rms;
-    for (int64_t i = threadIdx.x; i < H8; i += 256) yr[i] = rms_apply8(xr[i], w[i], rms, inv, numerics == QIE_NUMERICS_HF);
+    for (int64_t i = threadIdx.x; i < H8; i += 256) yr[i] = rms_apply8(xr[i], w[i], rms, inv, numerics == QIE_NUMERICS_HF, false);
 }
 
 // H <= 2048 V: the row and the norm weights stay in registers, both loaded up front (one
@@ -171,7 +171,7 @@ __global__ __launch_bounds__(256) void rmsnorm_reg_kernel(const uint4* __restric
 #pragma unroll
     for (int c = 0; c < V; c++) {
         const int64_t i = threadIdx.x + 256 * c;
-        if (i < H8) yr[i] = rms_apply8(xv[c], wv[c], rms, inv, numerics == QIE_NUMERICS_HF);
+        if (i < H8) yr[i] = rms_apply8(xv[c], wv[c], rms, inv, numerics == QIE_NUMERICS_HF, false);
     }
 }
 

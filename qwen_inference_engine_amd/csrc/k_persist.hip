@@ -79,10 +79,6 @@ constexpr int kTsSlots = 12;
 
 __device__ __forceinline__ float bl(uint32_t w) { return __uint_as_float(w << 16); }
 __device__ __forceinline__ float bh(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
-__device__ __forceinline__ void unpack8(const uint4& v, float* f) {
-    f[0] = bl(v.x); f[1] = bh(v.x); f[2] = bl(v.y); f[3] = bh(v.y);
-    f[4] = bl(v.z); f[5] = bh(v.z); f[6] = bl(v.w); f[7] = bh(v.w);
-}
 // the GEMV kernels' per-chunk FMA chain (k_gemv.hip fma8): element order 0..7
 __device__ __forceinline__ void fma8(float& acc, const float* xf, u32x4 w) {
     acc = fmaf(xf[0], bl(w.x), acc);
@@ -293,23 +289,8 @@ __device__ __forceinline__ void normalize(const uint16_t* x, const uint16_t* nw,
 #pragma clang fp contract(off)
     const float inv = 1.0f / rms;
     for (int i = threadIdx.x; i * 8 < K; i += blockDim.x) {
-        float f[8], wf[8];
-        unpack8(*reinterpret_cast<const uint4*>(x + i * 8), f);
-        unpack8(*reinterpret_cast<const uint4*>(nw + i * 8), wf);
-        uint32_t o[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            float y0, y1;
-            if (hf) {
-                y0 = wf[2 * j] * rbf(f[2 * j] * inv);
-                y1 = wf[2 * j + 1] * rbf(f[2 * j + 1] * inv);
-            } else {
-                y0 = (f[2 * j] / rms) * wf[2 * j];
-                y1 = (f[2 * j + 1] / rms) * wf[2 * j + 1];
-            }
-            o[j] = pack2(y0, y1);
-        }
-        *reinterpret_cast<uint4*>(y + i * 8) = make_uint4(o[0], o[1], o[2], o[3]);
+        const uint4 xv = *reinterpret_cast<const uint4*>(x + i * 8), wv = *reinterpret_cast<const uint4*>(nw + i * 8);
+        *reinterpret_cast<uint4*>(y + i * 8) = rms_apply8(xv, wv, rms, inv, hf, false);
     }
 }
 

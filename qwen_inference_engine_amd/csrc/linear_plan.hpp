@@ -26,8 +26,6 @@ struct Knobs {
     int epre = 1;             // QIE_GEMV_EPRE
     int mkdiv = 0;            // QIE_GEMV_MKDIV
     int gemv_dbg = 0;         // QIE_GEMV_DBG (M = 1 timing experiments: 1 no norm, 2 no bias)
-    int rpw = 2;              // QIE_GEMV_RPW
-    int rpw_lm = 2;           // QIE_GEMV_RPW_LM (default: rpw)
     int blocks_per_cu = -1;   // QIE_GEMV_BLOCKS_PER_CU
     int xfirst = 1;           // QIE_GEMV_XFIRST
     int xreg = kAuto;         // QIE_GEMV_XREG (default: 1 for vocabulary rows, else 0)
@@ -195,7 +193,7 @@ inline bool one_block_per_cu(int mt, bool fp8, int epi, int bpc, int64_t n_tasks
            n_tasks <= max_waves * cus && k.balanced != 0;
 }
 
-// Chunks in flight per row (UO, 0 = the default 8, or 4 at four rows per wave) sized to K (bf16
+// Chunks in flight per row (UO, 0 = the default 8) sized to K (bf16
 // wave-loads per row n), so no load slot re-reads the row's tail: n <= 2 (Qwen2-0.5B, K = 896):
 // 2 instead of 8 slots, 6 of them duplicates — lm_head 72.1 -> 47.4 us, gate/up 8.4 -> 6.3,
 // decode 1,283 -> 1,471 tok/s; n = 7 (Qwen2-7B, K = 3,584): 7 instead of 8 — gate/up
@@ -295,13 +293,10 @@ inline LinearPlan plan_linear(const qie_linear_args& a, const LinearExtras& ex, 
         return pl;
     }
     const int64_t rows = a.epilogue == QIE_EPI_SWIGLU ? 2 * a.N : a.N;
-    // Rows per wave: 2 (measured faster than 4 for every Qwen2-7B decode GEMV on
-    // MI355X: down 23.7 vs 28.0 us, qkv 9.7 vs 10.9, o 6.6 vs 7.7, gate/up 42.9 vs 43.8).
-    int rpw = k.rpw;
-    // (dev A/B) vocabulary rows: 4 rows per wave measured 165.9 vs 164.8 µs at Qwen2-7B,
-    // 53.4 vs 48.7 at Qwen2-0.5B
-    if (MT == 1 && rows >= 65536) rpw = k.rpw_lm;
-    if (rpw != 2 && rpw != 4) rpw = 2;
+    // Rows per wave: 2, or 1 below.  (4, since removed, measured slower for every Qwen2-7B decode
+    // GEMV on MI355X: down 23.7 vs 28.0 us, qkv 9.7 vs 10.9, o 6.6 vs 7.7, gate/up 42.9 vs 43.8;
+    // vocabulary rows 165.9 vs 164.8 us, 53.4 vs 48.7 at Qwen2-0.5B.)
+    int rpw = 2;
     int64_t n_tasks = (rows + rpw - 1) / rpw;
     // Grid (QIE_GEMV_BLOCKS_PER_CU): default (auto) = one block per CU with ceil(tasks / CUs)
     // waves where 4..9 tasks per CU (Qwen2-7B QKV, O, down), else the occupancy-balanced

@@ -72,7 +72,7 @@ inline std::string format_linear_plan(const qie_linear_args& a, const Knobs& k, 
             break;
         case LinearFamily::Gemv:
             plan_appendf(s, "gemv_kernel<%d,%d,%s,%d,%d,%d>", pl.mt, pl.rpw, epi_name(pl.epi),
-                         pl.uo ? pl.uo : (pl.rpw >= 4 ? 4 : 8), pl.xch, pl.wt);
+                         pl.uo ? pl.uo : 8, pl.xch, pl.wt);
             if (pl.block_waves) plan_appendf(s, " LB=%d", pl.rpw == 1 ? 1024 : kGemvBalancedThreads);
             plan_appendf(s, " xlds=%d tasks=%lld bpc=%d", pl.xlds, (long long)pl.n_tasks, pl.bpc);
             break;

@@ -85,33 +85,58 @@ __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
 }
 
 // ------------------------------------------------------------- RMSNorm step
+// REF quotient f / rms as the FMA-corrected product with the reciprocal (Markstein): correctly
+// rounded, i.e. equal to the division, for normal operands; |f| outside [1e-30, 1e30] takes
+// the real division.
+__device__ __forceinline__ float div_mk(float f, float rms, float inv) {
+#pragma clang fp contract(off)
+    const float q = f * inv;
+    float d = fmaf(fmaf(-q, rms, f), inv, q);
+    const float af = fabsf(f);
+    if (af != 0.f && (af < 1e-30f || af > 1e30f)) d = f / rms;
+    return d;
+}
+__device__ __forceinline__ void unpack8(uint4 v, float* f) {
+    f[0] = bf_lo(v.x); f[1] = bf_hi(v.x);
+    f[2] = bf_lo(v.y); f[3] = bf_hi(v.y);
+    f[4] = bf_lo(v.z); f[5] = bf_hi(v.z);
+    f[6] = bf_lo(v.w); f[7] = bf_hi(v.w);
+}
 // Eight elements of a normed row, packed to bf16 (REF parity is bit-exact on this expression):
 //   REF: y = bf16((x / rms) * w)              normalization.cu:18-23
 //   HF : y = bf16(w * bf16(x * (1 / rms)))    (inv = 1 / rms)
-// qie_rmsnorm's kernels (k_misc.hip) call it.  The fused prologues of gemv_kernel,
-// skinny_mfma_kernel and the persistent step (k_persist.hip normalize) spell the same step out
-// in place: calling this helper there changed their register allocation (compared on the
-// gfx950 disassembly), so they are to be moved only together with a measurement.
-__device__ __forceinline__ uint4 rms_apply8(uint4 xv, uint4 wv, float rms, float inv, bool hf) {
+// `mk` picks REF's quotient: false the division, true div_mk.  Each caller keeps the form it was
+// written with: qie_rmsnorm (k_misc.hip), gemv_kernel's XCH 3 and generic prologues and the
+// persistent step (k_persist.hip normalize) divide, gemv_kernel's XCH 2 / 4 / 5 prologues follow
+// the mkdiv knob, skinny_mfma_kernel takes div_mk.  Calling it from the fused prologues moves
+// their register allocation by a few VGPRs against the step written in place (no shipped kernel
+// gains scratch); outputs are bit-identical and every decode kernel and step time stayed within
+// the in-place form's run-to-run spread on MI355X (profiles/rms_step_shared.json).
+__device__ __forceinline__ uint4 rms_apply8(const float* f, const float* wf, float rms, float inv, bool hf, bool mk) {
 #pragma clang fp contract(off)
-    uint32_t xs[4] = {xv.x, xv.y, xv.z, xv.w};
-    uint32_t ws[4] = {wv.x, wv.y, wv.z, wv.w};
     uint32_t o[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-        float a0 = bf_lo(xs[j]), a1 = bf_hi(xs[j]);
-        float w0 = bf_lo(ws[j]), w1 = bf_hi(ws[j]);
         float y0, y1;
         if (hf) {
-            y0 = w0 * rbf(a0 * inv);
-            y1 = w1 * rbf(a1 * inv);
+            y0 = wf[2 * j] * rbf(f[2 * j] * inv);
+            y1 = wf[2 * j + 1] * rbf(f[2 * j + 1] * inv);
+        } else if (mk) {
+            y0 = div_mk(f[2 * j], rms, inv) * wf[2 * j];
+            y1 = div_mk(f[2 * j + 1], rms, inv) * wf[2 * j + 1];
         } else {
-            y0 = (a0 / rms) * w0;
-            y1 = (a1 / rms) * w1;
+            y0 = (f[2 * j] / rms) * wf[2 * j];
+            y1 = (f[2 * j + 1] / rms) * wf[2 * j + 1];
         }
         o[j] = pack2(y0, y1);
     }
     return make_uint4(o[0], o[1], o[2], o[3]);
+}
+__device__ __forceinline__ uint4 rms_apply8(uint4 xv, uint4 wv, float rms, float inv, bool hf, bool mk) {
+    float f[8], wf[8];
+    unpack8(xv, f);
+    unpack8(wv, wf);
+    return rms_apply8(f, wf, rms, inv, hf, mk);
 }
 
 // ------------------------------------------------------ fp8 (OCP e4m3fn) weights

@@ -168,6 +168,8 @@ CASES = [
     # L2, XL 1 the rows staged in LDS (a fused norm, or more than two column tiles per CU)
     C("sk_store_m16_k192", 16, 192, (23, 9, 8), "STORE", "skinny_mfma_kernel<STORE,0,0,4,0>", bias=True,
       ldx_pad=8, ldy_pad=3),   # 3 units: wave 3 has no K range
+    C("sk_store_m13_keys", 13, 192, (23, 9, 8), "STORE", "skinny_mfma_kernel<STORE,0,0,4,0>", bias=True,
+      key_col0=5),             # arg-max keys of rows past 4 (every lane group of the C tile), three column tiles
     C("sk_swiglu_norm_m16_k320", 16, 320, 40, "SWIGLU", "skinny_mfma_kernel<SWIGLU,0,1,4,0>", norm="ref"),
     C("sk_res_staged_514tiles", 5, 64, 8210, "RESIDUAL", "skinny_mfma_kernel<RESIDUAL,0,1,4,0>", twice=True),
     C("sk_swiglu_staged_514tiles", 5, 64, 8210, "SWIGLU", "skinny_mfma_kernel<SWIGLU,0,1,4,0>", twice=True),

@@ -32,8 +32,7 @@ GRID_N = [2, 16, 18, 130, 512, 1024, 2048, 2050, 2304, 2306, 3584, 4096, 4098, 4
           18944, 32768, 32784, 65536, 65538, 152064]
 
 # QIE_GEMV_CASE(MT, XCH, WT, UO) entries no shape reaches with the shipped knobs: development
-# A/B code ("Linear variants: the coverage rule").  Rows per wave is no part of the
-# entry: every RPW 4 form likewise needs QIE_GEMV_RPW / QIE_GEMV_RPW_LM = 4.
+# A/B code ("Linear variants: the coverage rule").
 DEV_ONLY_GEMV_CASES = {
     (1, 3, 0, 7): "QIE_GEMV_XREG=1 (XCH 3 below the vocabulary threshold, K of 7 wave-loads)",
 }
