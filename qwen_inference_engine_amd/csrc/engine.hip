@@ -20,12 +20,12 @@
 #include "qie_index.hpp"
 #include "qie_comm.hpp"
 #include "verify.hpp"
+#include "row_bufs.hpp"
 
 #include <chrono>
 #include <cstring>
 #include <fstream>
 #include <functional>
-#include <type_traits>
 #include <vector>
 
 namespace qie {
@@ -107,43 +107,53 @@ struct qie_engine {
     int rope_rows = 0;
 };
 
+static int dmalloc(void** p, size_t bytes) {
+    QIE_HIP(hipMalloc(p, bytes < 16 ? 16 : bytes));
+    return 0;
+}
+
+// One device allocation that frees itself: the per-call workspaces that grow on their own
+// schedule, and the timing calls' scratch
+struct DevBlock {
+    void* p = nullptr;
+    size_t bytes = 0;
+    DevBlock() = default;
+    DevBlock(const DevBlock&) = delete;
+    DevBlock& operator=(const DevBlock&) = delete;
+    ~DevBlock() { release(); }
+    void release() {
+        if (p) hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    // at least n bytes (never null afterwards); freed before it is made anew, so the peak does
+    // not double and a failure leaves nothing dangling
+    int grow(size_t n) {
+        if (p && n <= bytes) return 0;
+        release();
+        QIE_TRY(dmalloc(&p, n));
+        bytes = n;
+        return 0;
+    }
+};
+
+// Device rows (row_bufs.hpp; DESIGN.md §2 "Row buffers").  Pointer stability: `dec` and `v` are
+// made once and never reallocated, `pf`, `pf_ws`, `sc` and `sc_ws` grow (freed, then made anew);
+// captured work (the decode graph, captured verify steps, the persistent step's attention table)
+// may reference only the former.
 struct qie_batch {
     qie_engine* e = nullptr;
     int B = 0, max_ctx = 0;
+    // KV pools (not rows): their own allocations
     uint16_t* kc = nullptr;
     uint16_t* vc = nullptr;
     int64_t seq_stride = 0;
     int run_pad = 0;             // contiguous: run = max_ctx + run_pad tokens (dev A/B)
-    int32_t* d_pos = nullptr;
-    float* d_rope_cur = nullptr;   // [B][rope_cur_stride(hd)]: RoPE row of each slot's current position
-    int32_t* d_step = nullptr;
-    int32_t* d_hist = nullptr;
-    int32_t* d_ids = nullptr;
-    unsigned long long* d_keys = nullptr;
-    uint16_t* x_res = nullptr;
-    uint16_t* qkv = nullptr;
-    uint16_t* q = nullptr;
-    uint16_t* att = nullptr;
-    uint16_t* h = nullptr;
-    uint16_t* xn = nullptr;     // [B][H] RMS-normed rows feeding the batched (B >= 2) projections
-    uint16_t* logits = nullptr;
-    void* attn_ws = nullptr;
-    void* dec_ws = nullptr;     // fused decode attention: split partials + zeroed counters
-    void* samp_ws = nullptr;
-    // tensor parallel: fp32 partials of the row-parallel projections, gathered logits
-    float* part = nullptr;            // [B][H]
-    uint16_t* logits_full = nullptr;  // [B][V]
-    uint16_t* gather_tmp = nullptr;   // [tp][B][V/tp]
-    float* pf_part = nullptr;         // [pf_rows][H]
+    DecodeRows dec;              // the B slots, made by batch_create
     std::vector<int32_t> h_pos;
-    // prefill scratch
-    int64_t pf_rows = 0;
-    uint16_t *pf_x = nullptr, *pf_hn = nullptr, *pf_qkv = nullptr, *pf_q = nullptr, *pf_att = nullptr,
-             *pf_h = nullptr;
-    int32_t *pf_pos = nullptr, *pf_ids = nullptr;
-    uint8_t *pf_q8 = nullptr, *pf_e8 = nullptr;   // fp8 prefill (opts.prefill_fp8): codes [rows][max K], exps [rows]
-    void* pf_attn_ws = nullptr;
-    int64_t pf_attn_ws_bytes = 0;   // the split workspace depends on n (short prompts split), not on n <= pf_rows
+    PrefillRows pf;              // prompt rows, grown to the largest prefill so far
+    DevBlock pf_ws;              // its attention workspace: depends on n and on the form (short prompts split;
+                                 //   an append's partials grow with its rows), not monotone in n
     // paged KV (qie_batch_create_paged): pool pages of page_tokens tokens, block table
     // [B][max_pages] on device and host, free list, pages held per slot
     int page_tokens = 0, max_pages = 0, n_pages = 0;
@@ -166,19 +176,9 @@ struct qie_batch {
     qie_layer_weights* d_layers = nullptr;
     void* d_attp = nullptr;      // the attention role's parameters per layer (persist_attn_table)
     unsigned long long* pk_ts = nullptr;   // qie_batch_pk_trace: phase timestamps [cu][layer][slots]
-    // speculative verify (qie_verify): the step's own row buffers, made once at
-    // kVerifyMaxRows rows by the first call (one allocation; a captured step holds pointers
-    // into it, never into the growable prefill scratch), and one captured step per
-    // (slot, rows, sampling)
-    struct VerifyBufs {
-        void* mem = nullptr;
-        uint16_t *x = nullptr, *xn = nullptr, *qkv = nullptr, *q = nullptr, *att = nullptr, *h = nullptr;
-        uint16_t *logits = nullptr, *logits_full = nullptr, *gather_tmp = nullptr;
-        float* part = nullptr;
-        void *attn_ws = nullptr, *samp_ws = nullptr;
-        unsigned long long* keys = nullptr;
-        int32_t *ids = nullptr, *pos = nullptr, *step = nullptr, *draft = nullptr, *res = nullptr;
-    } v;
+    // speculative verify (qie_verify): the step's own rows, made once at
+    // kVerifyMaxRows rows by the first call, and one captured step per (slot, rows, sampling)
+    VerifyRows v;
     struct VerifyGraph {
         int seq, M;
         bool greedy;
@@ -188,13 +188,9 @@ struct qie_batch {
     std::vector<VerifyGraph> v_graphs;
     int v_rows = 0;   // rows of the last qie_verify (what qie_verify_logits returns)
     // scoring (qie_score, qie_batch_logprobs): device targets, log-probabilities and
-    // greedy ids of `rows` rows, and the fused head's workspace; grown before any launch
-    struct ScoreBufs {
-        int64_t rows = 0, ws_bytes = 0;
-        int32_t *tgt = nullptr, *ids = nullptr;
-        float* lp = nullptr;
-        void* ws = nullptr;
-    } sc;
+    // greedy ids of sc.rows rows, and the fused head's workspace; grown before any launch
+    ScoreRows sc;
+    DevBlock sc_ws;
 };
 
 namespace qie {
@@ -255,14 +251,9 @@ __global__ void copy_ids_kernel(const int32_t* src, int32_t* dst, int len, int64
     if (i < len) dst[blockIdx.y * dst_stride + i] = src[(int64_t)blockIdx.y * len + i];
 }
 
-static int dmalloc(void** p, size_t bytes) {
-    QIE_HIP(hipMalloc(p, bytes < 16 ? 16 : bytes));
-    return 0;
-}
-
 static RopeCurArgs rope_cur_args(const qie_batch* b) {
     const qie_engine* e = b->e;
-    return RopeCurArgs{b->d_rope_cur, e->rope_cos, e->rope_sin, (int)e->spec.head_dim, e->rope_rows};
+    return RopeCurArgs{b->dec.rope_cur, e->rope_cos, e->rope_sin, (int)e->spec.head_dim, e->rope_rows};
 }
 
 // KV descriptor of the batch's sequences seq0.. (kernels see them as sequences 0..)
@@ -590,21 +581,8 @@ static bool rope_in_projection(const qie_batch* b) {
 static int dbg_snap(qie_batch* b, int slot) {
     if (!b->dbg_x) return 0;
     const int64_t n = (int64_t)b->B * b->e->spec.hidden;
-    QIE_HIP(hipMemcpyAsync(b->dbg_x + slot * n, b->x_res, (size_t)n * 2, hipMemcpyDeviceToDevice, b->e->stream));
+    QIE_HIP(hipMemcpyAsync(b->dbg_x + slot * n, b->dec.x, (size_t)n * 2, hipMemcpyDeviceToDevice, b->e->stream));
     return 0;
-}
-
-// The M rows a layer works on: the decode step's are the batch's B slots, a verify step's
-// (qie_verify) its own M <= 16 rows of one sequence, a prefill's the prompt rows.
-struct LayerRows {
-    int64_t M;
-    uint16_t *x, *xn, *qkv, *q, *att, *h;   // residual [M][H], normed [M][H], [M][QKVD], [M][QD] x 2, [M][I]
-    float* part;                            // [M][H] fp32 partials (exchange path only)
-    const int32_t* pos;                     // [M] positions on device; consecutive runs of
-    int32_t rows_per_seq;                   //   rows_per_seq rows belong to one sequence
-};
-static LayerRows decode_rows(const qie_batch* b) {
-    return LayerRows{b->B, b->x_res, b->xn, b->qkv, b->q, b->att, b->h, b->part, b->d_pos, 1};
 }
 
 // The four projections of a layer, described once: [norm + QKV (+ bias)], [O], [norm + gate/up +
@@ -680,8 +658,8 @@ static int stage_input(qie_batch* b, InputForm form, qie_linear_args& a, const L
     if (form == InputForm::Decode) return prenorm(b, a, r.xn);
     if (a.norm_w) QIE_TRY(norm_rows(b, a, r.xn));
     if (form == InputForm::Normed) return 0;
-    QIE_TRY(qie_quantize_rows_fp8(a.x, a.ldx, a.M, a.K, b->pf_q8, a.K, b->pf_e8, b->e->stream));
-    a.x = b->pf_q8; a.ldx = a.K; a.x_exps = b->pf_e8;
+    QIE_TRY(qie_quantize_rows_fp8(a.x, a.ldx, a.M, a.K, b->pf.q8, a.K, b->pf.e8, b->e->stream));
+    a.x = b->pf.q8; a.ldx = a.K; a.x_exps = b->pf.e8;
     a.flags |= QIE_LINEAR_ACT_FP8;
     return 0;
 }
@@ -711,19 +689,19 @@ static LinearExtras decode_qkv_extras(const qie_batch* b) {
     const qie_engine* e = b->e;
     const int64_t hd = e->spec.head_dim;
     LinearExtras ex;
-    if (rope_in_projection(b)) ex.rope = RopeArgs{b->d_pos, e->rope_cos, e->rope_sin, (int)hd, (e->sh.nq + e->sh.nkv) * hd};
+    if (rope_in_projection(b)) ex.rope = RopeArgs{b->dec.pos, e->rope_cos, e->rope_sin, (int)hd, (e->sh.nq + e->sh.nkv) * hd};
     return ex;
 }
-// the decode step's attention of layer l into out ([B][QD]: b->att, or the timing call's scratch)
+// the decode step's attention of layer l into out ([B][QD]: b->dec.att, or the timing call's scratch)
 static int attend_decode(qie_batch* b, int l, void* out) {
     qie_engine* e = b->e;
     const qie_model_spec& s = e->spec;
     const qie_layer_weights& L = e->layers[l];
     const qie_kv_cache cache = batch_cache(b, 0);
-    set_decode_rope_cur(b->d_rope_cur);
-    const int rc = qie_attention_decode(b->qkv, b->B, b->d_pos, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, e->sh.nq,
+    set_decode_rope_cur(b->dec.rope_cur);
+    const int rc = qie_attention_decode(b->dec.qkv, b->B, b->dec.pos, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, e->sh.nq,
                                         &cache, l, s.rms_eps,
-                                        s.numerics | (rope_in_projection(b) ? QIE_ATTN_PREROPED : 0), out, b->dec_ws,
+                                        s.numerics | (rope_in_projection(b) ? QIE_ATTN_PREROPED : 0), out, b->dec.dec_ws,
                                         e->stream);
     set_decode_rope_cur(nullptr);
     return rc;
@@ -733,7 +711,7 @@ static int enqueue_layer_decode(qie_batch* b, int l) {
     qie_engine* e = b->e;
     const LayerPath p = decode_path(e);
     const qie_layer_weights& L = p.layers[l];
-    const LayerRows r = decode_rows(b);
+    const LayerRows r = layer_rows(b->dec, b->B, 1);
     QIE_TRY(run_proj(b, qkv_args(e, L, p.flags, r), p.in, r, decode_qkv_extras(b)));
     QIE_TRY(attend_decode(b, l, r.att));
     QIE_TRY(run_row_proj(b, o_args(e, L, p.flags, r), p.in, r));
@@ -775,27 +753,6 @@ __global__ void unshard_rows_kernel(const uint16_t* __restrict__ tmp, uint16_t* 
     }
 }
 
-// What a head launch reads and writes: the batch's per-slot rows (batch_head) or a verify
-// step's own (verify_head).  logits / keys / ids / step / xn are row 0 of the rows served.
-struct HeadBufs {
-    uint16_t* logits;             // [M][Vl]
-    unsigned long long* keys;     // [M] (zero before the launch)
-    int32_t* ids;                 // [M]
-    const int32_t* step;          // [M] sampling counters
-    void* samp_ws;
-    uint16_t* xn;                 // [M][H] (prenorm)
-    uint16_t *gather_tmp, *logits_full;   // exchange path: [tp][M][Vl], [rows][V]
-    int full_row0;                // first row of logits_full the M rows land in
-};
-static HeadBufs batch_head(const qie_batch* b, int m0) {
-    return HeadBufs{b->logits + (int64_t)m0 * b->e->sh.vocab, b->d_keys + m0, b->d_ids + m0, b->d_step + m0, b->samp_ws,
-                    b->xn, b->gather_tmp, b->logits_full, m0};
-}
-static HeadBufs verify_head(const qie_batch* b) {
-    return HeadBufs{b->v.logits, b->v.keys, b->v.ids, b->v.step, b->v.samp_ws, b->v.xn, b->v.gather_tmp,
-                    b->v.logits_full, 0};
-}
-
 // all-gather of M rows of vocab-parallel logits into hb.logits_full rows [full_row0, + M)
 static int gather_rows(qie_batch* b, const HeadBufs& hb, int M) {
     qie_engine* e = b->e;
@@ -808,7 +765,7 @@ static int gather_rows(qie_batch* b, const HeadBufs& hb, int M) {
     return 0;
 }
 // ... of the batch's rows [m0, m0 + M)
-static int gather_logits(qie_batch* b, int m0, int M) { return gather_rows(b, batch_head(b, m0), M); }
+static int gather_logits(qie_batch* b, int m0, int M) { return gather_rows(b, head_bufs(b->dec, m0, b->e->sh.vocab), M); }
 
 // the persistent step's words behind its granules: [0] step epoch, [1] error word
 static unsigned* pk_epoch_ptr(const qie_batch* b) {
@@ -862,11 +819,11 @@ static int enqueue_head(qie_batch* b, const uint16_t* x, int64_t ldx, int m0, in
     qie_engine* e = b->e;
     const qie_model_spec& s = e->spec;
     hipStream_t st = e->stream;
-    QIE_TRY(enqueue_head_rows(b, x, ldx, M, smp, batch_head(b, m0)));
+    QIE_TRY(enqueue_head_rows(b, x, ldx, M, smp, head_bufs(b->dec, m0, b->e->sh.vocab)));
     const bool greedy = is_greedy(smp);
-    hipLaunchKernelGGL(finalize_kernel, dim3(M), dim3(256), 0, st, m0, greedy ? b->d_keys : nullptr,
-                       b->d_ids, b->d_ids, b->d_pos, b->d_step, b->d_hist, b->max_ctx,
-                       (const uint4*)e->w.embed, (uint4*)b->x_res, (int64_t)s.hidden / 8, s.vocab, rope_cur_args(b),
+    hipLaunchKernelGGL(finalize_kernel, dim3(M), dim3(256), 0, st, m0, greedy ? b->dec.keys : nullptr,
+                       b->dec.ids, b->dec.ids, b->dec.pos, b->dec.step, b->dec.hist, b->max_ctx,
+                       (const uint4*)e->w.embed, (uint4*)b->dec.x, (int64_t)s.hidden / 8, s.vocab, rope_cur_args(b),
                        b->pk_mem ? pk_epoch_ptr(b) : nullptr);
     QIE_LAUNCH_CHECK();
     return 0;
@@ -879,8 +836,8 @@ static int pk_splits_target(const qie_batch* b) { (void)b; return 32; }
 
 static int enqueue_layers_persistent(qie_batch* b) {
     qie_engine* e = b->e;
-    return persist_decode_launch(e->spec, b->d_layers, b->d_attp, b->x_res, (unsigned long long*)b->pk_mem,
-                                 pk_epoch_ptr(b), pk_epoch_ptr(b) + 1, b->d_pos, pk_splits_target(b), b->pk_ts,
+    return persist_decode_launch(e->spec, b->d_layers, b->d_attp, b->dec.x, (unsigned long long*)b->pk_mem,
+                                 pk_epoch_ptr(b), pk_epoch_ptr(b) + 1, b->dec.pos, pk_splits_target(b), b->pk_ts,
                                  e->stream);
 }
 
@@ -888,7 +845,7 @@ static int enqueue_decode(qie_batch* b, const qie_sampling* smp) {
     if (pk_on(b)) QIE_TRY(enqueue_layers_persistent(b));
     else
         for (int l = 0; l < b->e->spec.n_layers; l++) QIE_TRY(enqueue_layer_decode(b, l));
-    return enqueue_head(b, b->x_res, b->e->spec.hidden, 0, b->B, smp);
+    return enqueue_head(b, b->dec.x, b->e->spec.hidden, 0, b->B, smp);
 }
 
 // opts.prefill_fp8 (numerics flag): the prefill projections on the block-scaled fp8 MFMA
@@ -908,53 +865,46 @@ static int64_t prefill_attn_ws_bytes(const qie_batch* b, int64_t n, bool extend)
     return qie_attention_workspace_bytes(n, b->e->sh.nq, s.head_dim, b->max_ctx);
 }
 
-static int ensure_prefill_scratch(qie_batch* b, int64_t n, bool extend) {
-    if (n <= b->pf_rows) {
-        // rows fit; the attention workspace is not monotone in n (<= 8 rows run the split
-        // kernel with partials, longer prompts need none; an append's split partials grow
-        // with its rows), so size it for this n and this form
-        const int64_t ws = prefill_attn_ws_bytes(b, n, extend);
-        if (ws > b->pf_attn_ws_bytes) {
-            hipFree(b->pf_attn_ws);
-            b->pf_attn_ws = nullptr;
-            b->pf_attn_ws_bytes = 0;
-            QIE_TRY(dmalloc(&b->pf_attn_ws, (size_t)ws));
-            b->pf_attn_ws_bytes = ws;
-        }
-        return 0;
-    }
-    const qie_model_spec& s = b->e->spec;
-    const TpShard& sh = b->e->sh;
-    const int64_t H = s.hidden, QD = (int64_t)sh.nq * s.head_dim, KD = (int64_t)sh.nkv * s.head_dim;
-    void** olds[] = {(void**)&b->pf_x, (void**)&b->pf_hn, (void**)&b->pf_qkv, (void**)&b->pf_q, (void**)&b->pf_att,
-                     (void**)&b->pf_h, (void**)&b->pf_pos, (void**)&b->pf_ids, &b->pf_attn_ws, (void**)&b->pf_part,
-                     (void**)&b->pf_q8, (void**)&b->pf_e8};
-    for (void** p : olds) {   // nulled as freed: a failed re-allocation below leaves nothing dangling
-        if (*p) hipFree(*p);
-        *p = nullptr;
-    }
-    b->pf_rows = 0;
-    if (use_comm(b->e)) QIE_TRY(dmalloc((void**)&b->pf_part, n * H * 4));
-    QIE_TRY(dmalloc((void**)&b->pf_x, n * H * 2));
-    QIE_TRY(dmalloc((void**)&b->pf_hn, n * H * 2));
-    QIE_TRY(dmalloc((void**)&b->pf_qkv, n * (QD + 2 * KD) * 2));
-    QIE_TRY(dmalloc((void**)&b->pf_q, n * QD * 2));
-    QIE_TRY(dmalloc((void**)&b->pf_att, n * QD * 2));
-    QIE_TRY(dmalloc((void**)&b->pf_h, n * (int64_t)sh.ffn * 2));
-    if (prefill_mx(b->e)) {
-        const int64_t kmax = std::max<int64_t>(std::max<int64_t>(H, QD), sh.ffn);
-        QIE_TRY(dmalloc((void**)&b->pf_q8, n * kmax));
-        QIE_TRY(dmalloc((void**)&b->pf_e8, std::max<int64_t>(n, 16)));
-    }
-    QIE_TRY(dmalloc((void**)&b->pf_pos, n * 4));
-    QIE_TRY(dmalloc((void**)&b->pf_ids, n * 4));
-    b->pf_attn_ws = nullptr;
-    b->pf_attn_ws_bytes = 0;
-    int64_t ws = prefill_attn_ws_bytes(b, n, extend);
-    QIE_TRY(dmalloc(&b->pf_attn_ws, (size_t)ws));
-    b->pf_attn_ws_bytes = ws;
-    b->pf_rows = n;
+// The shared dimensions of a block of `rows` rows on this rank; the caller adds the workspace
+// byte counts its set carves
+static RowDims row_dims(const qie_engine* e, int64_t rows) {
+    const qie_model_spec& s = e->spec;
+    RowDims d;
+    d.rows = rows;
+    d.H = s.hidden, d.QD = (int64_t)e->sh.nq * s.head_dim, d.KD = (int64_t)e->sh.nkv * s.head_dim;
+    d.I = e->sh.ffn, d.Vl = e->sh.vocab, d.V = s.vocab;
+    d.exchange = use_comm(e);
+    return d;
+}
+
+// One allocation for what `list(carver, rows)` names: the listing runs for the size, then for
+// the pointers.  `r` is written only once the allocation exists.
+template <class Rows, class List>
+static int alloc_rows(Rows& r, int64_t rows, List list) {
+    Carver c;
+    list(c, r);
+    void* mem = nullptr;
+    QIE_TRY(dmalloc(&mem, c.off));
+    c = Carver{(char*)mem};
+    list(c, r);
+    r.mem = mem, r.bytes = c.off, r.rows = rows;
     return 0;
+}
+template <class Rows>
+static void free_rows(Rows& r) {
+    if (r.mem) hipFree(r.mem);
+    r = Rows{};
+}
+
+// The growable blocks: the old block is freed (and nulled) BEFORE the new one is made, so the
+// peak does not double and a failed allocation leaves rows == 0 and nothing dangling.  Not zeroed.
+static int ensure_prefill_scratch(qie_batch* b, int64_t n, bool extend) {
+    if (n > b->pf.rows) {
+        free_rows(b->pf);
+        const RowDims d = row_dims(b->e, n);
+        QIE_TRY(alloc_rows(b->pf, n, [&](Carver& c, PrefillRows& r) { carve_prefill(c, r, d, prefill_mx(b->e)); }));
+    }
+    return b->pf_ws.grow((size_t)prefill_attn_ws_bytes(b, n, extend));
 }
 
 // The persistent step's error word (a bounded hand-off wait that gave up): the step's outputs
@@ -989,7 +939,7 @@ static int read_back(qie_batch* b, void* dst, const void* src, size_t bytes, con
 }
 
 static int sync_ids(qie_batch* b, int32_t* next_ids) {
-    return next_ids ? read_back(b, next_ids, b->d_ids, (size_t)b->B * 4, "decode") : pk_check(b);
+    return next_ids ? read_back(b, next_ids, b->dec.ids, (size_t)b->B * 4, "decode") : pk_check(b);
 }
 
 }  // namespace qie
@@ -1356,7 +1306,7 @@ static int batch_create(qie_engine* e, int32_t batch, int32_t max_ctx, int32_t p
     b->B = batch;
     b->max_ctx = max_ctx;
     const TpShard& sh = e->sh;
-    const int64_t H = s.hidden, hd = s.head_dim, QD = (int64_t)sh.nq * hd, KD = (int64_t)sh.nkv * hd;
+    const int64_t hd = s.head_dim;
     int64_t n_runs = batch;   // sequences (contiguous) or pages (paged) in the K and V pools
     if (page_tokens > 0) {
         b->page_tokens = page_tokens;
@@ -1376,58 +1326,32 @@ static int batch_create(qie_engine* e, int32_t batch, int32_t max_ctx, int32_t p
     // set_position, so unused slots never take pool pages (they run on scratch page 0)
     // and are rewound before they would pass max_ctx (prepare_steps).
     b->idle.assign(batch, 1);
-    int rc = 0;
-    auto A = [&](void** p, size_t bytes) {
-        if (!rc) rc = dmalloc(p, bytes);
-    };
-    A((void**)&b->kc, (size_t)n_runs * b->seq_stride * 2);
-    A((void**)&b->vc, (size_t)n_runs * b->seq_stride * 2);
-    if (page_tokens > 0) A((void**)&b->d_table, b->h_table.size() * 4);
-    A((void**)&b->d_pos, batch * 4);
-    A((void**)&b->d_rope_cur, (size_t)batch * rope_cur_stride((int)hd) * 4);
-    A((void**)&b->d_step, batch * 4);
-    A((void**)&b->d_hist, (size_t)batch * max_ctx * 4);
-    A((void**)&b->d_ids, batch * 4);
-    A((void**)&b->d_keys, batch * 8);
-    A((void**)&b->x_res, batch * H * 2);
-    A((void**)&b->qkv, batch * (QD + 2 * KD) * 2);
-    A((void**)&b->q, batch * QD * 2);
-    A((void**)&b->att, batch * QD * 2);
-    A((void**)&b->h, batch * (int64_t)sh.ffn * 2);
-    A((void**)&b->xn, batch * H * 2);
-    A((void**)&b->logits, batch * (int64_t)sh.vocab * 2);
-    A(&b->attn_ws, (size_t)qie_attention_workspace_bytes(batch, sh.nq, s.head_dim, max_ctx));
-    A(&b->samp_ws, (size_t)qie_sample_workspace_bytes(batch, s.vocab));
-    const int64_t dec_ws = qie_attention_decode_workspace_bytes(batch, sh.nq, sh.nkv, s.head_dim, max_ctx);
-    A(&b->dec_ws, (size_t)dec_ws);
-    if (use_comm(e)) {
-        A((void**)&b->part, batch * H * 4);
-        A((void**)&b->logits_full, batch * (int64_t)s.vocab * 2);
-        A((void**)&b->gather_tmp, batch * (int64_t)s.vocab * 2);
-    }
-    if (!rc) {
-        hipMemsetAsync(b->dec_ws, 0, (size_t)dec_ws, e->stream);
-        hipMemsetAsync(b->kc, 0, (size_t)n_runs * b->seq_stride * 2, e->stream);
-        hipMemsetAsync(b->vc, 0, (size_t)n_runs * b->seq_stride * 2, e->stream);
-        hipMemsetAsync(b->d_keys, 0, batch * 8, e->stream);
-        hipMemsetAsync(b->d_pos, 0, batch * 4, e->stream);
-        hipMemsetAsync(b->d_rope_cur, 0xff, (size_t)batch * rope_cur_stride((int)hd) * 4, e->stream);   // tags -1
-        hipMemsetAsync(b->d_step, 0, batch * 4, e->stream);
-        hipMemsetAsync(b->d_ids, 0, batch * 4, e->stream);
-        hipMemsetAsync(b->d_hist, 0, (size_t)batch * max_ctx * 4, e->stream);
-        hipMemsetAsync(b->x_res, 0, batch * H * 2, e->stream);
-        hipError_t he = hipStreamSynchronize(e->stream);
-        if (he != hipSuccess) rc = fail((int)he, "batch init: %s", hipGetErrorString(he));
-    }
-    if (rc) {
-        qie_batch_destroy(b);
-        return rc;
-    }
     b->h_pos.assign(batch, 0);
-    if (!rc) rc = flush_table(b);
-    // the fp8 batched-decode split-K workspace of this stream, before any graph capture
-    if (!rc && e->fp8 && (batch >= 2 || e->fp8_t16)) rc = dec8_reserve(e->stream);
-    if (rc) {
+    // the KV pools, the block table, and the slots' rows: one block, zero but for the RoPE rows'
+    // tags (-1: no position).  Never reallocated: the decode graph and the persistent step's
+    // attention table hold pointers into it.
+    auto make = [&]() -> int {
+        const size_t pool = (size_t)n_runs * b->seq_stride * 2;
+        QIE_TRY(dmalloc((void**)&b->kc, pool));
+        QIE_TRY(dmalloc((void**)&b->vc, pool));
+        if (page_tokens > 0) QIE_TRY(dmalloc((void**)&b->d_table, b->h_table.size() * 4));
+        RowDims d = row_dims(e, batch);
+        d.samp_ws_bytes = qie_sample_workspace_bytes(batch, s.vocab);
+        const int64_t rc_floats = rope_cur_stride((int)hd);
+        const int64_t dec_ws = qie_attention_decode_workspace_bytes(batch, sh.nq, sh.nkv, s.head_dim, max_ctx);
+        QIE_TRY(alloc_rows(b->dec, batch,
+                           [&](Carver& c, DecodeRows& r) { carve_decode(c, r, d, max_ctx, rc_floats, dec_ws); }));
+        QIE_HIP(hipMemsetAsync(b->kc, 0, pool, e->stream));
+        QIE_HIP(hipMemsetAsync(b->vc, 0, pool, e->stream));
+        QIE_HIP(hipMemsetAsync(b->dec.mem, 0, b->dec.bytes, e->stream));
+        QIE_HIP(hipMemsetAsync(b->dec.rope_cur, 0xff, (size_t)batch * rc_floats * 4, e->stream));
+        QIE_HIP(hipStreamSynchronize(e->stream));
+        QIE_TRY(flush_table(b));
+        // the fp8 batched-decode split-K workspace of this stream, before any graph capture
+        if (e->fp8 && (batch >= 2 || e->fp8_t16)) QIE_TRY(dec8_reserve(e->stream));
+        return 0;
+    };
+    if (const int rc = make()) {
         qie_batch_destroy(b);
         return rc;
     }
@@ -1455,8 +1379,8 @@ int qie_batch_release(qie_batch* b, int32_t seq) {
     b->idle[seq] = 1;
     QIE_TRY(flush_table(b));
     qie_engine* e = b->e;
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(256), 0, e->stream, seq, 0, 0, 0, b->d_pos, b->d_step, b->d_hist,
-                       b->max_ctx, (const uint4*)e->w.embed, (uint4*)b->x_res, (int64_t)e->spec.hidden / 8, 1, rope_cur_args(b));
+    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(256), 0, e->stream, seq, 0, 0, 0, b->dec.pos, b->dec.step, b->dec.hist,
+                       b->max_ctx, (const uint4*)e->w.embed, (uint4*)b->dec.x, (int64_t)e->spec.hidden / 8, 1, rope_cur_args(b));
     QIE_LAUNCH_CHECK();
     QIE_HIP(hipStreamSynchronize(e->stream));
     b->h_pos[seq] = 0;
@@ -1485,14 +1409,14 @@ void qie_batch_destroy(qie_batch* b) {
     if (b->e && b->e->stream) hipStreamSynchronize(b->e->stream);
     if (b->gexec) hipGraphExecDestroy(b->gexec);
     for (auto& g : b->v_graphs) hipGraphExecDestroy(g.exec);
-    if (b->v.mem) hipFree(b->v.mem);
-    void* ps[] = {b->kc, b->vc, b->d_table, b->d_pos, b->d_rope_cur, b->d_step, b->d_hist, b->d_ids, b->d_keys, b->x_res, b->qkv, b->q,
-                  b->att, b->h, b->logits, b->attn_ws, b->dec_ws, b->samp_ws, b->pf_x, b->pf_hn, b->pf_qkv, b->pf_q,
-                  b->pf_att, b->pf_h, b->pf_pos, b->pf_ids, b->pf_attn_ws, b->part, b->logits_full,
-                  b->gather_tmp, b->pf_part, b->xn, b->pf_q8, b->pf_e8, b->pk_mem, b->d_layers, b->d_attp, b->pk_ts,
-                  b->sc.tgt, b->sc.ids, b->sc.lp, b->sc.ws};
-    for (void* p : ps)
+    free_rows(b->dec);
+    free_rows(b->pf);
+    free_rows(b->v);
+    free_rows(b->sc);
+    for (void* p : {(void*)b->kc, (void*)b->vc, (void*)b->d_table, b->pk_mem, (void*)b->d_layers, b->d_attp,
+                    (void*)b->pk_ts})
         if (p) hipFree(p);
+    // (the DevBlock workspaces free themselves)
     delete b;
 }
 
@@ -1513,32 +1437,15 @@ static bool score_fused(const qie_engine* e, int flags) {
 static int ensure_verify_bufs(qie_batch* b);
 
 static int ensure_score_scratch(qie_batch* b, int64_t n, bool fused) {
-    qie_batch::ScoreBufs& sc = b->sc;
-    if (n > sc.rows) {
-        void** olds[] = {(void**)&sc.tgt, (void**)&sc.ids, (void**)&sc.lp};
-        for (void** p : olds) {
-            if (*p) hipFree(*p);
-            *p = nullptr;
-        }
-        sc.rows = 0;
-        QIE_TRY(dmalloc((void**)&sc.tgt, n * 4));
-        QIE_TRY(dmalloc((void**)&sc.ids, n * 4));
-        QIE_TRY(dmalloc((void**)&sc.lp, n * 4));
-        sc.rows = n;
+    if (n > b->sc.rows) {
+        free_rows(b->sc);
+        QIE_TRY(alloc_rows(b->sc, n, [&](Carver& c, ScoreRows& r) { carve_score(c, r, n); }));
     }
-    const int64_t ws = fused ? qie_score_rows_workspace_bytes(n, b->e->spec.vocab) : 0;
-    if (ws > sc.ws_bytes) {
-        if (sc.ws) hipFree(sc.ws);
-        sc.ws = nullptr;
-        sc.ws_bytes = 0;
-        QIE_TRY(dmalloc(&sc.ws, (size_t)ws));
-        sc.ws_bytes = ws;
-    }
-    return 0;
+    return fused ? b->sc_ws.grow((size_t)qie_score_rows_workspace_bytes(n, b->e->spec.vocab)) : 0;
 }
 
-// The scoring head over the n rows of b->pf_x a prefill of slot `seq` has just run (after its own
-// last-row head, which is left as it is).  Fused: final norm of all rows into pf_hn (free after
+// The scoring head over the n rows of b->pf.x a prefill of slot `seq` has just run (after its own
+// last-row head, which is left as it is).  Fused: final norm of all rows into pf.xn (free after
 // the layer loop), then qie_score_rows.  General (fp8 heads, the exchange path, QIE_SCORE_UNFUSED):
 // rows [0, n - 1) in pieces of <= kVerifyMaxRows through the head launch of decode and qie_verify
 // into the verify step's logit rows, qie_logprob_rows on each piece; row n - 1 from the batch's
@@ -1550,13 +1457,13 @@ static int enqueue_score(qie_batch* b, int seq, int n, const ScoreReq& rq) {
     const int64_t H = s.hidden, V = s.vocab;
     QIE_HIP(hipMemcpyAsync(b->sc.tgt, rq.targets, (size_t)n * 4, hipMemcpyHostToDevice, st));
     if (score_fused(e, rq.flags)) {
-        QIE_TRY(qie_rmsnorm(b->pf_x, e->w.final_norm, b->pf_hn, n, H, s.rms_eps, s.numerics, st));
-        return qie_score_rows(b->pf_hn, H, e->w.lm_head, n, H, V, b->sc.tgt, b->sc.lp, b->sc.ids, b->sc.ws, st);
+        QIE_TRY(qie_rmsnorm(b->pf.x, e->w.final_norm, b->pf.xn, n, H, s.rms_eps, s.numerics, st));
+        return qie_score_rows(b->pf.xn, H, e->w.lm_head, n, H, V, b->sc.tgt, b->sc.lp, b->sc.ids, b->sc_ws.p, st);
     }
-    const HeadBufs hb = verify_head(b);
+    const HeadBufs hb = head_bufs(b->v, 0, b->e->sh.vocab);
     for (int r0 = 0; r0 < n - 1; r0 += kVerifyMaxRows) {
         const int M = std::min(kVerifyMaxRows, n - 1 - r0);
-        qie_linear_args a = head_args(e, b->pf_x + (int64_t)r0 * H, H, M, false, hb);
+        qie_linear_args a = head_args(e, b->pf.x + (int64_t)r0 * H, H, M, false, hb);
         QIE_TRY(prenorm(b, a, hb.xn));
         QIE_TRY(linear(&a, LinearExtras{}, st));
         const uint16_t* lg = hb.logits;
@@ -1567,10 +1474,10 @@ static int enqueue_score(qie_batch* b, int seq, int n, const ScoreReq& rq) {
         QIE_TRY(qie_logprob_rows(lg, M, V, V, b->sc.tgt + r0, b->sc.lp + r0, b->sc.ids + r0, st));
     }
     b->v_rows = 0;   // the verify step's logit rows no longer hold a qie_verify's
-    const uint16_t* last = b->logits + (int64_t)seq * e->sh.vocab;
+    const uint16_t* last = b->dec.logits + (int64_t)seq * e->sh.vocab;
     if (use_comm(e)) {
         QIE_TRY(gather_logits(b, seq, 1));
-        last = b->logits_full + (int64_t)seq * V;
+        last = b->dec.logits_full + (int64_t)seq * V;
     }
     return qie_logprob_rows(last, 1, V, V, b->sc.tgt + (n - 1), b->sc.lp + (n - 1), b->sc.ids + (n - 1), st);
 }
@@ -1645,13 +1552,13 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
     }
     QIE_TRY(flush_table(b));
     const int64_t H = s.hidden;
-    QIE_HIP(hipMemcpyAsync(b->pf_ids, ids, (size_t)n * 4, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b->pf_pos, (int)n, len, pos0);
-    hipLaunchKernelGGL(copy_ids_kernel, dim3((len + 255) / 256, n_seqs), dim3(256), 0, st, b->pf_ids,
-                       b->d_hist + (int64_t)seq0 * b->max_ctx + pos0, len, (int64_t)b->max_ctx);
-    QIE_TRY(qie_embedding(e->w.embed, b->pf_ids, b->pf_x, n, H, st));
+    QIE_HIP(hipMemcpyAsync(b->pf.ids_in, ids, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b->pf.pos, (int)n, len, pos0);
+    hipLaunchKernelGGL(copy_ids_kernel, dim3((len + 255) / 256, n_seqs), dim3(256), 0, st, b->pf.ids_in,
+                       b->dec.hist + (int64_t)seq0 * b->max_ctx + pos0, len, (int64_t)b->max_ctx);
+    QIE_TRY(qie_embedding(e->w.embed, b->pf.ids_in, b->pf.x, n, H, st));
     const qie_kv_cache cache = batch_cache(b, seq0);
-    const LayerRows r{n, b->pf_x, b->pf_hn, b->pf_qkv, b->pf_q, b->pf_att, b->pf_h, b->pf_part, b->pf_pos, len};
+    const LayerRows r = layer_rows(b->pf, n, len);
     // opts.prefill_fp8: every projection on fp8 codes x fp8 weights (e->layers: the fp8 arena).
     // Otherwise bf16 rows; on an fp8 engine at >= 256 rows the GEMMs run on the dequantised bf16
     // copy (layers_pf), and with tiled fp8 projections (readable by the batched-decode kernel
@@ -1661,25 +1568,25 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
     if (pf16 && path.in == InputForm::Normed)
         path = LayerPath{e->layers_pf.data(), path.flags & ~(QIE_LINEAR_FP8 | QIE_LINEAR_FP8_T16), InputForm::Normed};
     for (int l = 0; l < s.n_layers; l++)
-        QIE_TRY(enqueue_layer_rows(b, l, r, path, cache, append ? qie_attention_extend : qie_attention, b->pf_attn_ws));
+        QIE_TRY(enqueue_layer_rows(b, l, r, path, cache, append ? qie_attention_extend : qie_attention, b->pf_ws.p));
     // position of each last prompt token; finalize advances it to pos0 + len (the new token).
     for (int z = 0; z < n_seqs; z++) {
         hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(64), 0, st, seq0 + z, pos0 + len - 1, 0,
-                           ids[(int64_t)z * len + len - 1], b->d_pos, b->d_step, b->d_hist, b->max_ctx,
-                           (const uint4*)e->w.embed, (uint4*)b->x_res, (int64_t)H / 8, 0, rope_cur_args(b));
+                           ids[(int64_t)z * len + len - 1], b->dec.pos, b->dec.step, b->dec.hist, b->max_ctx,
+                           (const uint4*)e->w.embed, (uint4*)b->dec.x, (int64_t)H / 8, 0, rope_cur_args(b));
         QIE_LAUNCH_CHECK();
     }
-    const uint16_t* last = b->pf_x + (int64_t)(len - 1) * H;
+    const uint16_t* last = b->pf.x + (int64_t)(len - 1) * H;
     if (n_seqs > 1) {   // the last rows, packed (the head's pre-norm reads contiguous rows)
-        QIE_HIP(hipMemcpy2DAsync(b->pf_hn, (size_t)H * 2, last, (size_t)len * H * 2, (size_t)H * 2, n_seqs,
+        QIE_HIP(hipMemcpy2DAsync(b->pf.xn, (size_t)H * 2, last, (size_t)len * H * 2, (size_t)H * 2, n_seqs,
                                  hipMemcpyDeviceToDevice, st));
-        last = b->pf_hn;
+        last = b->pf.xn;
     }
     QIE_TRY(enqueue_head(b, last, H, seq0, n_seqs, smp));
     for (int z = 0; z < n_seqs; z++) b->h_pos[seq0 + z] = pos0 + len;
     if (score) QIE_TRY(enqueue_score(b, seq0, len, *score));
     if (next_ids) {
-        QIE_HIP(hipMemcpyAsync(next_ids, b->d_ids + seq0, (size_t)n_seqs * 4, hipMemcpyDeviceToHost, st));
+        QIE_HIP(hipMemcpyAsync(next_ids, b->dec.ids + seq0, (size_t)n_seqs * 4, hipMemcpyDeviceToHost, st));
         QIE_HIP(hipStreamSynchronize(st));
         QIE_TRY(comm_check(e, who));
     }
@@ -1721,10 +1628,10 @@ int qie_batch_logprobs(qie_batch* b, const int32_t* ids, float* out) {
         QIE_REQUIRE(ids[m] >= -1 && ids[m] < V, "qie_batch_logprobs: id %d of slot %d is neither -1 nor a token id",
                     ids[m], m);
     QIE_TRY(ensure_score_scratch(b, b->B, false));
-    const uint16_t* src = b->logits;
+    const uint16_t* src = b->dec.logits;
     if (use_comm(e)) {   // collective: every rank calls this at the same point
         QIE_TRY(gather_logits(b, 0, b->B));
-        src = b->logits_full;
+        src = b->dec.logits_full;
     }
     QIE_HIP(hipMemcpyAsync(b->sc.tgt, ids, (size_t)b->B * 4, hipMemcpyHostToDevice, e->stream));
     QIE_TRY(qie_logprob_rows(src, b->B, V, V, b->sc.tgt, b->sc.lp, nullptr, e->stream));
@@ -1821,8 +1728,8 @@ static int prepare_steps(qie_batch* b, int n_steps, const char* who) {
     qie_engine* e = b->e;
     for (int m = 0; m < b->B; m++)
         if (b->idle[m] && b->h_pos[m] + n_steps >= b->max_ctx) {
-            hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(256), 0, e->stream, m, 0, 0, 0, b->d_pos, b->d_step,
-                               b->d_hist, b->max_ctx, (const uint4*)e->w.embed, (uint4*)b->x_res,
+            hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(256), 0, e->stream, m, 0, 0, 0, b->dec.pos, b->dec.step,
+                               b->dec.hist, b->max_ctx, (const uint4*)e->w.embed, (uint4*)b->dec.x,
                                (int64_t)e->spec.hidden / 8, 1, rope_cur_args(b));
             QIE_LAUNCH_CHECK();
             b->h_pos[m] = 0;
@@ -1852,7 +1759,7 @@ int qie_decode(qie_batch* b, int32_t n_steps, const qie_sampling* smp, int32_t* 
     if (out_ids && n_steps > 0) {
         std::vector<int32_t> row(b->max_ctx);
         for (int m = 0; m < b->B; m++) {
-            QIE_HIP(d2h(b->e, row.data(), b->d_hist + (int64_t)m * b->max_ctx, (size_t)b->max_ctx * 4));
+            QIE_HIP(d2h(b->e, row.data(), b->dec.hist + (int64_t)m * b->max_ctx, (size_t)b->max_ctx * 4));
             for (int i = 0; i < n_steps; i++) out_ids[(int64_t)i * b->B + m] = row[p0[m] + 1 + i];
         }
     }
@@ -1861,10 +1768,10 @@ int qie_decode(qie_batch* b, int32_t n_steps, const qie_sampling* smp, int32_t* 
 
 int qie_batch_logits(qie_batch* b, void* host_out) {
     QIE_REQUIRE(b && host_out, "qie_batch_logits: bad arguments");
-    const uint16_t* src = b->logits;
+    const uint16_t* src = b->dec.logits;
     if (use_comm(b->e)) {   // collective: every rank calls this at the same point
         QIE_TRY(gather_logits(b, 0, b->B));
-        src = b->logits_full;
+        src = b->dec.logits_full;
     }
     QIE_HIP(hipStreamSynchronize(b->e->stream));
     QIE_TRY(comm_check(b->e, "qie_batch_logits"));
@@ -1876,7 +1783,7 @@ int qie_batch_logits(qie_batch* b, void* host_out) {
 int qie_batch_positions(qie_batch* b, int32_t* host_pos) {
     QIE_REQUIRE(b && host_pos, "qie_batch_positions: bad arguments");
     QIE_HIP(hipStreamSynchronize(b->e->stream));
-    QIE_HIP(d2h(b->e, host_pos, b->d_pos, (size_t)b->B * 4));
+    QIE_HIP(d2h(b->e, host_pos, b->dec.pos, (size_t)b->B * 4));
     return 0;
 }
 
@@ -1884,7 +1791,7 @@ int qie_batch_history(qie_batch* b, int32_t seq, int32_t* host_ids, int32_t n) {
     QIE_REQUIRE(b && host_ids && seq >= 0 && seq < b->B && n >= 0 && n <= b->max_ctx,
                 "qie_batch_history: bad arguments");
     QIE_HIP(hipStreamSynchronize(b->e->stream));
-    QIE_HIP(d2h(b->e, host_ids, b->d_hist + (int64_t)seq * b->max_ctx, (size_t)n * 4));
+    QIE_HIP(d2h(b->e, host_ids, b->dec.hist + (int64_t)seq * b->max_ctx, (size_t)n * 4));
     return 0;
 }
 
@@ -1896,8 +1803,8 @@ int qie_batch_set_position(qie_batch* b, int32_t seq, int32_t pos, int32_t token
     QIE_TRY(flush_table(b));
     b->idle[seq] = 0;
     qie_engine* e = b->e;
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(256), 0, e->stream, seq, pos, pos, token, b->d_pos, b->d_step,
-                       b->d_hist, b->max_ctx, (const uint4*)e->w.embed, (uint4*)b->x_res,
+    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(256), 0, e->stream, seq, pos, pos, token, b->dec.pos, b->dec.step,
+                       b->dec.hist, b->max_ctx, (const uint4*)e->w.embed, (uint4*)b->dec.x,
                        (int64_t)e->spec.hidden / 8, 1, rope_cur_args(b));
     QIE_LAUNCH_CHECK();
     QIE_HIP(hipStreamSynchronize(e->stream));
@@ -1906,60 +1813,24 @@ int qie_batch_set_position(qie_batch* b, int32_t seq, int32_t pos, int32_t token
 }
 
 // ------------------------------------------------------------ speculative verify
-// The step's row buffers, once per batch at kVerifyMaxRows rows: one allocation carved into
-// 256-byte aligned pieces, so a failure leaves nothing behind and captured steps keep valid
-// pointers for the batch's lifetime.
+// The step's rows, once per batch at kVerifyMaxRows rows and never reallocated: captured steps
+// (and the unfused scoring path) keep valid pointers for the batch's lifetime.
 static int ensure_verify_bufs(qie_batch* b) {
     if (b->v.mem) return 0;
     qie_engine* e = b->e;
-    const qie_model_spec& s = e->spec;
-    const TpShard& sh = e->sh;
-    const int64_t R = kVerifyMaxRows, H = s.hidden, QD = (int64_t)sh.nq * s.head_dim, KD = (int64_t)sh.nkv * s.head_dim;
-    const bool comm = use_comm(e);
-    qie_batch::VerifyBufs v;
-    size_t off = 0;
-    char* base = nullptr;
-    auto take = [&](auto** p, int64_t bytes) {
-        if (base) *p = reinterpret_cast<std::remove_reference_t<decltype(*p)>>(base + off);
-        off += ((size_t)std::max<int64_t>(bytes, 16) + 255) / 256 * 256;
-    };
-    auto carve = [&]() {
-        off = 0;
-        take(&v.x, R * H * 2);
-        take(&v.xn, R * H * 2);
-        take(&v.qkv, R * (QD + 2 * KD) * 2);
-        take(&v.q, R * QD * 2);
-        take(&v.att, R * QD * 2);
-        take(&v.h, R * (int64_t)sh.ffn * 2);
-        take(&v.logits, R * (int64_t)sh.vocab * 2);
-        take(&v.attn_ws, qie_attention_extend_workspace_bytes(R, sh.nq, s.head_dim, b->max_ctx + b->run_pad));
-        take(&v.samp_ws, qie_sample_workspace_bytes(R, s.vocab));
-        take(&v.keys, R * 8);
-        take(&v.ids, R * 4);
-        take(&v.pos, R * 4);
-        take(&v.step, R * 4);
-        take(&v.draft, R * 4);
-        take(&v.res, (R + 1) * 4);
-        if (comm) {
-            take(&v.part, R * H * 4);
-            take(&v.logits_full, R * (int64_t)s.vocab * 2);
-            take(&v.gather_tmp, R * (int64_t)s.vocab * 2);
-        }
-    };
-    carve();   // sizes
-    void* mem = nullptr;
-    QIE_TRY(dmalloc(&mem, off));
-    base = (char*)mem;
-    carve();   // pointers
-    v.mem = mem;
+    RowDims d = row_dims(e, kVerifyMaxRows);
+    d.attn_ws_bytes = qie_attention_extend_workspace_bytes(d.rows, e->sh.nq, e->spec.head_dim, b->max_ctx + b->run_pad);
+    d.samp_ws_bytes = qie_sample_workspace_bytes(d.rows, e->spec.vocab);
+    VerifyRows v;
+    QIE_TRY(alloc_rows(v, d.rows, [&](Carver& c, VerifyRows& r) { carve_verify(c, r, d); }));
     // key slots start zero (the commit kernel leaves them so); the fp8 batched-decode kernel's
     // split-K workspace must exist before a capture (batch 1 never made it for M = 1)
-    hipError_t he = hipMemsetAsync(mem, 0, off, e->stream);
+    hipError_t he = hipMemsetAsync(v.mem, 0, v.bytes, e->stream);
     if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
     int rc = he == hipSuccess ? 0 : fail((int)he, "qie_verify: buffer init: %s", hipGetErrorString(he));
     if (!rc && e->fp8) rc = dec8_reserve(e->stream);
     if (rc) {
-        hipFree(mem);
+        hipFree(v.mem);
         return rc;
     }
     b->v = v;
@@ -1972,19 +1843,19 @@ static int enqueue_verify(qie_batch* b, int seq, int M, const qie_sampling* smp)
     const qie_model_spec& s = e->spec;
     hipStream_t st = e->stream;
     const int64_t H8 = (int64_t)s.hidden / 8;
-    VerifyRowsArgs ra{seq, M, b->v.draft, s.vocab, (const uint4*)e->w.embed, (const uint4*)b->x_res, H8,
-                      b->d_pos, b->d_step, (uint4*)b->v.x, b->v.pos, b->v.step};
+    VerifyRowsArgs ra{seq, M, b->v.draft, s.vocab, (const uint4*)e->w.embed, (const uint4*)b->dec.x, H8,
+                      b->dec.pos, b->dec.step, (uint4*)b->v.x, b->v.pos, b->v.step};
     QIE_TRY(launch_verify_rows(ra, st));
     const qie_kv_cache cache = batch_cache(b, seq);
     // the M rows of ONE sequence at consecutive positions v.pos, in the decode input form
-    const LayerRows r{M, b->v.x, b->v.xn, b->v.qkv, b->v.q, b->v.att, b->v.h, b->v.part, b->v.pos, M};
+    const LayerRows r = layer_rows(b->v, M, M);
     for (int l = 0; l < s.n_layers; l++)
         QIE_TRY(enqueue_layer_rows(b, l, r, decode_path(e), cache, qie_attention_extend, b->v.attn_ws));
-    QIE_TRY(enqueue_head_rows(b, b->v.x, s.hidden, M, smp, verify_head(b)));
+    QIE_TRY(enqueue_head_rows(b, b->v.x, s.hidden, M, smp, head_bufs(b->v, 0, b->e->sh.vocab)));
     const bool greedy = is_greedy(smp);
-    VerifyCommitArgs ca{seq, M, greedy ? b->v.keys : nullptr, b->v.ids, b->v.draft, s.vocab, b->d_pos, b->d_step,
-                        b->d_hist, b->max_ctx, b->d_ids, (const uint4*)e->w.embed, (uint4*)b->x_res, H8,
-                        rope_cur_args(b), b->v.logits, b->logits, (int64_t)e->sh.vocab, b->v.res};
+    VerifyCommitArgs ca{seq, M, greedy ? b->v.keys : nullptr, b->v.ids, b->v.draft, s.vocab, b->dec.pos, b->dec.step,
+                        b->dec.hist, b->max_ctx, b->dec.ids, (const uint4*)e->w.embed, (uint4*)b->dec.x, H8,
+                        rope_cur_args(b), b->v.logits, b->dec.logits, (int64_t)e->sh.vocab, b->v.res};
     return launch_verify_commit(ca, st);
 }
 
@@ -2057,7 +1928,7 @@ int qie_verify_logits(qie_batch* b, void* host_out) {
     qie_engine* e = b->e;
     const uint16_t* src = b->v.logits;
     if (use_comm(e)) {   // collective: every rank calls this at the same point
-        QIE_TRY(gather_rows(b, verify_head(b), b->v_rows));
+        QIE_TRY(gather_rows(b, head_bufs(b->v, 0, b->e->sh.vocab), b->v_rows));
         src = b->v.logits_full;
     }
     QIE_HIP(hipStreamSynchronize(e->stream));
@@ -2097,9 +1968,9 @@ int qie_batch_set_decode_mode(qie_batch* b, int32_t mode) {
             QIE_HIP(hipMemcpyAsync(b->d_layers, e->layers.data(), sizeof(qie_layer_weights) * e->layers.size(),
                                    hipMemcpyHostToDevice, e->stream));
             const qie_kv_cache cache = batch_cache(b, 0);
-            set_decode_rope_cur(b->d_rope_cur);
-            const int rc = persist_attn_table(e->spec, e->layers.data(), b->qkv, b->d_pos, e->rope_cos, e->rope_sin,
-                                              &cache, b->dec_ws, b->d_attp, e->stream);
+            set_decode_rope_cur(b->dec.rope_cur);
+            const int rc = persist_attn_table(e->spec, e->layers.data(), b->dec.qkv, b->dec.pos, e->rope_cos, e->rope_sin,
+                                              &cache, b->dec.dec_ws, b->d_attp, e->stream);
             set_decode_rope_cur(nullptr);
             QIE_TRY(rc);
             QIE_HIP(hipStreamSynchronize(e->stream));
@@ -2183,6 +2054,28 @@ int qie_engine_rope_tables(const qie_engine* e, const float** rope_cos, const fl
 // real epoch advanced past them afterwards, and the KV rows the launches wrote at the current
 // position are rewritten by the next real step.  Bytes: every layer weight read once plus the
 // K / V rows the attention reads.
+// `warm` untimed launches run(0 ..), then `iters` timed ones run(0 ..) between two events on the
+// stream: the mean per launch.  The events are destroyed on every path.
+static int time_launches(hipStream_t st, const std::function<int(int)>& run, int warm, int iters, double* avg_us) {
+    struct Event {
+        hipEvent_t ev = nullptr;
+        ~Event() {
+            if (ev) hipEventDestroy(ev);
+        }
+    } t0, t1;
+    QIE_HIP(hipEventCreate(&t0.ev));
+    QIE_HIP(hipEventCreate(&t1.ev));
+    for (int i = 0; i < warm; i++) QIE_TRY(run(i));
+    QIE_HIP(hipEventRecord(t0.ev, st));
+    for (int i = 0; i < iters; i++) QIE_TRY(run(i));
+    QIE_HIP(hipEventRecord(t1.ev, st));
+    QIE_HIP(hipEventSynchronize(t1.ev));
+    float ms = 0;
+    QIE_HIP(hipEventElapsedTime(&ms, t0.ev, t1.ev));
+    *avg_us = ms * 1000.0 / iters;
+    return 0;
+}
+
 static int time_persistent(qie_batch* b, int iters, double* avg_us, double* bytes) {
     qie_engine* e = b->e;
     const qie_model_spec& s = e->spec;
@@ -2191,47 +2084,35 @@ static int time_persistent(qie_batch* b, int iters, double* avg_us, double* byte
                   I = s.ffn;
     int32_t pos = 0;
     unsigned ep = 0;
-    QIE_HIP(d2h(e, &pos, b->d_pos, 4));
+    QIE_HIP(d2h(e, &pos, b->dec.pos, 4));
     QIE_HIP(d2h(e, &ep, pk_epoch_ptr(b), 4));
     const int n = iters + 4;
     std::vector<unsigned> eps(n);
     for (int i = 0; i < n; i++) eps[i] = ep + 1 + (unsigned)i;
-    unsigned* d_eps = nullptr;
-    uint16_t* xsave = nullptr;
-    QIE_TRY(dmalloc((void**)&d_eps, n * 4));
-    QIE_TRY(dmalloc((void**)&xsave, H * 2));
-    QIE_HIP(hipMemcpyAsync(d_eps, eps.data(), n * 4, hipMemcpyHostToDevice, e->stream));
-    QIE_HIP(hipMemcpyAsync(xsave, b->x_res, H * 2, hipMemcpyDeviceToDevice, e->stream));
+    DevBlock eps_mem, xsave;
+    QIE_TRY(eps_mem.grow((size_t)n * 4));
+    QIE_TRY(xsave.grow((size_t)H * 2));
+    const unsigned* d_eps = (const unsigned*)eps_mem.p;
+    QIE_HIP(hipMemcpyAsync(eps_mem.p, eps.data(), n * 4, hipMemcpyHostToDevice, e->stream));
+    QIE_HIP(hipMemcpyAsync(xsave.p, b->dec.x, H * 2, hipMemcpyDeviceToDevice, e->stream));
     // launches back to back on the same input: x_res is only read at layer 0 and written at the
-    // last layer, so each launch sees a row of the same magnitude (restored afterwards)
-    auto run = [&](int i) {
-        return persist_decode_launch(s, b->d_layers, b->d_attp, b->x_res, (unsigned long long*)b->pk_mem, d_eps + i,
-                                     pk_epoch_ptr(b) + 1, b->d_pos, pk_splits_target(b), nullptr, e->stream);
+    // last layer, so each launch sees a row of the same magnitude (restored afterwards); every
+    // launch, warm-up included, takes the next fresh epoch
+    int k = 0;
+    auto run = [&](int) {
+        return persist_decode_launch(s, b->d_layers, b->d_attp, b->dec.x, (unsigned long long*)b->pk_mem, d_eps + k++,
+                                     pk_epoch_ptr(b) + 1, b->dec.pos, pk_splits_target(b), nullptr, e->stream);
     };
-    hipEvent_t t0, t1;
-    QIE_HIP(hipEventCreate(&t0));
-    QIE_HIP(hipEventCreate(&t1));
-    for (int i = 0; i < 4; i++) QIE_TRY(run(i));
-    QIE_HIP(hipEventRecord(t0, e->stream));
-    for (int i = 0; i < iters; i++) QIE_TRY(run(4 + i));
-    QIE_HIP(hipEventRecord(t1, e->stream));
-    QIE_HIP(hipEventSynchronize(t1));
-    float ms = 0;
-    QIE_HIP(hipEventElapsedTime(&ms, t0, t1));
-    hipEventDestroy(t0);
-    hipEventDestroy(t1);
+    QIE_TRY(time_launches(e->stream, run, 4, iters, avg_us));
     const unsigned ep_after = ep + (unsigned)n + 1;
-    QIE_HIP(hipMemcpyAsync(b->x_res, xsave, H * 2, hipMemcpyDeviceToDevice, e->stream));
+    QIE_HIP(hipMemcpyAsync(b->dec.x, xsave.p, H * 2, hipMemcpyDeviceToDevice, e->stream));
     QIE_HIP(hipMemcpyAsync(pk_epoch_ptr(b), &ep_after, 4, hipMemcpyHostToDevice, e->stream));
     QIE_HIP(hipStreamSynchronize(e->stream));
-    hipFree(d_eps);
-    hipFree(xsave);
     QIE_TRY(pk_check(b));
     const double per_layer = (double)(QD + 2 * KD) * H * 2 + (double)(QD + 2 * KD) * 2 * (s.qkv_bias ? 1 : 0) +
                              (double)H * QD * 2 + 2.0 * I * H * 2 + (double)H * I * 2 + 2.0 * H * 2 +
                              (double)(pos + 1) * KD * 2 * 2;
     *bytes = per_layer * s.n_layers;
-    *avg_us = ms * 1000.0 / iters;
     return 0;
 }
 
@@ -2244,9 +2125,9 @@ int qie_batch_time_kernel(qie_batch* b, int32_t which, int32_t iters, double* av
     const int64_t H = s.hidden, hd = s.head_dim, QD = (int64_t)sh.nq * hd, KD = (int64_t)sh.nkv * hd;
     const int64_t I = sh.ffn, B = b->B, V = sh.vocab;
     // scratch output so timing never disturbs the sequence state
-    uint16_t* scratch = nullptr;
-    QIE_TRY(dmalloc((void**)&scratch,
-                    (size_t)B * std::max<int64_t>(std::max(I, V), QD + 2 * KD) * 2 + B * 8 + 64));
+    DevBlock scratch_mem;
+    QIE_TRY(scratch_mem.grow((size_t)B * std::max<int64_t>(std::max(I, V), QD + 2 * KD) * 2 + B * 8 + 64));
+    uint16_t* scratch = (uint16_t*)scratch_mem.p;
     const double wb = e->fp8 ? 1.0 : 2.0;   // weight bytes per element (fp8 row scales: negligible)
     double by = 0;
     switch (which) {
@@ -2257,7 +2138,7 @@ int qie_batch_time_kernel(qie_batch* b, int32_t which, int32_t iters, double* av
         case 4: by = (double)V * H * wb + B * H * 2 + B * (double)V * 2; break;
         default: {
             std::vector<int32_t> pos(B);
-            QIE_HIP(d2h(e, pos.data(), b->d_pos, B * 4));
+            QIE_HIP(d2h(e, pos.data(), b->dec.pos, B * 4));
             for (int m = 0; m < B; m++) by += (double)(pos[m] + 1) * KD * 2 * 2;
             by += (double)B * QD * 2 * 2;
         }
@@ -2265,10 +2146,10 @@ int qie_batch_time_kernel(qie_batch* b, int32_t which, int32_t iters, double* av
     // the step's own rows and launches (the builders, prenorm()'s decision, the step's extras),
     // with every output in scratch: gate/up and QKV through their rows, O and down as plain
     // stores (the residual stream stays untouched), the head with its arg-max keys behind its logits
-    LayerRows r = decode_rows(b);
+    LayerRows r = layer_rows(b->dec, b->B, 1);
     if (which == 0) r.h = scratch;
     if (which == 2) r.qkv = scratch;
-    HeadBufs hb = batch_head(b, 0);
+    HeadBufs hb = head_bufs(b->dec, 0, b->e->sh.vocab);
     hb.logits = scratch;
     hb.keys = (unsigned long long*)(((uintptr_t)(scratch + B * V) + 7) & ~(uintptr_t)7);
     const LayerPath p = decode_path(e);
@@ -2281,28 +2162,15 @@ int qie_batch_time_kernel(qie_batch* b, int32_t which, int32_t iters, double* av
                             : which == 1 ? down_args(e, L, p.flags, r)
                             : which == 2 ? qkv_args(e, L, p.flags, r)
                             : which == 3 ? o_args(e, L, p.flags, r)
-                                         : head_args(e, b->x_res, H, (int)B, true, hb);
+                                         : head_args(e, b->dec.x, H, (int)B, true, hb);
         if (which == 1 || which == 3) {
             a.y = scratch;
             a.epilogue = QIE_EPI_STORE;
         }
-        if (prenorm_applies(a)) take_normed(a, b->xn);   // rows normed by the step's own prenorm(): no norm launch here
+        if (prenorm_applies(a)) take_normed(a, b->dec.xn);   // rows normed by the step's own prenorm(): no norm launch here
         return linear(&a, which == 2 ? decode_qkv_extras(b) : LinearExtras{}, e->stream);
     };
-    hipEvent_t t0, t1;
-    QIE_HIP(hipEventCreate(&t0));
-    QIE_HIP(hipEventCreate(&t1));
-    for (int i = 0; i < std::min(nl, 4); i++) QIE_TRY(run(i));   // warm-up
-    QIE_HIP(hipEventRecord(t0, e->stream));
-    for (int i = 0; i < iters; i++) QIE_TRY(run(i));
-    QIE_HIP(hipEventRecord(t1, e->stream));
-    QIE_HIP(hipEventSynchronize(t1));
-    float ms = 0;
-    QIE_HIP(hipEventElapsedTime(&ms, t0, t1));
-    hipEventDestroy(t0);
-    hipEventDestroy(t1);
-    hipFree(scratch);
-    *avg_us = ms * 1000.0 / iters;
+    QIE_TRY(time_launches(e->stream, run, std::min(nl, 4), iters, avg_us));
     *bytes = by;
     return 0;
 }

@@ -300,6 +300,52 @@ def test_short_prefill_after_long_prefill(oracle, paged):
     assert np.array_equal(lg, f.logits()[1])
 
 
+def test_prefill_scratch_regrowth_is_invisible():
+    """The prefill rows are one block that grows (freed, then made anew): on one batch, prefills of
+    5, 40 and 5 tokens into the same slot (made, regrown, reused) give the id and the logits of
+    three fresh batches doing one prefill each, bit for bit."""
+    spec = CONFIGS["qwen2-bias-hd64"]
+    eng = Q.Engine(spec, max_ctx=128).init_synthetic(SYN)
+    b = eng.batch(1, 128)
+    for i, P in enumerate((5, 40, 5)):
+        prompt = [int(t) for t in rng(60 + i).integers(0, spec.vocab, P)]
+        got, lg = b.prefill(0, prompt), b.logits()
+        f = eng.batch(1, 128)
+        assert got == f.prefill(0, prompt), f"prefill {i} (P = {P})"
+        assert np.array_equal(lg, f.logits()), f"prefill {i} (P = {P})"
+        f.close()
+
+
+def test_captured_work_survives_prefill_regrowth():
+    """Captured work may point only into blocks that are never reallocated.  B = 2 with graphs:
+    prefill slot 0 (P = 5), 2 decode steps (captures the decode graph), a verify with 3 drafts
+    (captures that step); then a P = 40 prefill of slot 1 frees and reallocates the prefill rows;
+    2 more decode steps and the verify again replay the captured work.  Ids and logits of every
+    step equal the same sequence on an eager engine, bit for bit."""
+    spec = CONFIGS["qwen2-bias-hd64"]
+    p0 = [int(t) for t in rng(70).integers(0, spec.vocab, 5)]
+    p1 = [int(t) for t in rng(71).integers(0, spec.vocab, 40)]
+    draft = [int(t) for t in rng(72).integers(0, spec.vocab, 3)]
+
+    def run(use_graph):
+        eng = Q.Engine(spec, max_ctx=128, use_graph=use_graph).init_synthetic(SYN)
+        b = eng.batch(2, 128)
+        out = [("prefill0", [b.prefill(0, p0)], b.logits()[:1])]
+        for phase in (0, 1):
+            if phase == 1:
+                out.append(("prefill1", [b.prefill(1, p1)], b.logits()))
+            rows = slice(0, 1 + phase)   # slot 1 is idle (its logits unwritten) before its prefill
+            for i in range(2):
+                out.append((f"decode{phase}.{i}", b.decode_step()[rows], b.logits()[rows]))
+            out.append((f"verify{phase}", b.verify(0, draft), b.verify_logits()))
+            out.append((f"after_verify{phase}", [], b.logits()[rows]))
+        return out
+
+    for (what, ids_g, lg_g), (_, ids_e, lg_e) in zip(run(True), run(False)):
+        assert list(ids_g) == list(ids_e), what
+        assert np.array_equal(lg_g, lg_e), what
+
+
 @pytest.mark.parametrize("L", [5, 40])
 @pytest.mark.parametrize("paged", [False, True])
 def test_prefill_batch_matches_oracle(oracle, L, paged):

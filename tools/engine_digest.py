@@ -19,8 +19,13 @@ Cases (tests/test_gpu_engine.py's tiny CONFIGS, synthetic weights, fixed seeds):
     fused norm where it applies), verify with 7 drafts;
   * prefill_fp8: tests/test_gpu_fp8_mx.py's test_engine_prefill_fp8_batched_tiny configuration;
   * comm_always at world size 1 (the exchange form of the row-parallel projections, the
-    gathered head): prefill, 4 decode steps, verify with 7 drafts, greedy and sampled;
-  * qie_batch_debug_step: a hash of the residual snapshots."""
+    gathered head): prefill, 4 decode steps, verify with 7 drafts, greedy and sampled; scoring;
+  * qie_batch_debug_step: a hash of the residual snapshots;
+  * qie_score, fused and QIE_SCORE_UNFUSED, from position 0 and as an append (hashes of the
+    log-probabilities and the greedy ids); qie_batch_logprobs;
+  * release, then a new prefill of the slot; set_position;
+  * the prefill rows growing on one batch: P = 5, 40, 5, then an append;
+  * decode mode 1 (the persistent step), 4 steps."""
 import hashlib
 import json
 import os
@@ -43,6 +48,8 @@ CONFIGS = {
 }
 TILED = S.tiny("t-t16", n_layers=2, hidden=896, n_heads=14, n_kv_heads=2, head_dim=64, ffn=2048, vocab=1024, bias=True)
 MX = S.tiny("t-mx", n_layers=2, hidden=256, n_heads=4, n_kv_heads=2, head_dim=64, ffn=512, vocab=1024, bias=True)
+PERSIST = S.tiny("t-q3-128", n_layers=3, hidden=1024, n_heads=8, n_kv_heads=2, head_dim=128, ffn=2048, vocab=4096,
+                 bias=False, qk_norm=True)
 SYN = W.SynthParams(seed=11, w_scale=0.08, norm_scale=0.25, bias_scale=0.05)
 SAMPLED = Q.Sampling(top_k=40, temperature=0.8, top_p=0.9, seed=99)
 
@@ -103,6 +110,23 @@ def verify_cases(tag, eng, spec, counts, samplings, P=12):
             c.took(b.decode_step(smp), b)
             twin.close()
             c.done(b)
+
+
+def score_cases(tag, eng, spec, unfused_forms):
+    """qie_score from position 0 (P = 40: the prefill rows grow past the scoring rows' first
+    size) and as an append: the log-probabilities and the greedy ids of every row."""
+    for unfused in unfused_forms:
+        c = Case(f"{tag}_score_{'unfused' if unfused else 'fused'}")
+        b = eng.batch(1, eng.max_ctx)
+        text = ids(spec, 60, 40 + 21)
+        lp, gr, nxt = b.score(0, text[:40], unfused=unfused)
+        c.took(nxt, b)
+        lp2, gr2, nxt = b.score(0, text[40:], pos0=40, unfused=unfused)
+        c.took(nxt, b)
+        c.rec["logprobs"] = [sha(lp), sha(lp2)]
+        c.rec["greedy"] = [sha(gr), sha(gr2)]
+        c.decode(b, 2)
+        c.done(b)
 
 
 def main():
@@ -184,8 +208,47 @@ def main():
                 c.decode(b, 4, smp)
                 c.done(b)
             verify_cases(f"comm_{g}", eng, spec, (7,), ((sn, smp),))
+        if graph:
+            score_cases("comm", eng, spec, (True,))   # the exchange form always scores unfused
         eng.close()
     comm.close()
+    # scoring, qie_batch_logprobs, slot reuse, scratch growth (bf16, graph)
+    eng = Q.Engine(spec, max_ctx=128).init_synthetic(SYN)
+    score_cases("bf16", eng, spec, (False, True))
+    c = Case("bf16_logprobs_B2")
+    b = eng.batch(2, 128)
+    for i in range(2):
+        c.took(b.prefill(i, ids(spec, 1 + i, 9)), b, slice(0, i + 1))
+    c.rec["logprobs"] = [sha(b.logprobs(ids(spec, 80, 2))), sha(b.logprobs([-1, 3]))]
+    c.done(b)
+    c = Case("bf16_release_reprefill_set_position")
+    b = eng.batch(2, 128)
+    for i in range(2):
+        c.took(b.prefill(i, ids(spec, 1 + i, 9)), b, slice(0, i + 1))
+    c.decode(b, 2)
+    b.release(0)
+    c.took(b.prefill(0, ids(spec, 81, 40)), b)
+    c.decode(b, 2)
+    b.set_position(1, 4, 17)   # rewind slot 1 to position 4 with token 17 pending
+    c.decode(b, 2)
+    c.done(b)
+    c = Case("bf16_scratch_growth")   # the prefill rows made, regrown, reused, then an append
+    b = eng.batch(1, 128)
+    for i, P in enumerate((5, 40, 5)):
+        c.took(b.prefill(0, ids(spec, 82 + i, P)), b)
+    c.took(b.append(0, ids(spec, 85, 50), 5), b)
+    c.decode(b, 2)
+    c.done(b)
+    eng.close()
+    # decode mode 1: the persistent step (tests/test_gpu_persist.py's qk-norm model)
+    eng = Q.Engine(PERSIST, max_ctx=64).init_synthetic(SYN)
+    c = Case("bf16_persistent_step")
+    b = eng.batch(1, 64)
+    b.set_decode_mode(1)
+    c.took(b.prefill(0, ids(PERSIST, 90, 20)), b)
+    c.decode(b, 4)
+    c.done(b)
+    eng.close()
 
 
 if __name__ == "__main__":
