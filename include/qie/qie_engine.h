@@ -157,7 +157,8 @@ void qie_batch_destroy(qie_batch* b);
  * Page 0 is a scratch page that idle slots write into. */
 int qie_batch_create_paged(qie_engine* e, int32_t batch, int32_t max_ctx, int32_t page_tokens,
                            int32_t n_pages, qie_batch** out);
-/* Ends sequence `seq`: its pages go back to the pool (paged) and the slot idles —
+/* Ends sequence `seq`: its pages go back to the pool (paged; a page another holder shares, see
+ * "forks and prefix handles" below, stays with that holder) and the slot idles —
  * it still runs through every decode step on the scratch page, its outputs are
  * meaningless — until the next qie_prefill into it.  Any batch. */
 int qie_batch_release(qie_batch* b, int32_t seq);
@@ -254,8 +255,55 @@ int qie_batch_logits(qie_batch* b, void* host_out);
 int qie_batch_positions(qie_batch* b, int32_t* host_pos);
 int qie_batch_history(qie_batch* b, int32_t seq, int32_t* host_ids, int32_t n);
 /* Rewind/set sequence `seq` to position pos with current token `token`
- * (KV rows >= pos are simply overwritten later). */
+ * (KV rows >= pos are simply overwritten later).  When pos lies in a page another holder shares
+ * ("forks and prefix handles" below) the slot first gets a private page holding that page's rows
+ * below pos only (-28 if the pool has none, nothing changed): the slot's rows at or past pos of
+ * that page are then gone, so a later set_position forward over them without a write in between
+ * finds undefined rows where a rewind within the slot's own pages finds the old ones. */
 int qie_batch_set_position(qie_batch* b, int32_t seq, int32_t pos, int32_t token);
+
+/* ------------------------------------------------- forks and prefix handles
+ * Sequences that begin alike share KV pages instead of prefilling the same ids twice (DESIGN.md
+ * §18).  Paged batches count the holders of every page: a page returns to the pool when the last
+ * holder (a slot or a prefix handle) lets go of it; qie_batch_release and qie_prefill drop
+ * references.  Every writer of the engine tier — the decode steps, qie_verify, qie_prefill_append /
+ * qie_score at pos0 >= 1, qie_batch_set_position — first replaces the pages of its write range that
+ * another holder shares by private ones (copying the rows below its first position), counted in
+ * its all-or-nothing pool check (-28); the other holder's pages are never touched.  The operator
+ * tier's raw descriptors (qie_batch_kv_cache, qie_kv_write, qie_batch_reserve) do none of this:
+ * writing through one into a page qie_batch_page_refs shows shared is the caller's doing.
+ *
+ * qie_batch_fork: src is a live slot at position p, dst != src any slot (a live dst is released
+ * first; the pages only it holds count towards the check), 1 <= n_tokens <= p.  Afterwards dst is a
+ * live sequence at position n_tokens whose K/V rows [0, n_tokens) equal src's bit for bit, with
+ * src's history [0 .. n_tokens], current token = src's history[n_tokens] (for n_tokens == p the
+ * pending current token, and then row dst of qie_batch_logits equals row src and a decode step
+ * produces in dst exactly what it produces in src) and step counter = src's + step_offset (the
+ * sampler draws from seed + step: forks that should sample differently get different offsets).
+ * Paged: the n_tokens / page_tokens full pages are shared, the remaining rows copied into one fresh
+ * page (qie_kv_copy); contiguous: all rows copied.  -22 for bad arguments or an idle src, -28 when
+ * the pool cannot supply the tail page; nothing has changed in either case.  Synchronises;
+ * collective under tensor parallelism (every rank decides alike). */
+typedef struct qie_kv_prefix qie_kv_prefix;
+int qie_batch_fork(qie_batch* b, int32_t src, int32_t dst, int32_t n_tokens, int32_t step_offset);
+/* Paged batches: the holder count of pool pages 0 .. n-1 (host; 0 = free; page 0, the scratch
+ * page, is always 0). */
+int qie_batch_page_refs(qie_batch* b, int32_t* host_refs, int32_t n);
+/* Prefix handles (paged batches; -22 on a contiguous one) keep a prefix alive after its slot is
+ * gone.  save: a reference on the pages of [0, n_tokens) of live slot seq (n_tokens a positive
+ * multiple of page_tokens, <= its position) and a host copy of those ids; takes no page, launches
+ * nothing.  load: releases dst, shares the handle's first n_tokens / page_tokens pages with it
+ * (n_tokens a positive multiple of page_tokens, <= the handle's length) and leaves it live at
+ * position n_tokens with current token `token` and the history filled, as qie_batch_set_position
+ * would; it takes no page (the page of position n_tokens is drawn by the append or decode step
+ * that writes it), so it cannot return -28.  The caller appends the rest at pos0 = n_tokens.
+ * tokens: the handle's first n ids (n <= its length) into host_ids, returning 0; host_ids NULL
+ * returns the length.  drop releases the references; qie_batch_destroy drops open handles. */
+int qie_batch_prefix_save(qie_batch* b, int32_t seq, int32_t n_tokens, qie_kv_prefix** out);
+int qie_batch_prefix_load(qie_batch* b, const qie_kv_prefix* p, int32_t dst, int32_t n_tokens, int32_t token);
+int qie_batch_prefix_tokens(const qie_kv_prefix* p, int32_t* host_ids, int32_t n);
+int qie_batch_prefix_drop(qie_batch* b, qie_kv_prefix* p);
+
 /* Decode structure of the batch's steps: 0 = five launches per layer (the reference path:
  * QKV GEMV, attention, O GEMV, gate/up GEMV, down GEMV, hipGraph-captured); 1 = the whole
  * layer stack as ONE persistent launch (one workgroup per CU, weight streams running ahead of

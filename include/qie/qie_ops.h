@@ -219,6 +219,15 @@ int qie_rope(void* x, int64_t rows, int64_t row_stride, int32_t n_heads, int32_t
              int32_t numerics, void* stream);
 int qie_kv_write(const void* k, const void* v, int64_t rows, int64_t ld, int32_t pos0,
                  const qie_kv_cache* cache, int32_t seq, int32_t layer, void* stream);
+/* The K and V rows of positions [pos0, pos0 + n_rows), every layer and kv head, from sequence
+ * src_seq of `src` to the same positions of sequence dst_seq of `dst`, in one launch (k_kvcopy.hip;
+ * the reference's sequences never share or copy rows).  Both caches contiguous or both paged (a
+ * mixed pair: -22), equal in n_layers, n_kv_heads, head_dim and page_tokens; a paged copy walks
+ * both block tables and writes only into the pages dst's table names for those positions, which
+ * the caller holds.  n_rows == 0 returns 0 without a launch; the same sequence of the same cache
+ * and positions past either max_ctx return -22.  Never allocates or synchronises; capturable. */
+int qie_kv_copy(const qie_kv_cache* src, int32_t src_seq, const qie_kv_cache* dst, int32_t dst_seq,
+                int32_t pos0, int32_t n_rows, void* stream);
 
 /* ------------------------------------------------------------- elementwise
  * launch_act + launch_elem (helpers.cuh:108-115) and launch_resadd (:116-119)

@@ -125,6 +125,7 @@ SIGNATURES = [
     ("qie_qknorm", C.c_int, [_P, _I64, _I64, _I32, _I32, _P, _F, _I32, _P]),
     ("qie_rope", C.c_int, [_P, _I64, _I64, _I32, _I32, _P, _I32, _P, _P, _I32, _P]),
     ("qie_kv_write", C.c_int, [_P, _P, _I64, _I64, _I32, C.POINTER(KvCacheC), _I32, _I32, _P]),
+    ("qie_kv_copy", C.c_int, [C.POINTER(KvCacheC), _I32, C.POINTER(KvCacheC), _I32, _I32, _I32, _P]),
     ("qie_silu", C.c_int, [_P, _I64, _P]),
     ("qie_mul", C.c_int, [_P, _P, _P, _I64, _P]),
     ("qie_memcpy_d2d", C.c_int, [_P, _P, _I64, _P]),
@@ -200,6 +201,12 @@ SIGNATURES = [
     ("qie_batch_positions", C.c_int, [_P, _PI32]),
     ("qie_batch_history", C.c_int, [_P, _I32, _PI32, _I32]),
     ("qie_batch_set_position", C.c_int, [_P, _I32, _I32, _I32]),
+    ("qie_batch_fork", C.c_int, [_P, _I32, _I32, _I32, _I32]),
+    ("qie_batch_page_refs", C.c_int, [_P, _PI32, _I32]),
+    ("qie_batch_prefix_save", C.c_int, [_P, _I32, _I32, C.POINTER(_P)]),
+    ("qie_batch_prefix_load", C.c_int, [_P, _P, _I32, _I32, _I32]),
+    ("qie_batch_prefix_tokens", C.c_int, [_P, _PI32, _I32]),
+    ("qie_batch_prefix_drop", C.c_int, [_P, _P]),
     ("qie_batch_dims", C.c_int, [_P, _PI32, _PI32]),
     ("qie_batch_set_decode_mode", C.c_int, [_P, _I32]),
     ("qie_batch_decode_mode", C.c_int, [_P]),

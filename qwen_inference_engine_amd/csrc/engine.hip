@@ -21,6 +21,7 @@
 #include "qie_comm.hpp"
 #include "verify.hpp"
 #include "row_bufs.hpp"
+#include "page_pool.hpp"
 
 #include <chrono>
 #include <cstring>
@@ -137,6 +138,13 @@ struct DevBlock {
     }
 };
 
+// A prefix kept alive after its slot is gone (qie_batch_prefix_save): one reference
+// on each of its pages and a host copy of its ids.  Host state only.
+struct qie_kv_prefix {
+    qie_batch* owner = nullptr;
+    std::vector<int32_t> pages, ids;
+};
+
 // Device rows (row_bufs.hpp; DESIGN.md §2 "Row buffers").  Pointer stability: `dec` and `v` are
 // made once and never reallocated, `pf`, `pf_ws`, `sc` and `sc_ws` grow (freed, then made anew);
 // captured work (the decode graph, captured verify steps, the persistent step's attention table)
@@ -154,11 +162,15 @@ struct qie_batch {
     PrefillRows pf;              // prompt rows, grown to the largest prefill so far
     DevBlock pf_ws;              // its attention workspace: depends on n and on the form (short prompts split;
                                  //   an append's partials grow with its rows), not monotone in n
-    // paged KV (qie_batch_create_paged): pool pages of page_tokens tokens, block table
-    // [B][max_pages] on device and host, free list, pages held per slot
+    // paged KV (qie_batch_create_paged): pool pages of page_tokens tokens; the host block table,
+    // the free list, the pages held per slot and the count per page live in `pool`
+    // (page_pool.hpp), the device table [B + 1][max_pages] mirrors its table.  Row B belongs to
+    // no slot: a writer stages the shared page it is replacing there, so that qie_kv_copy can
+    // read the old page and write the new one through the one table (make_writable).
     int page_tokens = 0, max_pages = 0, n_pages = 0;
     int32_t* d_table = nullptr;
-    std::vector<int32_t> h_table, free_pages, held;
+    PagePool pool;
+    std::vector<qie_kv_prefix*> prefixes;   // open prefix handles (dropped by qie_batch_destroy)
     std::vector<char> idle;
     bool table_dirty = false;
     // decode graph
@@ -282,36 +294,24 @@ static qie_kv_cache batch_cache(const qie_batch* b, int seq0) {
 // Host-side allocator of the paged batch.  Decisions are deterministic, so the
 // tensor-parallel ranks (each holding its own heads' pages) stay in step.
 
-// Pages slot seq still lacks to hold ntok tokens (negative: it holds more than they need; 0 on
-// a contiguous batch).  The all-or-nothing checks sum this before anything is drawn.
-static int64_t pages_missing(const qie_batch* b, int seq, int64_t ntok) {
-    if (!b->d_table) return 0;
-    return (ntok + b->page_tokens - 1) / b->page_tokens - b->held[seq];
-}
-
 static int ensure_pages(qie_batch* b, int seq, int64_t ntok) {
     if (!b->d_table) return 0;
-    const int64_t need = (ntok + b->page_tokens - 1) / b->page_tokens;
+    const int64_t need = b->pool.pages_for(ntok);
     QIE_REQUIRE(need <= b->max_pages, "KV pages: %lld tokens exceed max_ctx %d", (long long)ntok, b->max_ctx);
-    int64_t extra = need - b->held[seq];
-    QIE_REQUIRE(extra <= (int64_t)b->free_pages.size(), "KV pages: sequence %d needs %lld more pages, %zu free",
-                seq, (long long)extra, b->free_pages.size());
-    for (; b->held[seq] < need; b->held[seq]++) {
-        b->h_table[(int64_t)seq * b->max_pages + b->held[seq]] = b->free_pages.back();
-        b->free_pages.pop_back();
+    int64_t extra = need - b->pool.held[seq];
+    QIE_REQUIRE(extra <= b->pool.free_count(), "KV pages: sequence %d needs %lld more pages, %lld free", seq,
+                (long long)extra, (long long)b->pool.free_count());
+    if (extra > 0) {
+        b->pool.grow(seq, ntok);
         b->table_dirty = true;
     }
     return 0;
 }
 
+// the slot lets go of its pages: those no other holder references return to the free list
 static void drop_pages(qie_batch* b, int seq) {
     if (!b->d_table) return;
-    for (int i = b->held[seq] - 1; i >= 0; i--) {
-        int32_t& t = b->h_table[(int64_t)seq * b->max_pages + i];
-        b->free_pages.push_back(t);
-        t = 0;   // scratch page
-    }
-    b->held[seq] = 0;
+    b->pool.release(seq);
     b->table_dirty = true;
 }
 
@@ -320,10 +320,36 @@ static int flush_table(qie_batch* b) {
     if (!b->d_table || !b->table_dirty) return 0;
     // on the engine stream (non-blocking: a legacy-null-stream copy is not ordered before its
     // kernels), complete before the host table may change again
-    QIE_HIP(hipMemcpyAsync(b->d_table, b->h_table.data(), b->h_table.size() * 4, hipMemcpyHostToDevice, b->e->stream));
+    QIE_HIP(hipMemcpyAsync(b->d_table, b->pool.table.data(), b->pool.table.size() * 4, hipMemcpyHostToDevice, b->e->stream));
     QIE_HIP(hipStreamSynchronize(b->e->stream));
     b->table_dirty = false;
     return 0;
+}
+
+// The writers' planning step (prepare_steps, qie_verify, an append, qie_batch_set_position): what
+// writing positions [lo, hi] of slot seq takes from the pool — growth plus a private replacement
+// for every page of the range another holder shares.  Changes nothing; the caller
+// adds fresh() to its pool check.
+static PagePool::WritePlan plan_write(const qie_batch* b, int seq, int64_t lo, int64_t hi) {
+    return b->d_table ? b->pool.plan_write(seq, lo, hi) : PagePool::WritePlan{};
+}
+
+// Applies a checked plan: the slot's shared pages of [lo, hi] become private ones, it grows to hold
+// hi + 1 tokens, and the rows below lo of the page holding lo are copied from the page it shared
+// (staged in table row B) into its replacement.  The other holders' pages are not touched.
+static int make_writable(qie_batch* b, int seq, const PagePool::WritePlan& w, int64_t lo, int64_t hi) {
+    if (!b->d_table || w.fresh() == 0) return 0;
+    int32_t was = 0, now = 0;
+    b->pool.make_private(seq, w, lo, hi, &was, &now);
+    b->table_dirty = true;
+    if (!now) return 0;   // no page with rows to keep (or another slot of this call made it private first)
+    b->pool.row(b->B)[w.copy_index] = was;
+    QIE_TRY(flush_table(b));
+    const qie_kv_cache c = batch_cache(b, 0);
+    const int rc = qie_kv_copy(&c, b->B, &c, seq, w.copy_index * b->page_tokens, w.copy_rows, b->e->stream);
+    b->pool.row(b->B)[w.copy_index] = 0;
+    b->table_dirty = true;
+    return rc;
 }
 
 
@@ -1314,9 +1340,7 @@ static int batch_create(qie_engine* e, int32_t batch, int32_t max_ctx, int32_t p
         b->n_pages = n_pages > 0 ? n_pages : batch * b->max_pages + 1;
         b->seq_stride = (int64_t)s.n_layers * sh.nkv * page_tokens * hd;   // elements per page
         n_runs = b->n_pages;
-        b->h_table.assign((size_t)batch * b->max_pages, 0);
-        for (int p = b->n_pages - 1; p >= 1; p--) b->free_pages.push_back(p);   // page 1 handed out first
-        b->held.assign(batch, 0);
+        b->pool.init(batch + 1, b->max_pages, page_tokens, b->n_pages);   // page 1 handed out first; row B: staging
         b->table_dirty = true;
     } else {
         b->run_pad = dev_env("QIE_KV_RUN_PAD", 0);   // dev A/B: tokens of padding per (layer, head) run
@@ -1334,7 +1358,7 @@ static int batch_create(qie_engine* e, int32_t batch, int32_t max_ctx, int32_t p
         const size_t pool = (size_t)n_runs * b->seq_stride * 2;
         QIE_TRY(dmalloc((void**)&b->kc, pool));
         QIE_TRY(dmalloc((void**)&b->vc, pool));
-        if (page_tokens > 0) QIE_TRY(dmalloc((void**)&b->d_table, b->h_table.size() * 4));
+        if (page_tokens > 0) QIE_TRY(dmalloc((void**)&b->d_table, b->pool.table.size() * 4));
         RowDims d = row_dims(e, batch);
         d.samp_ws_bytes = qie_sample_workspace_bytes(batch, s.vocab);
         const int64_t rc_floats = rope_cur_stride((int)hd);
@@ -1389,9 +1413,9 @@ int qie_batch_release(qie_batch* b, int32_t seq) {
 
 int qie_batch_page_stats(qie_batch* b, int32_t* free_pages, int32_t* pages_per_seq, int32_t* page_tokens) {
     QIE_REQUIRE(b, "qie_batch_page_stats: null batch");
-    if (free_pages) *free_pages = (int32_t)b->free_pages.size();
+    if (free_pages) *free_pages = (int32_t)b->pool.free_count();
     if (pages_per_seq)
-        for (int m = 0; m < b->B; m++) pages_per_seq[m] = b->d_table ? b->held[m] : 0;
+        for (int m = 0; m < b->B; m++) pages_per_seq[m] = b->d_table ? b->pool.held[m] : 0;
     if (page_tokens) *page_tokens = b->page_tokens;
     return 0;
 }
@@ -1417,6 +1441,7 @@ void qie_batch_destroy(qie_batch* b) {
                     (void*)b->pk_ts})
         if (p) hipFree(p);
     // (the DevBlock workspaces free themselves)
+    for (qie_kv_prefix* p : b->prefixes) delete p;   // handles still open: their pages go with the pool
     delete b;
 }
 
@@ -1520,11 +1545,13 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
             QIE_REQUIRE(score->targets[i] >= -1 && score->targets[i] < s.vocab,
                         "%s: target %d of row %lld is neither -1 nor a token id", who, score->targets[i], (long long)i);
     hipStream_t st = e->stream;
+    PagePool::WritePlan wplan;
     if (append) {   // all-or-nothing, before anything is allocated or launched
-        const int64_t need = pages_missing(b, seq0, (int64_t)pos0 + len);
-        if (need > (int64_t)b->free_pages.size())
-            return fail(-28, "%s: KV pool exhausted (%lld more pages needed for %d rows at position %d, %zu free)",
-                        who, (long long)need, len, pos0, b->free_pages.size());
+        wplan = plan_write(b, seq0, pos0, (int64_t)pos0 + len - 1);
+        const int64_t need = wplan.fresh();   // growth + a private copy of every shared page of the range
+        if (need > b->pool.free_count())
+            return fail(-28, "%s: KV pool exhausted (%lld more pages needed for %d rows at position %d, %lld free)",
+                        who, (long long)need, len, pos0, (long long)b->pool.free_count());
     }
     QIE_TRY(ensure_prefill_scratch(b, n, append));
     if (score) {   // the scoring head's scratch too, before anything is launched
@@ -1532,20 +1559,23 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
         if (!score_fused(e, score->flags)) QIE_TRY(ensure_verify_bufs(b));
     }
     if (b->d_table && !append) {   // all-or-nothing: the slots' own pages count, nothing is dropped on failure
-        int64_t missing = 0, held = 0;
+        // (held: the pages only that slot holds — a page shared with another holder does not
+        // return to the pool when the slot lets go of it)
+        int64_t needed = 0, held = 0;
         for (int z = 0; z < n_seqs; z++) {
-            missing += pages_missing(b, seq0 + z, len);
-            held += b->held[seq0 + z];
+            needed += b->pool.pages_for(len);
+            held += b->pool.exclusive(seq0 + z);
         }
-        QIE_REQUIRE(missing <= (int64_t)b->free_pages.size(),
-                    "%s: KV pool exhausted (%lld pages needed, %zu free + %lld held by slots %d..%d)", who,
-                    (long long)(missing + held), b->free_pages.size(), (long long)held, seq0, seq0 + n_seqs - 1);
+        QIE_REQUIRE(needed - held <= b->pool.free_count(),
+                    "%s: KV pool exhausted (%lld pages needed, %lld free + %lld held by slots %d..%d)", who,
+                    (long long)needed, (long long)b->pool.free_count(), (long long)held, seq0, seq0 + n_seqs - 1);
     }
     // a prefill starts a new sequence in each slot: every target slot's pages go back to
     // the pool BEFORE any slot draws, so the check above (free + held) is exactly what the
     // draws below can use and none of them can fail part way
     if (!append)
         for (int z = 0; z < n_seqs; z++) drop_pages(b, seq0 + z);
+    if (append) QIE_TRY(make_writable(b, seq0, wplan, pos0, (int64_t)pos0 + len - 1));
     for (int z = 0; z < n_seqs; z++) {
         QIE_TRY(ensure_pages(b, seq0 + z, (int64_t)pos0 + len));
         b->idle[seq0 + z] = 0;
@@ -1715,14 +1745,22 @@ static int prepare_steps(qie_batch* b, int n_steps, const char* who) {
             QIE_REQUIRE(b->h_pos[m] + n_steps < b->max_ctx, "%s: sequence %d would exceed max_ctx %d", who, m,
                         b->max_ctx);
     if (b->d_table) {
+        // growth, plus a private copy of any shared page in the steps' range (only a slot rewound
+        // below a fork point has one: a fork copies its tail page eagerly)
         int64_t need = 0;
+        PagePool::WritePlan plans[8];   // B <= 8 (batch_create)
         for (int m = 0; m < b->B; m++)
-            if (!b->idle[m])
-                need += std::max<int64_t>(0, pages_missing(b, m, b->h_pos[m] + n_steps));
-        QIE_REQUIRE(need <= (int64_t)b->free_pages.size(), "%s: KV pool exhausted (%lld pages needed, %zu free)", who,
-                    (long long)need, b->free_pages.size());
+            if (!b->idle[m]) {
+                plans[m] = plan_write(b, m, b->h_pos[m], (int64_t)b->h_pos[m] + n_steps - 1);
+                need += plans[m].fresh();
+            }
+        QIE_REQUIRE(need <= b->pool.free_count(), "%s: KV pool exhausted (%lld pages needed, %lld free)", who,
+                    (long long)need, (long long)b->pool.free_count());
         for (int m = 0; m < b->B; m++)
-            if (!b->idle[m]) QIE_TRY(ensure_pages(b, m, b->h_pos[m] + n_steps));
+            if (!b->idle[m]) {
+                QIE_TRY(make_writable(b, m, plans[m], b->h_pos[m], (int64_t)b->h_pos[m] + n_steps - 1));
+                QIE_TRY(ensure_pages(b, m, b->h_pos[m] + n_steps));
+            }
         QIE_TRY(flush_table(b));
     }
     qie_engine* e = b->e;
@@ -1795,21 +1833,145 @@ int qie_batch_history(qie_batch* b, int32_t seq, int32_t* host_ids, int32_t n) {
     return 0;
 }
 
-int qie_batch_set_position(qie_batch* b, int32_t seq, int32_t pos, int32_t token) {
-    QIE_REQUIRE(b && seq >= 0 && seq < b->B && pos >= 0 && pos + 1 < b->max_ctx && token >= 0 &&
-                    token < b->e->spec.vocab,
-                "qie_batch_set_position: bad arguments");
-    QIE_TRY(ensure_pages(b, seq, (int64_t)pos + 1));
-    QIE_TRY(flush_table(b));
-    b->idle[seq] = 0;
+// Slot dst becomes a live sequence at position n with current token tok and step counter step_v:
+// its next input row, RoPE row and history[n] as set_state_kernel sets them; synchronises.  The
+// one tail of qie_batch_set_position, qie_batch_fork and qie_batch_prefix_load.
+static int start_slot(qie_batch* b, int dst, int n, int step_v, int tok) {
     qie_engine* e = b->e;
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(256), 0, e->stream, seq, pos, pos, token, b->dec.pos, b->dec.step,
+    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(256), 0, e->stream, dst, n, step_v, tok, b->dec.pos, b->dec.step,
                        b->dec.hist, b->max_ctx, (const uint4*)e->w.embed, (uint4*)b->dec.x,
                        (int64_t)e->spec.hidden / 8, 1, rope_cur_args(b));
     QIE_LAUNCH_CHECK();
     QIE_HIP(hipStreamSynchronize(e->stream));
-    b->h_pos[seq] = pos;
+    b->idle[dst] = 0;
+    b->h_pos[dst] = n;
     return 0;
+}
+
+int qie_batch_set_position(qie_batch* b, int32_t seq, int32_t pos, int32_t token) {
+    QIE_REQUIRE(b && seq >= 0 && seq < b->B && pos >= 0 && pos + 1 < b->max_ctx && token >= 0 &&
+                    token < b->e->spec.vocab,
+                "qie_batch_set_position: bad arguments");
+    // a rewind into a page another holder shares: this slot gets a private copy of it first
+    const PagePool::WritePlan wplan = plan_write(b, seq, pos, pos);
+    if (wplan.n_private && wplan.fresh() > b->pool.free_count())
+        return fail(-28, "qie_batch_set_position: KV pool exhausted (position %d lies in a shared page: %lld pages "
+                         "needed, %lld free)", pos, (long long)wplan.fresh(), (long long)b->pool.free_count());
+    if (wplan.n_private) QIE_TRY(make_writable(b, seq, wplan, pos, pos));
+    QIE_TRY(ensure_pages(b, seq, (int64_t)pos + 1));
+    QIE_TRY(flush_table(b));
+    return start_slot(b, seq, pos, pos, token);
+}
+
+// ------------------------------------------------------------ forks and prefix handles
+
+int qie_batch_fork(qie_batch* b, int32_t src, int32_t dst, int32_t n_tokens, int32_t step_offset) {
+    QIE_REQUIRE(b && src >= 0 && src < b->B && dst >= 0 && dst < b->B && src != dst,
+                "qie_batch_fork: bad arguments (two different slots of the batch)");
+    QIE_REQUIRE(!b->idle[src], "qie_batch_fork: slot %d holds no live sequence", src);
+    const int p = b->h_pos[src], n = n_tokens;
+    QIE_REQUIRE(n >= 1 && n <= p, "qie_batch_fork: n_tokens %d outside [1, %d] (the source's position)", n, p);
+    if (b->d_table && !b->pool.fork_fits(dst, n))
+        return fail(-28, "qie_batch_fork: KV pool exhausted (no page for the %d rows past the last full page; "
+                         "%lld free)", n % b->page_tokens, (long long)b->pool.free_count());
+    // nothing can fail for lack of pages from here on
+    qie_engine* e = b->e;
+    hipStream_t st = e->stream;
+    int32_t tok_step[2] = {0, 0};   // the source's history[n] and its step counter
+    QIE_HIP(hipMemcpyAsync(&tok_step[0], b->dec.hist + (int64_t)src * b->max_ctx + n, 4, hipMemcpyDeviceToHost, st));
+    QIE_HIP(hipMemcpyAsync(&tok_step[1], b->dec.step + src, 4, hipMemcpyDeviceToHost, st));
+    QIE_HIP(hipStreamSynchronize(st));
+    const int tok = tok_step[0];
+    // every writer of the history stores ids in [0, vocab): anything else means the history is
+    // corrupt, and a fork would only copy the damage — fail while nothing has changed
+    if (tok < 0 || tok >= e->spec.vocab)
+        return fail(-5, "qie_batch_fork: history[%d] of slot %d holds %d, not a token id", n, src, tok);
+    const qie_kv_cache c = batch_cache(b, 0);
+    if (b->d_table) {   // full pages shared, the partial last page copied into a page of dst's own
+        b->pool.fork(src, dst, n);
+        b->table_dirty = true;
+        QIE_TRY(flush_table(b));
+        const int tail = n % b->page_tokens;
+        QIE_TRY(qie_kv_copy(&c, src, &c, dst, n - tail, tail, st));
+    } else {
+        QIE_TRY(qie_kv_copy(&c, src, &c, dst, 0, n, st));
+    }
+    QIE_HIP(hipMemcpyAsync(b->dec.hist + (int64_t)dst * b->max_ctx, b->dec.hist + (int64_t)src * b->max_ctx,
+                           (size_t)(n + 1) * 4, hipMemcpyDeviceToDevice, st));
+    if (n == p)   // the pending token's logits: row dst of qie_batch_logits equals row src
+        QIE_HIP(hipMemcpyAsync(b->dec.logits + (int64_t)dst * e->sh.vocab, b->dec.logits + (int64_t)src * e->sh.vocab,
+                               (size_t)e->sh.vocab * 2, hipMemcpyDeviceToDevice, st));
+    return start_slot(b, dst, n, tok_step[1] + step_offset, tok);
+}
+
+int qie_batch_page_refs(qie_batch* b, int32_t* host_refs, int32_t n) {
+    QIE_REQUIRE(b && b->d_table && host_refs && n >= 0 && n <= b->n_pages,
+                "qie_batch_page_refs: bad arguments (paged batch, n <= its pages)");
+    for (int i = 0; i < n; i++) host_refs[i] = b->pool.refs[i];
+    return 0;
+}
+
+int qie_batch_prefix_save(qie_batch* b, int32_t seq, int32_t n_tokens, qie_kv_prefix** out) {
+    QIE_REQUIRE(b && out && seq >= 0 && seq < b->B, "qie_batch_prefix_save: bad arguments");
+    QIE_REQUIRE(b->d_table, "qie_batch_prefix_save: prefix handles need a paged batch");
+    QIE_REQUIRE(!b->idle[seq], "qie_batch_prefix_save: slot %d holds no live sequence", seq);
+    QIE_REQUIRE(n_tokens > 0 && n_tokens % b->page_tokens == 0 && n_tokens <= b->h_pos[seq],
+                "qie_batch_prefix_save: n_tokens %d must be a positive multiple of %d and at most the position %d",
+                n_tokens, b->page_tokens, b->h_pos[seq]);
+    qie_kv_prefix* p = new qie_kv_prefix();
+    p->owner = b;
+    p->ids.resize(n_tokens);
+    const hipError_t he = d2h(b->e, p->ids.data(), b->dec.hist + (int64_t)seq * b->max_ctx, (size_t)n_tokens * 4);
+    if (he != hipSuccess) {
+        delete p;
+        return fail((int)he, "qie_batch_prefix_save: reading the history: %s", hipGetErrorString(he));
+    }
+    for (int i = 0; i < n_tokens / b->page_tokens; i++) {
+        p->pages.push_back(b->pool.row(seq)[i]);
+        b->pool.share(p->pages.back());
+    }
+    b->prefixes.push_back(p);
+    *out = p;
+    return 0;
+}
+
+int qie_batch_prefix_load(qie_batch* b, const qie_kv_prefix* p, int32_t dst, int32_t n_tokens, int32_t token) {
+    QIE_REQUIRE(b && p && dst >= 0 && dst < b->B && token >= 0 && token < b->e->spec.vocab,
+                "qie_batch_prefix_load: bad arguments");
+    QIE_REQUIRE(b->d_table && p->owner == b, "qie_batch_prefix_load: the handle belongs to another batch");
+    QIE_REQUIRE(n_tokens > 0 && n_tokens % b->page_tokens == 0 && n_tokens <= (int)p->ids.size() &&
+                    n_tokens + 1 < b->max_ctx,
+                "qie_batch_prefix_load: n_tokens %d must be a positive multiple of %d, at most the handle's %zu and "
+                "below max_ctx", n_tokens, b->page_tokens, p->ids.size());
+    // shares pages only: nothing is taken from the free list, so the call cannot run out
+    b->pool.release(dst);
+    for (int i = 0; i < n_tokens / b->page_tokens; i++) b->pool.push_shared(dst, p->pages[i]);
+    b->table_dirty = true;
+    QIE_TRY(flush_table(b));
+    QIE_HIP(hipMemcpyAsync(b->dec.hist + (int64_t)dst * b->max_ctx, p->ids.data(), (size_t)n_tokens * 4,
+                           hipMemcpyHostToDevice, b->e->stream));
+    return start_slot(b, dst, n_tokens, n_tokens, token);
+}
+
+int qie_batch_prefix_tokens(const qie_kv_prefix* p, int32_t* host_ids, int32_t n) {
+    QIE_REQUIRE(p, "qie_batch_prefix_tokens: null handle");
+    if (!host_ids) return (int)p->ids.size();
+    QIE_REQUIRE(n >= 0 && n <= (int)p->ids.size(), "qie_batch_prefix_tokens: n %d exceeds the handle's %zu ids", n,
+                p->ids.size());
+    std::memcpy(host_ids, p->ids.data(), (size_t)n * 4);
+    return 0;
+}
+
+int qie_batch_prefix_drop(qie_batch* b, qie_kv_prefix* p) {
+    QIE_REQUIRE(b && p && p->owner == b, "qie_batch_prefix_drop: bad arguments");
+    for (size_t i = 0; i < b->prefixes.size(); i++)
+        if (b->prefixes[i] == p) {
+            for (int32_t g : p->pages) b->pool.drop(g);
+            b->prefixes.erase(b->prefixes.begin() + i);
+            delete p;
+            return 0;
+        }
+    return fail(-22, "qie_batch_prefix_drop: not an open handle of this batch");
 }
 
 // ------------------------------------------------------------ speculative verify
@@ -1900,11 +2062,14 @@ int qie_verify(qie_batch* b, int32_t seq, const int32_t* draft, int32_t n_draft,
     const int p = b->h_pos[seq], M = n_draft + 1;
     QIE_REQUIRE((int64_t)p + n_draft + 1 < b->max_ctx, "qie_verify: %d rows from position %d do not fit max_ctx %d", M,
                 p, b->max_ctx);
-    const int64_t need = pages_missing(b, seq, (int64_t)p + M);   // all-or-nothing, before anything is allocated or launched
-    if (need > (int64_t)b->free_pages.size())
-        return fail(-28, "qie_verify: KV pool exhausted (%lld more pages needed for %d rows at position %d, %zu free)",
-                    (long long)need, M, p, b->free_pages.size());
+    // all-or-nothing, before anything is allocated or launched (growth + a private copy of a shared page)
+    const PagePool::WritePlan wplan = plan_write(b, seq, p, (int64_t)p + M - 1);
+    const int64_t need = wplan.fresh();
+    if (need > b->pool.free_count())
+        return fail(-28, "qie_verify: KV pool exhausted (%lld more pages needed for %d rows at position %d, %lld free)",
+                    (long long)need, M, p, (long long)b->pool.free_count());
     QIE_TRY(ensure_verify_bufs(b));
+    QIE_TRY(make_writable(b, seq, wplan, p, (int64_t)p + M - 1));
     QIE_TRY(ensure_pages(b, seq, (int64_t)p + M));
     QIE_TRY(flush_table(b));
     hipStream_t st = e->stream;

@@ -225,6 +225,28 @@ class Engine:
             pass
 
 
+class Prefix:
+    """A saved prefix of a paged batch (Batch.save_prefix): `.ids` its token ids, `.n_tokens`
+    their count; it holds a reference on the prefix's KV pages until drop()."""
+
+    def __init__(self, batch: "Batch", handle):
+        self.batch = batch
+        self.h = handle
+        n = int(batch.lib.qie_batch_prefix_tokens(handle, None, 0))
+        if n < 0:
+            _lib.check(n, "qie_batch_prefix_tokens")
+        arr = (C.c_int32 * max(n, 1))()
+        _lib.check(batch.lib.qie_batch_prefix_tokens(handle, arr, n), "qie_batch_prefix_tokens")
+        self.ids = [int(t) for t in arr[:n]]
+        self.n_tokens = n
+
+    def drop(self) -> None:
+        """Release the references; pages no slot holds return to the pool."""
+        if self.h is not None and getattr(self.batch, "h", None):
+            _lib.check(self.batch.lib.qie_batch_prefix_drop(self.batch.h, self.h), "qie_batch_prefix_drop")
+        self.h = None
+
+
 class Batch:
     def __init__(self, engine: Engine, batch: int, max_ctx: int, page_tokens: Optional[int] = None,
                  n_pages: int = 0):
@@ -233,6 +255,10 @@ class Batch:
         self.B = batch
         self.max_ctx = max_ctx
         self.paged = page_tokens is not None
+        # the pool's size as qie_batch_create_paged settles it (page_tokens 0 = 128; n_pages 0 =
+        # every slot at max_ctx + the scratch page); 0 for a contiguous batch
+        T = (page_tokens or 128) if self.paged else 0
+        self.n_pages = (n_pages or batch * ((max_ctx + T - 1) // T) + 1) if self.paged else 0
         h = C.c_void_p()
         if self.paged:
             _lib.check(self.lib.qie_batch_create_paged(engine.h, batch, max_ctx, page_tokens, n_pages, C.byref(h)),
@@ -400,6 +426,38 @@ class Batch:
     def release(self, seq: int) -> None:
         """End sequence `seq`: its KV pages return to the pool; the slot idles until the next prefill."""
         _lib.check(self.lib.qie_batch_release(self.h, seq), "qie_batch_release")
+
+    def fork(self, src: int, dst: int, n_tokens: Optional[int] = None, step_offset: int = 0) -> None:
+        """Make slot `dst` a sequence that begins as live slot `src` does (qie_batch_fork): its
+        first n_tokens rows (None: all of src's, up to its position) on shared KV pages, the
+        partial last page copied.  step_offset is added to the copy's sampling step counter, so
+        that forks of one sampled sequence draw different tokens."""
+        if n_tokens is None:
+            n_tokens = int(self.positions()[src])
+        _lib.check(self.lib.qie_batch_fork(self.h, src, dst, int(n_tokens), int(step_offset)), "qie_batch_fork")
+
+    def page_refs(self) -> np.ndarray:
+        """Holders per pool page (int32 [n_pages], 0 = free; page 0 is the scratch page); paged batches."""
+        n = self.n_pages
+        out = np.zeros(max(n, 1), dtype=np.int32)
+        _lib.check(self.lib.qie_batch_page_refs(self.h, out.ctypes.data_as(C.POINTER(C.c_int32)), n),
+                   "qie_batch_page_refs")
+        return out[:n]
+
+    def save_prefix(self, seq: int, n_tokens: int) -> "Prefix":
+        """Keep the first n_tokens (a multiple of page_tokens) of live slot `seq` alive beyond
+        the slot (qie_batch_prefix_save): a reference on their pages and a copy of their ids."""
+        h = C.c_void_p()
+        _lib.check(self.lib.qie_batch_prefix_save(self.h, seq, int(n_tokens), C.byref(h)), "qie_batch_prefix_save")
+        return Prefix(self, h)
+
+    def load_prefix(self, prefix: "Prefix", dst: int, token: int, n_tokens: Optional[int] = None) -> None:
+        """Start slot `dst` on the saved prefix's pages (its first n_tokens, None: all) at
+        position n_tokens with current token `token`; append() the rest at pos0 = n_tokens."""
+        if prefix.h is None:
+            raise _lib.QieError("load_prefix: the prefix was dropped")
+        n = prefix.n_tokens if n_tokens is None else int(n_tokens)
+        _lib.check(self.lib.qie_batch_prefix_load(self.h, prefix.h, dst, n, int(token)), "qie_batch_prefix_load")
 
     def page_stats(self):
         """(free pages, pages held per slot, page_tokens); zeros for a contiguous batch."""

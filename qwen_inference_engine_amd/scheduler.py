@@ -11,6 +11,11 @@ prefill in one ``qie_prefill_batch`` pass), and retired at its stop token / toke
 slots run on the scratch page and their outputs are dropped), so the hipGraph captured
 for the batch is replayed unchanged.
 
+With ``prefix_cache_pages`` the batcher keeps the page-aligned prefixes of the prompts it has
+seen on shared KV pages (``Batch.save_prefix``) and starts a request that begins like one of them
+from those pages (``Batch.load_prefix`` + ``append`` of the remainder) instead of prefilling the
+same ids again.
+
 One sampling configuration per batcher (``qie_sampling`` is per step); slot rows are
 independent, so a request's tokens do not depend on what the other slots hold.
 """
@@ -36,6 +41,7 @@ class Request:
     pages: int = 0
     done: bool = False
     chunks: list = dataclasses.field(default_factory=list)   # (offset, length) prompt pieces still to prefill
+    matched: int = 0          # prompt ids taken from the prefix cache (a multiple of page_tokens)
 
 
 def prefill_runs(admitted: Sequence[Request]) -> List[List[Request]]:
@@ -76,10 +82,45 @@ def score_pieces(ids: Sequence[int], chunk: Optional[int] = None, pos0: int = 0)
     return [(pos0 + off, ids[off:off + n], targets[off:off + n]) for off, n in prefill_chunks(len(ids), chunk)]
 
 
+def longest_prefix_match(prompt: Sequence[int], cached: Sequence[Sequence[int]], page_tokens: int) -> tuple:
+    """(n, index): the longest page-aligned prefix of `prompt` that one of the id lists in
+    `cached` begins with — n ids, a multiple of page_tokens — and which list (the first of
+    equally long matches); (0, -1) without one.  n is capped at
+    ((len(prompt) - 1) // page_tokens) * page_tokens, so at least one id is left to append."""
+    cap = ((len(prompt) - 1) // page_tokens) * page_tokens if len(prompt) else 0
+    best, idx = 0, -1
+    for i, ids in enumerate(cached):
+        lim = min(cap, (len(ids) // page_tokens) * page_tokens)
+        n = 0
+        while n < lim and prompt[n] == ids[n]:
+            n += 1
+        n = (n // page_tokens) * page_tokens
+        if n > best:
+            best, idx = n, i
+    return best, idx
+
+
+@dataclasses.dataclass
+class CacheEntry:
+    prefix: object            # engine.Prefix
+    ids: List[int]
+    pages: List[int]          # the pool pages it references
+    used: int = 0             # the batcher's clock at its last save / hit (least recently used goes first)
+
+
 class ContinuousBatcher:
     def __init__(self, engine: Engine, slots: int = 8, max_ctx: Optional[int] = None, page_tokens: int = 128,
                  n_pages: int = 0, sampling: Sampling = GREEDY, keep_logits: bool = False,
-                 prefill_chunk: Optional[int] = None, keep_logprobs: bool = False):
+                 prefill_chunk: Optional[int] = None, keep_logprobs: bool = False, prefix_cache_pages: int = 0):
+        # prefix_cache_pages > 0: prompts' page-aligned prefixes stay cached on shared KV pages
+        # (Batch.save_prefix) and a later prompt that begins alike loads them instead of
+        # prefilling them again; at most that many pages are held by the cache alone.  0: off,
+        # the batcher makes exactly the calls it made without the cache.
+        self.prefix_cache_pages = int(prefix_cache_pages)
+        self.cache: List[CacheEntry] = []
+        self.prefix_hits = 0
+        self.prefix_tokens_reused = 0
+        self._clock = 0
         # prefill_chunk: a prompt longer than this takes its first chunk at admission and one
         # more chunk per step() (qie_prefill_append), so an admission stalls the live slots for
         # one chunk's prefill at a time; its first token is emitted after the last chunk
@@ -119,6 +160,8 @@ class ContinuousBatcher:
         self.slots[r.slot] = None
         self.budget += r.pages
         r.slot = -1
+        if self.prefix_cache_pages > 0:
+            self._trim_cache()   # pages the finished request shared with the cache are now the cache's alone
 
     def _logprobs(self, toks: Dict[int, int]):
         """Log-probability of toks[slot] under each of those slots' current logits (None when
@@ -137,7 +180,133 @@ class ContinuousBatcher:
         if len(r.tokens) >= r.max_new_tokens or tok in r.stop_ids:
             self._finish(r)
 
+    # ------------------------------------------------------------ prefix cache
+    # Accounting with the cache on reads the pool itself: a request needs pages(prompt +
+    # max_new_tokens) minus the pages it shares with its match (Request.pages), and is admitted
+    # when that fits in the pool's free pages minus what the live requests have not drawn yet.
+    # Nothing the batcher does writes into a shared page (a loaded slot appends and decodes from
+    # its match's end, a page boundary; a slot is saved only once its whole prompt is cached), so
+    # no call makes a private copy and every admitted request's pages are there when it draws them.
+    def _room(self) -> int:
+        free, per, _ = self.batch.page_stats()
+        owed = sum(max(0, r.pages - (int(per[r.slot]) - r.matched // self.page_tokens)) for r in self.slots if r)
+        return free - owed
+
+    def _cache_only_pages(self) -> int:
+        refs = self.batch.page_refs()
+        holders = collections.Counter(p for e in self.cache for p in e.pages)
+        return sum(1 for p, c in holders.items() if int(refs[p]) == c)
+
+    def _evict(self, keep: Optional[CacheEntry] = None) -> bool:
+        """Drops the least recently used entry (`keep` only when nothing else is left)."""
+        if not self.cache:
+            return False
+        rest = [e for e in self.cache if e is not keep] or self.cache
+        e = min(rest, key=lambda x: x.used)
+        e.prefix.drop()
+        self.cache.remove(e)
+        return True
+
+    def _trim_cache(self) -> None:
+        while self.cache and self._cache_only_pages() > self.prefix_cache_pages:
+            self._evict()
+
+    def drop_cache(self) -> None:
+        while self._evict():
+            pass
+
+    def _save(self, r: Request) -> None:
+        """The request's whole prompt is cached: one handle for its page-aligned part, unless an
+        entry already covers it."""
+        n = (len(r.prompt) // self.page_tokens) * self.page_tokens
+        if n == 0 or any(len(e.ids) >= n and e.ids[:n] == r.prompt[:n] for e in self.cache):
+            return
+        self._clock += 1
+        pages = [int(p) for p in self.batch.block_table(r.slot, n // self.page_tokens)]
+        self.cache.append(CacheEntry(self.batch.save_prefix(r.slot, n), r.prompt[:n], pages, self._clock))
+        self._trim_cache()
+
+    def _flush_whole(self, whole: List[Request], out: list) -> None:
+        """Prefills the admitted whole prompts without a match (grouped as prefill_runs groups
+        them), saves them and emits their first tokens in admission order."""
+        if not whole:
+            return
+        first: Dict[int, int] = {}
+        for run in prefill_runs(whole):
+            if len(run) == 1:
+                first[run[0].rid] = self.batch.prefill(run[0].slot, run[0].prompt, self.sampling)
+            else:
+                toks = self.batch.prefill_batch(run[0].slot, [r.prompt for r in run], self.sampling)
+                first.update((r.rid, t) for r, t in zip(run, toks))
+        lg = self.batch.logits() if self.keep_logits else None
+        lps = self._logprobs({r.slot: first[r.rid] for r in whole})
+        for r in whole:
+            self._save(r)
+        for r in whole:
+            self._emit(r, first[r.rid], out, lg, lps)
+        whole.clear()
+
+    def _admit_cached(self, out: list) -> None:
+        T = self.page_tokens
+        whole: List[Request] = []   # admitted, no match, not chunked: prefilled together at the next flush
+        while self.waiting:
+            r = self.waiting[0]
+            free_slot = next((i for i, s in enumerate(self.slots) if s is None), None)
+            if free_slot is None:
+                break
+            # a request admitted just before may hold this one's prefix: cache it first
+            if whole and longest_prefix_match(r.prompt, [w.prompt for w in whole], T)[0] > 0:
+                self._flush_whole(whole, out)
+                continue   # (a request that finished at its first token freed a slot)
+            total = self._pages(len(r.prompt) + r.max_new_tokens)
+            n, idx = longest_prefix_match(r.prompt, [e.ids for e in self.cache], T)
+            entry = self.cache[idx] if n else None
+            # Only a whole prompt without a match may wait in `whole`.  Anything else prefills now,
+            # and the pending run goes first — BEFORE this request is accounted: the flush saves
+            # entries and may finish requests, and either can trim the cache, the matched entry
+            # included.  So flush and look the request up again; from the lookup below to
+            # load_prefix nothing then touches the cache but the eviction loop, which keeps `entry`.
+            if whole and (n or len(prefill_chunks(len(r.prompt), self.prefill_chunk)) > 1):
+                self._flush_whole(whole, out)
+                continue
+            # (_room counts the requests of `whole` too: they hold their slots and have drawn nothing)
+            while total - n // T > self._room() and self._evict(keep=entry):
+                if entry is not None and entry not in self.cache:
+                    n, entry = 0, None
+            need = total - n // T
+            if need > self._room():
+                break                           # FIFO: later requests wait behind the head
+            self.waiting.popleft()
+            r.slot, r.pages, r.matched = free_slot, need, n
+            self.budget -= need
+            self.slots[free_slot] = r
+            if n:
+                self._clock += 1
+                entry.used = self._clock
+                self.prefix_hits += 1
+                self.prefix_tokens_reused += n
+            pieces = [(n + off, m) for off, m in prefill_chunks(len(r.prompt) - n, self.prefill_chunk)]
+            if not n and len(pieces) == 1:
+                whole.append(r)
+                continue
+            assert not whole and (entry is None or entry in self.cache)
+            # pieces that follow a match are singletons; the first piece of an unmatched chunked
+            # prompt starts the sequence
+            off, m = pieces[0]
+            if n:
+                self.batch.load_prefix(entry.prefix, r.slot, r.prompt[n], n)
+                tok = self.batch.append(r.slot, r.prompt[off:off + m], off, self.sampling)
+            else:
+                tok = self.batch.prefill(r.slot, r.prompt[:m], self.sampling)
+            r.chunks = pieces[1:]
+            if not r.chunks:
+                self._save(r)
+                self._emit(r, tok, out)
+        self._flush_whole(whole, out)
+
     def _admit(self, out: list) -> None:
+        if self.prefix_cache_pages > 0:
+            return self._admit_cached(out)
         admitted: List[Request] = []
         while self.waiting:
             r = self.waiting[0]
@@ -183,6 +352,8 @@ class ContinuousBatcher:
             off, n = r.chunks.pop(0)
             tok = self.batch.append(r.slot, r.prompt[off:off + n], off, self.sampling)
             if not r.chunks:
+                if self.prefix_cache_pages > 0:
+                    self._save(r)
                 self._emit(r, tok, out)
 
     def step(self) -> List[tuple]:
