@@ -153,7 +153,11 @@ void qie_batch_destroy(qie_batch* b);
  * page_tokens tokens (a power of two >= 128; 0 = 128) shared by the B slots;
  * n_pages 0 = enough for every slot at max_ctx.  Pages are taken on demand by
  * qie_prefill / qie_decode* / qie_batch_set_position and returned by
- * qie_batch_release; running out of pages fails the call (-28, nothing launched).
+ * qie_batch_release; running out of pages fails the call with nothing launched and nothing
+ * changed: -28 from qie_prefill_append, qie_score at pos0 >= 1, qie_verify, qie_batch_fork
+ * and a qie_batch_set_position into a shared page; -22 from qie_prefill, qie_prefill_batch,
+ * qie_score at pos0 = 0, qie_decode_step, qie_decode, qie_batch_reserve and a
+ * qie_batch_set_position that only grows.
  * Page 0 is a scratch page that idle slots write into. */
 int qie_batch_create_paged(qie_engine* e, int32_t batch, int32_t max_ctx, int32_t page_tokens,
                            int32_t n_pages, qie_batch** out);
@@ -269,7 +273,8 @@ int qie_batch_set_position(qie_batch* b, int32_t seq, int32_t pos, int32_t token
  * references.  Every writer of the engine tier — the decode steps, qie_verify, qie_prefill_append /
  * qie_score at pos0 >= 1, qie_batch_set_position — first replaces the pages of its write range that
  * another holder shares by private ones (copying the rows below its first position), counted in
- * its all-or-nothing pool check (-28); the other holder's pages are never touched.  The operator
+ * its all-or-nothing pool check (-28, the decode steps -22: the list at qie_batch_create_paged);
+ * the other holder's pages are never touched.  The operator
  * tier's raw descriptors (qie_batch_kv_cache, qie_kv_write, qie_batch_reserve) do none of this:
  * writing through one into a page qie_batch_page_refs shows shared is the caller's doing.
  *

@@ -166,7 +166,7 @@ struct qie_batch {
     // the free list, the pages held per slot and the count per page live in `pool`
     // (page_pool.hpp), the device table [B + 1][max_pages] mirrors its table.  Row B belongs to
     // no slot: a writer stages the shared page it is replacing there, so that qie_kv_copy can
-    // read the old page and write the new one through the one table (make_writable).
+    // read the old page and write the new one through the one table (commit_kv_writes).
     int page_tokens = 0, max_pages = 0, n_pages = 0;
     int32_t* d_table = nullptr;
     PagePool pool;
@@ -268,6 +268,17 @@ static RopeCurArgs rope_cur_args(const qie_batch* b) {
     return RopeCurArgs{b->dec.rope_cur, e->rope_cos, e->rope_sin, (int)e->spec.head_dim, e->rope_rows};
 }
 
+// Enqueues set_state_kernel for one slot: position, step counter, history[pos] = tok and the RoPE
+// row; write_row: also the next input row x[slot] = E[tok].
+static int set_slot_state(qie_batch* b, int slot, int pos, int step, int tok, int write_row) {
+    const qie_engine* e = b->e;
+    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(256), 0, e->stream, slot, pos, step, tok, b->dec.pos, b->dec.step,
+                       b->dec.hist, b->max_ctx, (const uint4*)e->w.embed, (uint4*)b->dec.x, (int64_t)e->spec.hidden / 8,
+                       write_row, rope_cur_args(b));
+    QIE_LAUNCH_CHECK();
+    return 0;
+}
+
 // KV descriptor of the batch's sequences seq0.. (kernels see them as sequences 0..)
 static qie_kv_cache batch_cache(const qie_batch* b, int seq0) {
     const qie_engine* e = b->e;
@@ -289,69 +300,6 @@ static qie_kv_cache batch_cache(const qie_batch* b, int seq0) {
     }
     return c;
 }
-
-// ------------------------------------------------------------ page pool
-// Host-side allocator of the paged batch.  Decisions are deterministic, so the
-// tensor-parallel ranks (each holding its own heads' pages) stay in step.
-
-static int ensure_pages(qie_batch* b, int seq, int64_t ntok) {
-    if (!b->d_table) return 0;
-    const int64_t need = b->pool.pages_for(ntok);
-    QIE_REQUIRE(need <= b->max_pages, "KV pages: %lld tokens exceed max_ctx %d", (long long)ntok, b->max_ctx);
-    int64_t extra = need - b->pool.held[seq];
-    QIE_REQUIRE(extra <= b->pool.free_count(), "KV pages: sequence %d needs %lld more pages, %lld free", seq,
-                (long long)extra, (long long)b->pool.free_count());
-    if (extra > 0) {
-        b->pool.grow(seq, ntok);
-        b->table_dirty = true;
-    }
-    return 0;
-}
-
-// the slot lets go of its pages: those no other holder references return to the free list
-static void drop_pages(qie_batch* b, int seq) {
-    if (!b->d_table) return;
-    b->pool.release(seq);
-    b->table_dirty = true;
-}
-
-// uploads the host table (ordered after everything already on the stream)
-static int flush_table(qie_batch* b) {
-    if (!b->d_table || !b->table_dirty) return 0;
-    // on the engine stream (non-blocking: a legacy-null-stream copy is not ordered before its
-    // kernels), complete before the host table may change again
-    QIE_HIP(hipMemcpyAsync(b->d_table, b->pool.table.data(), b->pool.table.size() * 4, hipMemcpyHostToDevice, b->e->stream));
-    QIE_HIP(hipStreamSynchronize(b->e->stream));
-    b->table_dirty = false;
-    return 0;
-}
-
-// The writers' planning step (prepare_steps, qie_verify, an append, qie_batch_set_position): what
-// writing positions [lo, hi] of slot seq takes from the pool — growth plus a private replacement
-// for every page of the range another holder shares.  Changes nothing; the caller
-// adds fresh() to its pool check.
-static PagePool::WritePlan plan_write(const qie_batch* b, int seq, int64_t lo, int64_t hi) {
-    return b->d_table ? b->pool.plan_write(seq, lo, hi) : PagePool::WritePlan{};
-}
-
-// Applies a checked plan: the slot's shared pages of [lo, hi] become private ones, it grows to hold
-// hi + 1 tokens, and the rows below lo of the page holding lo are copied from the page it shared
-// (staged in table row B) into its replacement.  The other holders' pages are not touched.
-static int make_writable(qie_batch* b, int seq, const PagePool::WritePlan& w, int64_t lo, int64_t hi) {
-    if (!b->d_table || w.fresh() == 0) return 0;
-    int32_t was = 0, now = 0;
-    b->pool.make_private(seq, w, lo, hi, &was, &now);
-    b->table_dirty = true;
-    if (!now) return 0;   // no page with rows to keep (or another slot of this call made it private first)
-    b->pool.row(b->B)[w.copy_index] = was;
-    QIE_TRY(flush_table(b));
-    const qie_kv_cache c = batch_cache(b, 0);
-    const int rc = qie_kv_copy(&c, b->B, &c, seq, w.copy_index * b->page_tokens, w.copy_rows, b->e->stream);
-    b->pool.row(b->B)[w.copy_index] = 0;
-    b->table_dirty = true;
-    return rc;
-}
-
 
 static int build_rope(qie_engine* e) {
     const int hd = e->spec.head_dim, half = hd / 2, rows = e->opts.max_ctx;
@@ -1321,9 +1269,262 @@ void qie_engine_destroy(qie_engine* e) {
     delete e;
 }
 
+// ------------------------------------------------------------ page pool
+// Host-side allocator of the paged batch (page_pool.hpp) and the entry points that
+// deal in pages and slots.  Decisions are deterministic, so the tensor-parallel ranks (each
+// holding its own heads' pages) stay in step.
+
+// uploads the host table (ordered after everything already on the stream)
+static int flush_table(qie_batch* b) {
+    if (!b->d_table || !b->table_dirty) return 0;
+    // on the engine stream (non-blocking: a legacy-null-stream copy is not ordered before its
+    // kernels), complete before the host table may change again
+    QIE_HIP(hipMemcpyAsync(b->d_table, b->pool.table.data(), b->pool.table.size() * 4, hipMemcpyHostToDevice, b->e->stream));
+    QIE_HIP(hipStreamSynchronize(b->e->stream));
+    b->table_dirty = false;
+    return 0;
+}
+
+// The reservation of one engine call: every call that writes KV rows names them
+// as spans — positions [lo, hi] of a slot; hi < lo: only growth to lo tokens; restart: the slot
+// begins a new sequence — plans them, compares need with free under its own error line, and
+// commits.  This pair is the only place where a writer touches the pool.
+struct KvWrites {
+    PagePool::Reservation r;   // r.need: growth plus a private copy of every shared page of the spans
+    int64_t free = 0;
+    bool fits() const { return r.need <= free; }
+};
+
+// Changes nothing.  A contiguous batch has no pool: nothing is needed, and commit returns at once.
+static int plan_kv_writes(const qie_batch* b, const PagePool::Span* spans, int n, KvWrites& w) {
+    w = KvWrites{};
+    if (!b->d_table) return 0;
+    QIE_REQUIRE(n <= kMaxBatchSlots, "KV pages: %d spans in one call", n);
+    for (int i = 0; i < n; i++) {
+        const int64_t ntok = spans[i].hi >= spans[i].lo ? spans[i].hi + 1 : spans[i].lo;
+        QIE_REQUIRE(b->pool.pages_for(ntok) <= b->max_pages, "KV pages: %lld tokens exceed max_ctx %d",
+                    (long long)ntok, b->max_ctx);
+    }
+    w.r = b->pool.plan_reserve(spans, n);
+    w.free = b->pool.free_count();
+    return 0;
+}
+
+// Applies a plan that fits: restart slots let go of their pages, shared pages of the spans become
+// private ones, every slot grows, and for each replaced page with rows below lo those rows are
+// copied from the page the slot shared — staged in table row B, so that qie_kv_copy reads it
+// through the one table — into its replacement.  The other holders' pages are not touched.
+static int commit_kv_writes(qie_batch* b, const KvWrites& w) {
+    if (!b->d_table) return 0;
+    bool changes = w.r.need != 0;
+    for (int i = 0; i < w.r.n; i++) changes |= w.r.spans[i].restart;
+    if (changes) {
+        PagePool::CopyJob jobs[kMaxBatchSlots];
+        const int n_jobs = b->pool.commit(w.r, jobs);
+        b->table_dirty = true;
+        const qie_kv_cache c = batch_cache(b, 0);
+        for (int j = 0; j < n_jobs; j++) {
+            b->pool.row(b->B)[jobs[j].index] = jobs[j].old_page;
+            QIE_TRY(flush_table(b));
+            const int rc = qie_kv_copy(&c, b->B, &c, jobs[j].slot, jobs[j].index * b->page_tokens, jobs[j].rows,
+                                       b->e->stream);
+            b->pool.row(b->B)[jobs[j].index] = 0;
+            b->table_dirty = true;
+            QIE_TRY(rc);
+        }
+    }
+    return flush_table(b);
+}
+
+// Slot dst becomes a live sequence at position n with current token tok and step counter step_v:
+// its next input row, RoPE row and history[n] as set_state_kernel sets them; synchronises.  The
+// one tail of qie_batch_set_position, qie_batch_fork and qie_batch_prefix_load.
+static int start_slot(qie_batch* b, int dst, int n, int step_v, int tok) {
+    QIE_TRY(set_slot_state(b, dst, n, step_v, tok, 1));
+    QIE_HIP(hipStreamSynchronize(b->e->stream));
+    b->idle[dst] = 0;
+    b->h_pos[dst] = n;
+    return 0;
+}
+
+int qie_batch_release(qie_batch* b, int32_t seq) {
+    QIE_REQUIRE(b && seq >= 0 && seq < b->B, "qie_batch_release: bad arguments");
+    if (b->d_table) {   // the pages no other holder references return to the free list
+        b->pool.release(seq);
+        b->table_dirty = true;
+    }
+    b->idle[seq] = 1;
+    QIE_TRY(flush_table(b));
+    QIE_TRY(set_slot_state(b, seq, 0, 0, 0, 1));
+    QIE_HIP(hipStreamSynchronize(b->e->stream));
+    b->h_pos[seq] = 0;
+    return 0;
+}
+
+int qie_batch_page_stats(qie_batch* b, int32_t* free_pages, int32_t* pages_per_seq, int32_t* page_tokens) {
+    QIE_REQUIRE(b, "qie_batch_page_stats: null batch");
+    if (free_pages) *free_pages = (int32_t)b->pool.free_count();
+    if (pages_per_seq)
+        for (int m = 0; m < b->B; m++) pages_per_seq[m] = b->d_table ? b->pool.held[m] : 0;
+    if (page_tokens) *page_tokens = b->page_tokens;
+    return 0;
+}
+
+int qie_batch_block_table(qie_batch* b, int32_t seq, int32_t* host_pages, int32_t n) {
+    QIE_REQUIRE(b && b->d_table && host_pages && seq >= 0 && seq < b->B && n >= 0 && n <= b->max_pages,
+                "qie_batch_block_table: bad arguments (paged batch, n <= max_pages)");
+    QIE_HIP(hipStreamSynchronize(b->e->stream));
+    QIE_HIP(d2h(b->e, host_pages, b->d_table + (int64_t)seq * b->max_pages, (size_t)n * 4));
+    return 0;
+}
+
+int qie_batch_reserve(qie_batch* b, int32_t seq, int32_t n_tokens) {
+    QIE_REQUIRE(b && seq >= 0 && seq < b->B && n_tokens >= 0, "qie_batch_reserve: bad arguments");
+    QIE_REQUIRE(n_tokens <= b->max_ctx, "qie_batch_reserve: %d tokens exceed max_ctx %d", n_tokens, b->max_ctx);
+    // a grow-only span: the raw tier ignores sharing on purpose
+    const PagePool::Span span{seq, n_tokens, (int64_t)n_tokens - 1, false};
+    KvWrites kv;
+    QIE_TRY(plan_kv_writes(b, &span, 1, kv));
+    QIE_REQUIRE(kv.fits(), "KV pages: sequence %d needs %lld more pages, %lld free", seq, (long long)kv.r.need,
+                (long long)kv.free);
+    QIE_TRY(commit_kv_writes(b, kv));
+    b->idle[seq] = 0;
+    return 0;
+}
+
+int qie_batch_set_position(qie_batch* b, int32_t seq, int32_t pos, int32_t token) {
+    QIE_REQUIRE(b && seq >= 0 && seq < b->B && pos >= 0 && pos + 1 < b->max_ctx && token >= 0 &&
+                    token < b->e->spec.vocab,
+                "qie_batch_set_position: bad arguments");
+    // a rewind into a page another holder shares: this slot gets a private copy of it first
+    const PagePool::Span span{seq, pos, pos, false};
+    KvWrites kv;
+    QIE_TRY(plan_kv_writes(b, &span, 1, kv));
+    if (!kv.fits() && kv.r.plans[0].n_private)
+        return fail(-28, "qie_batch_set_position: KV pool exhausted (position %d lies in a shared page: %lld pages "
+                         "needed, %lld free)", pos, (long long)kv.r.need, (long long)kv.free);
+    QIE_REQUIRE(kv.fits(), "KV pages: sequence %d needs %lld more pages, %lld free", seq, (long long)kv.r.need,
+                (long long)kv.free);
+    QIE_TRY(commit_kv_writes(b, kv));
+    return start_slot(b, seq, pos, pos, token);
+}
+
+// --- forks and prefix handles: they share pages (a fork draws at most its tail page, after its
+// own check) and write no rows, so they use the pool directly
+
+int qie_batch_fork(qie_batch* b, int32_t src, int32_t dst, int32_t n_tokens, int32_t step_offset) {
+    QIE_REQUIRE(b && src >= 0 && src < b->B && dst >= 0 && dst < b->B && src != dst,
+                "qie_batch_fork: bad arguments (two different slots of the batch)");
+    QIE_REQUIRE(!b->idle[src], "qie_batch_fork: slot %d holds no live sequence", src);
+    const int p = b->h_pos[src], n = n_tokens;
+    QIE_REQUIRE(n >= 1 && n <= p, "qie_batch_fork: n_tokens %d outside [1, %d] (the source's position)", n, p);
+    if (b->d_table && !b->pool.fork_fits(dst, n))
+        return fail(-28, "qie_batch_fork: KV pool exhausted (no page for the %d rows past the last full page; "
+                         "%lld free)", n % b->page_tokens, (long long)b->pool.free_count());
+    // nothing can fail for lack of pages from here on
+    qie_engine* e = b->e;
+    hipStream_t st = e->stream;
+    int32_t tok_step[2] = {0, 0};   // the source's history[n] and its step counter
+    QIE_HIP(hipMemcpyAsync(&tok_step[0], b->dec.hist + (int64_t)src * b->max_ctx + n, 4, hipMemcpyDeviceToHost, st));
+    QIE_HIP(hipMemcpyAsync(&tok_step[1], b->dec.step + src, 4, hipMemcpyDeviceToHost, st));
+    QIE_HIP(hipStreamSynchronize(st));
+    const int tok = tok_step[0];
+    // every writer of the history stores ids in [0, vocab): anything else means the history is
+    // corrupt, and a fork would only copy the damage — fail while nothing has changed
+    if (tok < 0 || tok >= e->spec.vocab)
+        return fail(-5, "qie_batch_fork: history[%d] of slot %d holds %d, not a token id", n, src, tok);
+    const qie_kv_cache c = batch_cache(b, 0);
+    if (b->d_table) {   // full pages shared, the partial last page copied into a page of dst's own
+        b->pool.fork(src, dst, n);
+        b->table_dirty = true;
+        QIE_TRY(flush_table(b));
+        const int tail = n % b->page_tokens;
+        QIE_TRY(qie_kv_copy(&c, src, &c, dst, n - tail, tail, st));
+    } else {
+        QIE_TRY(qie_kv_copy(&c, src, &c, dst, 0, n, st));
+    }
+    QIE_HIP(hipMemcpyAsync(b->dec.hist + (int64_t)dst * b->max_ctx, b->dec.hist + (int64_t)src * b->max_ctx,
+                           (size_t)(n + 1) * 4, hipMemcpyDeviceToDevice, st));
+    if (n == p)   // the pending token's logits: row dst of qie_batch_logits equals row src
+        QIE_HIP(hipMemcpyAsync(b->dec.logits + (int64_t)dst * e->sh.vocab, b->dec.logits + (int64_t)src * e->sh.vocab,
+                               (size_t)e->sh.vocab * 2, hipMemcpyDeviceToDevice, st));
+    return start_slot(b, dst, n, tok_step[1] + step_offset, tok);
+}
+
+int qie_batch_page_refs(qie_batch* b, int32_t* host_refs, int32_t n) {
+    QIE_REQUIRE(b && b->d_table && host_refs && n >= 0 && n <= b->n_pages,
+                "qie_batch_page_refs: bad arguments (paged batch, n <= its pages)");
+    for (int i = 0; i < n; i++) host_refs[i] = b->pool.refs[i];
+    return 0;
+}
+
+int qie_batch_prefix_save(qie_batch* b, int32_t seq, int32_t n_tokens, qie_kv_prefix** out) {
+    QIE_REQUIRE(b && out && seq >= 0 && seq < b->B, "qie_batch_prefix_save: bad arguments");
+    QIE_REQUIRE(b->d_table, "qie_batch_prefix_save: prefix handles need a paged batch");
+    QIE_REQUIRE(!b->idle[seq], "qie_batch_prefix_save: slot %d holds no live sequence", seq);
+    QIE_REQUIRE(n_tokens > 0 && n_tokens % b->page_tokens == 0 && n_tokens <= b->h_pos[seq],
+                "qie_batch_prefix_save: n_tokens %d must be a positive multiple of %d and at most the position %d",
+                n_tokens, b->page_tokens, b->h_pos[seq]);
+    qie_kv_prefix* p = new qie_kv_prefix();
+    p->owner = b;
+    p->ids.resize(n_tokens);
+    const hipError_t he = d2h(b->e, p->ids.data(), b->dec.hist + (int64_t)seq * b->max_ctx, (size_t)n_tokens * 4);
+    if (he != hipSuccess) {
+        delete p;
+        return fail((int)he, "qie_batch_prefix_save: reading the history: %s", hipGetErrorString(he));
+    }
+    for (int i = 0; i < n_tokens / b->page_tokens; i++) {
+        p->pages.push_back(b->pool.row(seq)[i]);
+        b->pool.share(p->pages.back());
+    }
+    b->prefixes.push_back(p);
+    *out = p;
+    return 0;
+}
+
+int qie_batch_prefix_load(qie_batch* b, const qie_kv_prefix* p, int32_t dst, int32_t n_tokens, int32_t token) {
+    QIE_REQUIRE(b && p && dst >= 0 && dst < b->B && token >= 0 && token < b->e->spec.vocab,
+                "qie_batch_prefix_load: bad arguments");
+    QIE_REQUIRE(b->d_table && p->owner == b, "qie_batch_prefix_load: the handle belongs to another batch");
+    QIE_REQUIRE(n_tokens > 0 && n_tokens % b->page_tokens == 0 && n_tokens <= (int)p->ids.size() &&
+                    n_tokens + 1 < b->max_ctx,
+                "qie_batch_prefix_load: n_tokens %d must be a positive multiple of %d, at most the handle's %zu and "
+                "below max_ctx", n_tokens, b->page_tokens, p->ids.size());
+    // shares pages only: nothing is taken from the free list, so the call cannot run out
+    b->pool.release(dst);
+    for (int i = 0; i < n_tokens / b->page_tokens; i++) b->pool.push_shared(dst, p->pages[i]);
+    b->table_dirty = true;
+    QIE_TRY(flush_table(b));
+    QIE_HIP(hipMemcpyAsync(b->dec.hist + (int64_t)dst * b->max_ctx, p->ids.data(), (size_t)n_tokens * 4,
+                           hipMemcpyHostToDevice, b->e->stream));
+    return start_slot(b, dst, n_tokens, n_tokens, token);
+}
+
+int qie_batch_prefix_tokens(const qie_kv_prefix* p, int32_t* host_ids, int32_t n) {
+    QIE_REQUIRE(p, "qie_batch_prefix_tokens: null handle");
+    if (!host_ids) return (int)p->ids.size();
+    QIE_REQUIRE(n >= 0 && n <= (int)p->ids.size(), "qie_batch_prefix_tokens: n %d exceeds the handle's %zu ids", n,
+                p->ids.size());
+    std::memcpy(host_ids, p->ids.data(), (size_t)n * 4);
+    return 0;
+}
+
+int qie_batch_prefix_drop(qie_batch* b, qie_kv_prefix* p) {
+    QIE_REQUIRE(b && p && p->owner == b, "qie_batch_prefix_drop: bad arguments");
+    for (size_t i = 0; i < b->prefixes.size(); i++)
+        if (b->prefixes[i] == p) {
+            for (int32_t g : p->pages) b->pool.drop(g);
+            b->prefixes.erase(b->prefixes.begin() + i);
+            delete p;
+            return 0;
+        }
+    return fail(-22, "qie_batch_prefix_drop: not an open handle of this batch");
+}
+
 static int batch_create(qie_engine* e, int32_t batch, int32_t max_ctx, int32_t page_tokens, int32_t n_pages,
                         qie_batch** out) {
-    QIE_REQUIRE(e && out && batch > 0 && batch <= 8 && max_ctx > 1, "qie_batch_create: bad arguments (B <= 8)");
+    QIE_REQUIRE(e && out && batch > 0 && batch <= kMaxBatchSlots && max_ctx > 1,
+                "qie_batch_create: bad arguments (B <= %d)", kMaxBatchSlots);
     QIE_REQUIRE(e->have_weights, "qie_batch_create: engine has no weights");
     QIE_REQUIRE(max_ctx <= e->rope_rows, "qie_batch_create: max_ctx %d > engine max_ctx %d", max_ctx, e->rope_rows);
     const qie_model_spec& s = e->spec;
@@ -1395,37 +1596,6 @@ int qie_batch_create_paged(qie_engine* e, int32_t batch, int32_t max_ctx, int32_
     QIE_REQUIRE(n_pages >= 0, "qie_batch_create_paged: bad n_pages");
     QIE_REQUIRE(n_pages == 0 || n_pages >= 2, "qie_batch_create_paged: need the scratch page and one more");
     return batch_create(e, batch, max_ctx, page_tokens, n_pages, out);
-}
-
-int qie_batch_release(qie_batch* b, int32_t seq) {
-    QIE_REQUIRE(b && seq >= 0 && seq < b->B, "qie_batch_release: bad arguments");
-    drop_pages(b, seq);
-    b->idle[seq] = 1;
-    QIE_TRY(flush_table(b));
-    qie_engine* e = b->e;
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(256), 0, e->stream, seq, 0, 0, 0, b->dec.pos, b->dec.step, b->dec.hist,
-                       b->max_ctx, (const uint4*)e->w.embed, (uint4*)b->dec.x, (int64_t)e->spec.hidden / 8, 1, rope_cur_args(b));
-    QIE_LAUNCH_CHECK();
-    QIE_HIP(hipStreamSynchronize(e->stream));
-    b->h_pos[seq] = 0;
-    return 0;
-}
-
-int qie_batch_page_stats(qie_batch* b, int32_t* free_pages, int32_t* pages_per_seq, int32_t* page_tokens) {
-    QIE_REQUIRE(b, "qie_batch_page_stats: null batch");
-    if (free_pages) *free_pages = (int32_t)b->pool.free_count();
-    if (pages_per_seq)
-        for (int m = 0; m < b->B; m++) pages_per_seq[m] = b->d_table ? b->pool.held[m] : 0;
-    if (page_tokens) *page_tokens = b->page_tokens;
-    return 0;
-}
-
-int qie_batch_block_table(qie_batch* b, int32_t seq, int32_t* host_pages, int32_t n) {
-    QIE_REQUIRE(b && b->d_table && host_pages && seq >= 0 && seq < b->B && n >= 0 && n <= b->max_pages,
-                "qie_batch_block_table: bad arguments (paged batch, n <= max_pages)");
-    QIE_HIP(hipStreamSynchronize(b->e->stream));
-    QIE_HIP(d2h(b->e, host_pages, b->d_table + (int64_t)seq * b->max_pages, (size_t)n * 4));
-    return 0;
 }
 
 void qie_batch_destroy(qie_batch* b) {
@@ -1545,42 +1715,25 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
             QIE_REQUIRE(score->targets[i] >= -1 && score->targets[i] < s.vocab,
                         "%s: target %d of row %lld is neither -1 nor a token id", who, score->targets[i], (long long)i);
     hipStream_t st = e->stream;
-    PagePool::WritePlan wplan;
-    if (append) {   // all-or-nothing, before anything is allocated or launched
-        wplan = plan_write(b, seq0, pos0, (int64_t)pos0 + len - 1);
-        const int64_t need = wplan.fresh();   // growth + a private copy of every shared page of the range
-        if (need > b->pool.free_count())
-            return fail(-28, "%s: KV pool exhausted (%lld more pages needed for %d rows at position %d, %lld free)",
-                        who, (long long)need, len, pos0, (long long)b->pool.free_count());
-    }
+    // all-or-nothing, before anything is allocated or launched.  A prefill from position 0 starts a
+    // new sequence in each slot: every target slot's pages go back to the pool before any slot
+    // draws, and the pages only that slot holds count towards the check
+    PagePool::Span spans[kMaxBatchSlots];   // n_seqs <= B <= kMaxBatchSlots
+    for (int z = 0; z < n_seqs; z++) spans[z] = PagePool::Span{seq0 + z, pos0, (int64_t)pos0 + len - 1, !append};
+    KvWrites kv;
+    QIE_TRY(plan_kv_writes(b, spans, n_seqs, kv));
+    if (!kv.fits() && append)
+        return fail(-28, "%s: KV pool exhausted (%lld more pages needed for %d rows at position %d, %lld free)", who,
+                    (long long)kv.r.need, len, pos0, (long long)kv.free);
+    QIE_REQUIRE(kv.fits(), "%s: KV pool exhausted (%lld pages needed beyond those slots %d..%d hold alone, %lld free)",
+                who, (long long)kv.r.need, seq0, seq0 + n_seqs - 1, (long long)kv.free);
     QIE_TRY(ensure_prefill_scratch(b, n, append));
     if (score) {   // the scoring head's scratch too, before anything is launched
         QIE_TRY(ensure_score_scratch(b, n, score_fused(e, score->flags)));
         if (!score_fused(e, score->flags)) QIE_TRY(ensure_verify_bufs(b));
     }
-    if (b->d_table && !append) {   // all-or-nothing: the slots' own pages count, nothing is dropped on failure
-        // (held: the pages only that slot holds — a page shared with another holder does not
-        // return to the pool when the slot lets go of it)
-        int64_t needed = 0, held = 0;
-        for (int z = 0; z < n_seqs; z++) {
-            needed += b->pool.pages_for(len);
-            held += b->pool.exclusive(seq0 + z);
-        }
-        QIE_REQUIRE(needed - held <= b->pool.free_count(),
-                    "%s: KV pool exhausted (%lld pages needed, %lld free + %lld held by slots %d..%d)", who,
-                    (long long)needed, (long long)b->pool.free_count(), (long long)held, seq0, seq0 + n_seqs - 1);
-    }
-    // a prefill starts a new sequence in each slot: every target slot's pages go back to
-    // the pool BEFORE any slot draws, so the check above (free + held) is exactly what the
-    // draws below can use and none of them can fail part way
-    if (!append)
-        for (int z = 0; z < n_seqs; z++) drop_pages(b, seq0 + z);
-    if (append) QIE_TRY(make_writable(b, seq0, wplan, pos0, (int64_t)pos0 + len - 1));
-    for (int z = 0; z < n_seqs; z++) {
-        QIE_TRY(ensure_pages(b, seq0 + z, (int64_t)pos0 + len));
-        b->idle[seq0 + z] = 0;
-    }
-    QIE_TRY(flush_table(b));
+    QIE_TRY(commit_kv_writes(b, kv));
+    for (int z = 0; z < n_seqs; z++) b->idle[seq0 + z] = 0;
     const int64_t H = s.hidden;
     QIE_HIP(hipMemcpyAsync(b->pf.ids_in, ids, (size_t)n * 4, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b->pf.pos, (int)n, len, pos0);
@@ -1600,12 +1753,8 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
     for (int l = 0; l < s.n_layers; l++)
         QIE_TRY(enqueue_layer_rows(b, l, r, path, cache, append ? qie_attention_extend : qie_attention, b->pf_ws.p));
     // position of each last prompt token; finalize advances it to pos0 + len (the new token).
-    for (int z = 0; z < n_seqs; z++) {
-        hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(64), 0, st, seq0 + z, pos0 + len - 1, 0,
-                           ids[(int64_t)z * len + len - 1], b->dec.pos, b->dec.step, b->dec.hist, b->max_ctx,
-                           (const uint4*)e->w.embed, (uint4*)b->dec.x, (int64_t)H / 8, 0, rope_cur_args(b));
-        QIE_LAUNCH_CHECK();
-    }
+    for (int z = 0; z < n_seqs; z++)
+        QIE_TRY(set_slot_state(b, seq0 + z, pos0 + len - 1, 0, ids[(int64_t)z * len + len - 1], 0));
     const uint16_t* last = b->pf.x + (int64_t)(len - 1) * H;
     if (n_seqs > 1) {   // the last rows, packed (the head's pre-norm reads contiguous rows)
         QIE_HIP(hipMemcpy2DAsync(b->pf.xn, (size_t)H * 2, last, (size_t)len * H * 2, (size_t)H * 2, n_seqs,
@@ -1744,32 +1893,20 @@ static int prepare_steps(qie_batch* b, int n_steps, const char* who) {
         if (!b->idle[m])
             QIE_REQUIRE(b->h_pos[m] + n_steps < b->max_ctx, "%s: sequence %d would exceed max_ctx %d", who, m,
                         b->max_ctx);
-    if (b->d_table) {
-        // growth, plus a private copy of any shared page in the steps' range (only a slot rewound
-        // below a fork point has one: a fork copies its tail page eagerly)
-        int64_t need = 0;
-        PagePool::WritePlan plans[8];   // B <= 8 (batch_create)
-        for (int m = 0; m < b->B; m++)
-            if (!b->idle[m]) {
-                plans[m] = plan_write(b, m, b->h_pos[m], (int64_t)b->h_pos[m] + n_steps - 1);
-                need += plans[m].fresh();
-            }
-        QIE_REQUIRE(need <= b->pool.free_count(), "%s: KV pool exhausted (%lld pages needed, %lld free)", who,
-                    (long long)need, (long long)b->pool.free_count());
-        for (int m = 0; m < b->B; m++)
-            if (!b->idle[m]) {
-                QIE_TRY(make_writable(b, m, plans[m], b->h_pos[m], (int64_t)b->h_pos[m] + n_steps - 1));
-                QIE_TRY(ensure_pages(b, m, b->h_pos[m] + n_steps));
-            }
-        QIE_TRY(flush_table(b));
-    }
-    qie_engine* e = b->e;
+    // growth, plus a private copy of any shared page in the steps' range (only a slot rewound
+    // below a fork point has one: a fork copies its tail page eagerly)
+    PagePool::Span spans[kMaxBatchSlots];
+    int n = 0;
+    for (int m = 0; m < b->B; m++)
+        if (!b->idle[m]) spans[n++] = PagePool::Span{m, b->h_pos[m], (int64_t)b->h_pos[m] + n_steps - 1, false};
+    KvWrites kv;
+    QIE_TRY(plan_kv_writes(b, spans, n, kv));
+    QIE_REQUIRE(kv.fits(), "%s: KV pool exhausted (%lld pages needed, %lld free)", who, (long long)kv.r.need,
+                (long long)kv.free);
+    QIE_TRY(commit_kv_writes(b, kv));
     for (int m = 0; m < b->B; m++)
         if (b->idle[m] && b->h_pos[m] + n_steps >= b->max_ctx) {
-            hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(256), 0, e->stream, m, 0, 0, 0, b->dec.pos, b->dec.step,
-                               b->dec.hist, b->max_ctx, (const uint4*)e->w.embed, (uint4*)b->dec.x,
-                               (int64_t)e->spec.hidden / 8, 1, rope_cur_args(b));
-            QIE_LAUNCH_CHECK();
+            QIE_TRY(set_slot_state(b, m, 0, 0, 0, 1));
             b->h_pos[m] = 0;
         }
     return 0;
@@ -1831,147 +1968,6 @@ int qie_batch_history(qie_batch* b, int32_t seq, int32_t* host_ids, int32_t n) {
     QIE_HIP(hipStreamSynchronize(b->e->stream));
     QIE_HIP(d2h(b->e, host_ids, b->dec.hist + (int64_t)seq * b->max_ctx, (size_t)n * 4));
     return 0;
-}
-
-// Slot dst becomes a live sequence at position n with current token tok and step counter step_v:
-// its next input row, RoPE row and history[n] as set_state_kernel sets them; synchronises.  The
-// one tail of qie_batch_set_position, qie_batch_fork and qie_batch_prefix_load.
-static int start_slot(qie_batch* b, int dst, int n, int step_v, int tok) {
-    qie_engine* e = b->e;
-    hipLaunchKernelGGL(set_state_kernel, dim3(1), dim3(256), 0, e->stream, dst, n, step_v, tok, b->dec.pos, b->dec.step,
-                       b->dec.hist, b->max_ctx, (const uint4*)e->w.embed, (uint4*)b->dec.x,
-                       (int64_t)e->spec.hidden / 8, 1, rope_cur_args(b));
-    QIE_LAUNCH_CHECK();
-    QIE_HIP(hipStreamSynchronize(e->stream));
-    b->idle[dst] = 0;
-    b->h_pos[dst] = n;
-    return 0;
-}
-
-int qie_batch_set_position(qie_batch* b, int32_t seq, int32_t pos, int32_t token) {
-    QIE_REQUIRE(b && seq >= 0 && seq < b->B && pos >= 0 && pos + 1 < b->max_ctx && token >= 0 &&
-                    token < b->e->spec.vocab,
-                "qie_batch_set_position: bad arguments");
-    // a rewind into a page another holder shares: this slot gets a private copy of it first
-    const PagePool::WritePlan wplan = plan_write(b, seq, pos, pos);
-    if (wplan.n_private && wplan.fresh() > b->pool.free_count())
-        return fail(-28, "qie_batch_set_position: KV pool exhausted (position %d lies in a shared page: %lld pages "
-                         "needed, %lld free)", pos, (long long)wplan.fresh(), (long long)b->pool.free_count());
-    if (wplan.n_private) QIE_TRY(make_writable(b, seq, wplan, pos, pos));
-    QIE_TRY(ensure_pages(b, seq, (int64_t)pos + 1));
-    QIE_TRY(flush_table(b));
-    return start_slot(b, seq, pos, pos, token);
-}
-
-// ------------------------------------------------------------ forks and prefix handles
-
-int qie_batch_fork(qie_batch* b, int32_t src, int32_t dst, int32_t n_tokens, int32_t step_offset) {
-    QIE_REQUIRE(b && src >= 0 && src < b->B && dst >= 0 && dst < b->B && src != dst,
-                "qie_batch_fork: bad arguments (two different slots of the batch)");
-    QIE_REQUIRE(!b->idle[src], "qie_batch_fork: slot %d holds no live sequence", src);
-    const int p = b->h_pos[src], n = n_tokens;
-    QIE_REQUIRE(n >= 1 && n <= p, "qie_batch_fork: n_tokens %d outside [1, %d] (the source's position)", n, p);
-    if (b->d_table && !b->pool.fork_fits(dst, n))
-        return fail(-28, "qie_batch_fork: KV pool exhausted (no page for the %d rows past the last full page; "
-                         "%lld free)", n % b->page_tokens, (long long)b->pool.free_count());
-    // nothing can fail for lack of pages from here on
-    qie_engine* e = b->e;
-    hipStream_t st = e->stream;
-    int32_t tok_step[2] = {0, 0};   // the source's history[n] and its step counter
-    QIE_HIP(hipMemcpyAsync(&tok_step[0], b->dec.hist + (int64_t)src * b->max_ctx + n, 4, hipMemcpyDeviceToHost, st));
-    QIE_HIP(hipMemcpyAsync(&tok_step[1], b->dec.step + src, 4, hipMemcpyDeviceToHost, st));
-    QIE_HIP(hipStreamSynchronize(st));
-    const int tok = tok_step[0];
-    // every writer of the history stores ids in [0, vocab): anything else means the history is
-    // corrupt, and a fork would only copy the damage — fail while nothing has changed
-    if (tok < 0 || tok >= e->spec.vocab)
-        return fail(-5, "qie_batch_fork: history[%d] of slot %d holds %d, not a token id", n, src, tok);
-    const qie_kv_cache c = batch_cache(b, 0);
-    if (b->d_table) {   // full pages shared, the partial last page copied into a page of dst's own
-        b->pool.fork(src, dst, n);
-        b->table_dirty = true;
-        QIE_TRY(flush_table(b));
-        const int tail = n % b->page_tokens;
-        QIE_TRY(qie_kv_copy(&c, src, &c, dst, n - tail, tail, st));
-    } else {
-        QIE_TRY(qie_kv_copy(&c, src, &c, dst, 0, n, st));
-    }
-    QIE_HIP(hipMemcpyAsync(b->dec.hist + (int64_t)dst * b->max_ctx, b->dec.hist + (int64_t)src * b->max_ctx,
-                           (size_t)(n + 1) * 4, hipMemcpyDeviceToDevice, st));
-    if (n == p)   // the pending token's logits: row dst of qie_batch_logits equals row src
-        QIE_HIP(hipMemcpyAsync(b->dec.logits + (int64_t)dst * e->sh.vocab, b->dec.logits + (int64_t)src * e->sh.vocab,
-                               (size_t)e->sh.vocab * 2, hipMemcpyDeviceToDevice, st));
-    return start_slot(b, dst, n, tok_step[1] + step_offset, tok);
-}
-
-int qie_batch_page_refs(qie_batch* b, int32_t* host_refs, int32_t n) {
-    QIE_REQUIRE(b && b->d_table && host_refs && n >= 0 && n <= b->n_pages,
-                "qie_batch_page_refs: bad arguments (paged batch, n <= its pages)");
-    for (int i = 0; i < n; i++) host_refs[i] = b->pool.refs[i];
-    return 0;
-}
-
-int qie_batch_prefix_save(qie_batch* b, int32_t seq, int32_t n_tokens, qie_kv_prefix** out) {
-    QIE_REQUIRE(b && out && seq >= 0 && seq < b->B, "qie_batch_prefix_save: bad arguments");
-    QIE_REQUIRE(b->d_table, "qie_batch_prefix_save: prefix handles need a paged batch");
-    QIE_REQUIRE(!b->idle[seq], "qie_batch_prefix_save: slot %d holds no live sequence", seq);
-    QIE_REQUIRE(n_tokens > 0 && n_tokens % b->page_tokens == 0 && n_tokens <= b->h_pos[seq],
-                "qie_batch_prefix_save: n_tokens %d must be a positive multiple of %d and at most the position %d",
-                n_tokens, b->page_tokens, b->h_pos[seq]);
-    qie_kv_prefix* p = new qie_kv_prefix();
-    p->owner = b;
-    p->ids.resize(n_tokens);
-    const hipError_t he = d2h(b->e, p->ids.data(), b->dec.hist + (int64_t)seq * b->max_ctx, (size_t)n_tokens * 4);
-    if (he != hipSuccess) {
-        delete p;
-        return fail((int)he, "qie_batch_prefix_save: reading the history: %s", hipGetErrorString(he));
-    }
-    for (int i = 0; i < n_tokens / b->page_tokens; i++) {
-        p->pages.push_back(b->pool.row(seq)[i]);
-        b->pool.share(p->pages.back());
-    }
-    b->prefixes.push_back(p);
-    *out = p;
-    return 0;
-}
-
-int qie_batch_prefix_load(qie_batch* b, const qie_kv_prefix* p, int32_t dst, int32_t n_tokens, int32_t token) {
-    QIE_REQUIRE(b && p && dst >= 0 && dst < b->B && token >= 0 && token < b->e->spec.vocab,
-                "qie_batch_prefix_load: bad arguments");
-    QIE_REQUIRE(b->d_table && p->owner == b, "qie_batch_prefix_load: the handle belongs to another batch");
-    QIE_REQUIRE(n_tokens > 0 && n_tokens % b->page_tokens == 0 && n_tokens <= (int)p->ids.size() &&
-                    n_tokens + 1 < b->max_ctx,
-                "qie_batch_prefix_load: n_tokens %d must be a positive multiple of %d, at most the handle's %zu and "
-                "below max_ctx", n_tokens, b->page_tokens, p->ids.size());
-    // shares pages only: nothing is taken from the free list, so the call cannot run out
-    b->pool.release(dst);
-    for (int i = 0; i < n_tokens / b->page_tokens; i++) b->pool.push_shared(dst, p->pages[i]);
-    b->table_dirty = true;
-    QIE_TRY(flush_table(b));
-    QIE_HIP(hipMemcpyAsync(b->dec.hist + (int64_t)dst * b->max_ctx, p->ids.data(), (size_t)n_tokens * 4,
-                           hipMemcpyHostToDevice, b->e->stream));
-    return start_slot(b, dst, n_tokens, n_tokens, token);
-}
-
-int qie_batch_prefix_tokens(const qie_kv_prefix* p, int32_t* host_ids, int32_t n) {
-    QIE_REQUIRE(p, "qie_batch_prefix_tokens: null handle");
-    if (!host_ids) return (int)p->ids.size();
-    QIE_REQUIRE(n >= 0 && n <= (int)p->ids.size(), "qie_batch_prefix_tokens: n %d exceeds the handle's %zu ids", n,
-                p->ids.size());
-    std::memcpy(host_ids, p->ids.data(), (size_t)n * 4);
-    return 0;
-}
-
-int qie_batch_prefix_drop(qie_batch* b, qie_kv_prefix* p) {
-    QIE_REQUIRE(b && p && p->owner == b, "qie_batch_prefix_drop: bad arguments");
-    for (size_t i = 0; i < b->prefixes.size(); i++)
-        if (b->prefixes[i] == p) {
-            for (int32_t g : p->pages) b->pool.drop(g);
-            b->prefixes.erase(b->prefixes.begin() + i);
-            delete p;
-            return 0;
-        }
-    return fail(-22, "qie_batch_prefix_drop: not an open handle of this batch");
 }
 
 // ------------------------------------------------------------ speculative verify
@@ -2063,15 +2059,14 @@ int qie_verify(qie_batch* b, int32_t seq, const int32_t* draft, int32_t n_draft,
     QIE_REQUIRE((int64_t)p + n_draft + 1 < b->max_ctx, "qie_verify: %d rows from position %d do not fit max_ctx %d", M,
                 p, b->max_ctx);
     // all-or-nothing, before anything is allocated or launched (growth + a private copy of a shared page)
-    const PagePool::WritePlan wplan = plan_write(b, seq, p, (int64_t)p + M - 1);
-    const int64_t need = wplan.fresh();
-    if (need > b->pool.free_count())
+    const PagePool::Span span{seq, p, (int64_t)p + M - 1, false};
+    KvWrites kv;
+    QIE_TRY(plan_kv_writes(b, &span, 1, kv));
+    if (!kv.fits())
         return fail(-28, "qie_verify: KV pool exhausted (%lld more pages needed for %d rows at position %d, %lld free)",
-                    (long long)need, M, p, (long long)b->pool.free_count());
+                    (long long)kv.r.need, M, p, (long long)kv.free);
     QIE_TRY(ensure_verify_bufs(b));
-    QIE_TRY(make_writable(b, seq, wplan, p, (int64_t)p + M - 1));
-    QIE_TRY(ensure_pages(b, seq, (int64_t)p + M));
-    QIE_TRY(flush_table(b));
+    QIE_TRY(commit_kv_writes(b, kv));
     hipStream_t st = e->stream;
     if (n_draft > 0) QIE_HIP(hipMemcpyAsync(b->v.draft, draft, (size_t)n_draft * 4, hipMemcpyHostToDevice, st));
     QIE_TRY(launch_verify(b, seq, M, smp));
@@ -2181,15 +2176,6 @@ int qie_batch_dims(const qie_batch* b, int32_t* batch, int32_t* max_ctx) {
 int qie_batch_kv_cache(const qie_batch* b, int32_t seq, qie_kv_cache* out) {
     QIE_REQUIRE(b && out && seq >= 0 && seq < b->B, "qie_batch_kv_cache: bad arguments");
     *out = batch_cache(b, seq);
-    return 0;
-}
-
-int qie_batch_reserve(qie_batch* b, int32_t seq, int32_t n_tokens) {
-    QIE_REQUIRE(b && seq >= 0 && seq < b->B && n_tokens >= 0, "qie_batch_reserve: bad arguments");
-    QIE_REQUIRE(n_tokens <= b->max_ctx, "qie_batch_reserve: %d tokens exceed max_ctx %d", n_tokens, b->max_ctx);
-    QIE_TRY(ensure_pages(b, seq, n_tokens));
-    QIE_TRY(flush_table(b));
-    b->idle[seq] = 0;
     return 0;
 }
 

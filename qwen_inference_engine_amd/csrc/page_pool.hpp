@@ -11,14 +11,16 @@
 // list when the count reaches 0.  Every decision is a function of the call sequence alone, so
 // tensor-parallel ranks making the same calls keep identical tables.
 //
-// All-or-nothing: plan_write() and missing() change nothing; a caller sums what its call would
-// take, compares with free_count(), and only then applies (make_private, grow, ...), none of
-// which can fail afterwards.
+// All-or-nothing: a writer describes its call as spans, plan_reserve() sums what they would take
+// and changes nothing, the caller compares with free_count(), and only then commit() applies
+// them (make_private and grow per span), which cannot fail.
 #pragma once
 #include <cstdint>
 #include <vector>
 
 namespace qie {
+
+constexpr int kMaxBatchSlots = 8;   // the most slots a batch can have: a reservation's capacity
 
 struct PagePool {
     int page_tokens = 0, max_pages = 0, n_pages = 0, n_slots = 0;
@@ -150,6 +152,63 @@ struct PagePool {
             }
         }
         grow(slot, hi >= lo ? hi + 1 : lo);
+    }
+
+    // --- the reservation: what one engine call writes, as at most kMaxBatchSlots spans, planned
+    // as a whole, checked once (need <= free_count()) and then committed, which cannot fail.
+    // A span is positions [lo, hi] of a slot as plan_write takes them.  restart: the slot begins a
+    // new sequence of hi + 1 tokens — it lets go of all its pages first, and the pages only it
+    // holds count towards the check.
+    struct Span {
+        int slot = 0;
+        int64_t lo = 0, hi = -1;
+        bool restart = false;
+    };
+    struct Reservation {
+        int n = 0;
+        int64_t need = 0;   // fresh pages the commit may take beyond what the restart slots return
+        Span spans[kMaxBatchSlots];
+        WritePlan plans[kMaxBatchSlots];
+    };
+    // rows [0, rows) of the slot's page `index` are to be copied from old_page into new_page
+    struct CopyJob {
+        int slot, index, rows;
+        int32_t old_page, new_page;
+    };
+    // Changes nothing.  Every span is planned against the untouched pool, so the total errs on
+    // the safe side in two corners: a page shared only among the restart slots of one call counts
+    // as returned by none of them, and two spans that both plan a private copy of the same shared
+    // page count two pages, although the second finds the page its own at commit.
+    Reservation plan_reserve(const Span* spans, int n) const {
+        Reservation r;
+        r.n = n;
+        for (int i = 0; i < n; i++) {
+            const Span& s = r.spans[i] = spans[i];
+            if (s.restart) {
+                r.plans[i].grow = pages_for(s.hi + 1);   // nothing held once it has let go
+                r.need += r.plans[i].grow - exclusive(s.slot);
+            } else {
+                r.plans[i] = plan_write(s.slot, s.lo, s.hi);
+                r.need += r.plans[i].fresh();
+            }
+        }
+        return r;
+    }
+    // Applies a checked reservation: the restart slots are released in span order, then every span
+    // in order replaces its shared pages and grows.  jobs (kMaxBatchSlots entries) receives at most
+    // one copy per span; returns their number.
+    int commit(const Reservation& r, CopyJob* jobs) {
+        for (int i = 0; i < r.n; i++)
+            if (r.spans[i].restart) release(r.spans[i].slot);
+        int n_jobs = 0;
+        for (int i = 0; i < r.n; i++) {
+            const Span& s = r.spans[i];
+            int32_t was = 0, now = 0;
+            make_private(s.slot, r.plans[i], s.lo, s.hi, &was, &now);
+            // (no new page: another span of this call left the page to this slot alone)
+            if (now) jobs[n_jobs++] = CopyJob{s.slot, r.plans[i].copy_index, r.plans[i].copy_rows, was, now};
+        }
+        return n_jobs;
     }
 };
 

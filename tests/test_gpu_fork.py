@@ -264,6 +264,36 @@ def test_rewind_without_a_page_fails_and_changes_nothing(how):
     assert out[0][:2] == out[1][:2] and np.array_equal(out[0][2], out[1][2])
 
 
+def test_both_holders_rewind_into_one_shared_page():
+    """Fork at 256 with a prefix handle as third holder of the two pages, then source AND fork
+    rewind to 130 and one decode step writes row 130 of both: each ends with a page of its own at
+    index 1 whose rows [128, 130) are the pre-fork rows bit for bit, and the handle's page — the
+    old one — is untouched (a slot loaded from it reads the pre-fork rows [0, 256))."""
+    eng, prompt, b = _forked()
+    pf = b.save_prefix(0, 256)
+    b.fork(0, 2, 256)
+    snap = _rows(b, 0, 256)
+    old = b.block_table(0, 2).tolist()
+    assert b.block_table(2, 2).tolist() == old and b.page_refs()[old].tolist() == [3, 3]
+    free = b.page_stats()[0]
+    b.set_position(0, 130, 5)
+    b.set_position(2, 130, 6)
+    b.decode_step()
+    t0, t2 = b.block_table(0, 2).tolist(), b.block_table(2, 2).tolist()
+    assert t0[0] == t2[0] == old[0] and len({t0[1], t2[1], old[1], 0}) == 4
+    refs = b.page_refs()
+    assert refs[[old[0], old[1], t0[1], t2[1]]].tolist() == [3, 1, 1, 1] and b.page_stats()[0] == free - 2
+    for s in (0, 2):
+        assert _rows_equal(_rows(b, s, 130), [[k[:, :130], v[:, :130]] for k, v in snap]), s
+    r0, r2 = _rows(b, 0, 131), _rows(b, 2, 131)
+    assert not all(np.array_equal(x[0][:, 130], y[0][:, 130]) for x, y in zip(r0, r2)), "row 130: different tokens"
+    b.load_prefix(pf, 1, 7, 256)
+    assert b.block_table(1, 2).tolist() == old
+    assert _rows_equal(_rows(b, 1, 256), snap)
+    pf.drop()
+    b.close()
+
+
 # ------------------------------------------------------------------ 5. a fork that diverges
 @pytest.mark.parametrize("paged", [True, False], ids=["paged", "contig"])
 @pytest.mark.parametrize("name", list(CONFIGS))

@@ -10,7 +10,12 @@ model of the same rules written from DESIGN.md §18:
     holds);
   * a writer of positions [lo, hi] replaces the pages of that range whose count is above 1 by
     fresh ones (ascending), copies rows [0, lo % T) of the page holding lo when that one is
-    replaced, then grows to hi + 1 tokens — all or nothing against the free list.
+    replaced, then grows to hi + 1 tokens — all or nothing against the free list;
+  * a reservation is a list of such writes (spans) taken as a whole: every span is planned against
+    the pool as it stands, the sum of their fresh pages is compared with the free list once, and
+    only then are they applied in order (one copy per span at the most).  A restart reservation
+    gives each of its slots a new sequence of len tokens: it needs the pages of all of them minus
+    the pages only each slot holds, releases all its slots in order, then grows them in order.
 
 The sanitizer build of the same program (make pagepool_check_asan) runs the same script directly."""
 import os
@@ -93,6 +98,30 @@ class Model:
         self.grow(s, hi + 1 if hi >= lo else lo)
         return f"cow {was} {now}"
 
+    def reserve(self, *a):
+        spans = [a[i:i + 3] for i in range(0, len(a), 3)]
+        need = sum(self.plan(*sp)[6] for sp in spans)          # each against the untouched pool
+        if need > len(self.free):
+            return f"fail 28 need {need} free {len(self.free)}"
+        out = f"ok {need}"
+        for s, lo, hi in spans:
+            copy, rows = self.plan(s, lo, hi)[3:5]             # what is shared NOW: an earlier span may have left it
+            was, now = self.write(s, lo, hi).split()[1:]
+            if now != "0":
+                out += f" cow {s} {copy} {rows} {was} {now}"
+        return out
+
+    def restart(self, *a):
+        pairs = [a[i:i + 2] for i in range(0, len(a), 2)]
+        need = sum(self.pages_for(n) for _, n in pairs) - sum(self.exclusive(s) for s, _ in pairs)
+        if need > len(self.free):
+            return f"fail 28 need {need} free {len(self.free)}"
+        for s, _ in pairs:
+            self.release(s)
+        for s, n in pairs:
+            self.grow(s, n)
+        return f"ok {need}"
+
     def dump(self):
         out = [f"slot {s}:" + "".join(f" {p}" for p in r) for s, r in enumerate(self.rows)]
         out.append("refs:" + "".join(f" {c}" for c in self.refs[1:]))
@@ -160,6 +189,44 @@ take
 dump
 drop 1
 dump
+# case A: two spans of one reservation rewind into the same shared page (4 usable pages, 1 free)
+init 3 4 128 5
+grow 0 300
+fork 0 1 256
+reserve 0 130 130 1 130 130
+dump
+reserve 0 130 130
+reserve 1 130 130
+dump
+# ... with 5 usable pages both fit: one copy, the second span finds the page its own, page 5 stays free
+init 3 4 128 6
+grow 0 300
+fork 0 1 256
+reserve 0 130 130 1 130 130
+dump
+# case B: a restart of slots that share only with each other
+init 3 4 128 4
+grow 0 256
+fork 0 1 256
+restart 0 128 1 128
+dump
+restart 0 128
+dump
+# case C: growth and a copy in one span
+init 3 4 128 6
+grow 0 200
+fork 0 1 200
+reserve 1 100 260
+dump
+# several spans in order; a grow-only span
+init 4 4 128 12
+grow 0 300
+fork 0 1 300
+fork 0 2 200
+reserve 2 150 400 1 10 20 0 256 255 3 0 -1
+dump
+restart 1 500 2 1 3 129
+dump
 """
 
 
@@ -223,6 +290,29 @@ def test_page_pool_rejects_bad_operations():
     got = _run("pagepool_check", "grow 0 1\ninit 2 2 128 4\ngrow 5 1\ngrow 0 300\nshare 3\ndrop 0\nfork 0 0 1\n"
                                  "fork 0 1 1\nplan 0 5 2\nrelease 9\n")
     assert got == ["bad", "ok", "bad", "bad", "bad", "bad", "bad", "bad", "bad", "bad"]
+    # reservations: a slot out of range, more spans than a batch has slots, a length beyond
+    # max_pages, an incomplete span, a restart naming a slot twice, a restart of nothing
+    got = _run("pagepool_check", "init 2 2 128 4\nreserve 2 0 0\nrestart 2 10\nreserve" + " 0 0 0" * 9 + "\nrestart" +
+                                 " 0 1" * 9 + "\nrestart 0 257\nreserve 0 0 256\nreserve 0 0\nrestart 0 10 0 10\n"
+                                 "restart 0 0\nreserve\nreserve 0 0 0" + " 1 0 -1" * 7 + "\ndump\n")   # 8 spans: the capacity
+    assert got == ["ok"] + ["bad"] * 10 + ["ok 1", "slot 0: 1", "slot 1:", "refs: 1 0 0", "free: 3 2"]
+
+
+def test_reservations_by_hand():
+    """The lines of cases A, B and C, written out by hand from the single-span operations."""
+    got = _run("pagepool_check", SCRIPT)
+    a = got.index("fail 28 need 2 free 1")
+    assert got[a:a + 12] == ["fail 28 need 2 free 1", "slot 0: 1 2 3", "slot 1: 1 2", "slot 2:", "refs: 2 2 1 0",
+                             "free: 4", "ok 1 cow 0 1 2 2 4", "ok 0", "slot 0: 1 4 3", "slot 1: 1 2", "slot 2:",
+                             "refs: 2 1 1 1"]
+    a6 = got.index("ok 2 cow 0 1 2 2 4")
+    assert got[a6:a6 + 6] == ["ok 2 cow 0 1 2 2 4", "slot 0: 1 4 3", "slot 1: 1 2", "slot 2:", "refs: 2 1 1 1 0",
+                              "free: 5"]
+    b = got.index("fail 28 need 2 free 1", a + 1)
+    assert got[b + 1:b + 6] == ["slot 0: 1 2", "slot 1: 1 2", "slot 2:", "refs: 2 2 0", "free: 3"]
+    assert got[b + 6:b + 12] == ["ok 1", "slot 0: 3", "slot 1: 1 2", "slot 2:", "refs: 1 1 1", "free:"]
+    c = got.index("ok 2 cow 1 0 100 1 4")
+    assert got[c + 1:c + 6] == ["slot 0: 1 2", "slot 1: 4 3 5", "slot 2:", "refs: 1 1 1 1 1", "free:"]
 
 
 def test_page_pool_clean_under_asan_ubsan():

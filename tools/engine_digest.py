@@ -25,7 +25,17 @@ Cases (tests/test_gpu_engine.py's tiny CONFIGS, synthetic weights, fixed seeds):
     log-probabilities and the greedy ids); qie_batch_logprobs;
   * release, then a new prefill of the slot; set_position;
   * the prefill rows growing on one batch: P = 5, 40, 5, then an append;
-  * decode mode 1 (the persistent step), 4 steps."""
+  * decode mode 1 (the persistent step), 4 steps;
+  * paged batches whose slots share pages (3 slots, max_ctx 512, 128-token pages, prompts of about
+    300 ids; after every call the block tables, page counts, free pages and positions, and a hash
+    of the K/V rows where a copy happened): a fork at n == p and at n < p with a partial tail + 2
+    decode steps; the fork rewound by set_position into a shared page + a step; an append at a
+    pos0 inside a shared page; a verify with 7 drafts from a position rewound below the fork
+    point; save_prefix / load_prefix / append of the remainder / drop; prefill_batch over two
+    slots that share pages with each other; source and fork both rewound into the same shared
+    page + a step; in a pool with no free page the refused set_position, append, verify, fork,
+    prefill, prefill_batch, reserve and decode calls (the return code from the exception's text),
+    then a step; reserve on a paged slot."""
 import hashlib
 import json
 import os
@@ -127,6 +137,147 @@ def score_cases(tag, eng, spec, unfused_forms):
         c.rec["greedy"] = [sha(gr), sha(gr2)]
         c.decode(b, 2)
         c.done(b)
+
+
+class PagedCase(Case):
+    """A case on a paged batch of 3 slots (tests/test_gpu_fork.py's: max_ctx 512, 128-token pages):
+    after every call the record gains every slot's block table, the page counts, the free-page
+    count and the positions."""
+
+    def __init__(self, name, eng, n_pages=0):
+        super().__init__(name)
+        self.b = eng.batch(3, 512, page_tokens=128, n_pages=n_pages)
+        self.rec.update(pages=[], rc=[], rows=[])
+
+    def state(self):
+        b = self.b
+        self.rec["pages"].append({"tables": [b.block_table(s, 4).tolist() for s in range(3)],
+                                  "refs": b.page_refs().tolist(), "free": int(b.page_stats()[0]),
+                                  "pos": b.positions().tolist()})
+
+    def call(self, fn, *a, **kw):
+        """A call that returns nothing to hash (fork, set_position, reserve, ...)."""
+        out = fn(*a, **kw)
+        self.state()
+        return out
+
+    def tok(self, fn, *a, rows=None, **kw):
+        """A call that returns ids and writes logits (prefill, append, prefill_batch)."""
+        self.took(fn(*a, **kw), self.b, rows)
+        self.state()
+
+    def step(self, n=1, rows=None):
+        for _ in range(n):
+            self.decode(self.b, 1, rows=rows)
+            self.state()
+
+    def refused(self, fn, *a, **kw):
+        """A call the pool must refuse: the return code, from the exception's text."""
+        try:
+            fn(*a, **kw)
+            self.rec["rc"].append(0)
+        except Q._lib.QieError as e:
+            self.rec["rc"].append(int(str(e).split("rc=")[1].split(")")[0]))
+        self.state()
+
+    def kv(self, seq, n):
+        """K/V rows [0, n) of a slot, every layer: where a copy happened."""
+        self.rec["rows"].append(sha(np.concatenate([np.stack(self.b.kv_rows(seq, l, n)).ravel()
+                                                    for l in range(self.b.e.spec.n_layers)])))
+
+    def done(self):
+        super().done(self.b)
+
+
+def paged_cases(eng, spec):
+    """Forks, copy-on-write and prefix handles: every writer's reservation on shared pages."""
+    prompt = ids(spec, 101, 297)
+
+    def forked(name, n_pages=0, at=None):
+        """Slot 0 at position 300 (prefill of 297 + 3 steps), forked into slot 2."""
+        c = PagedCase(name, eng, n_pages)
+        c.tok(c.b.prefill, 0, prompt, rows=slice(0, 1))
+        c.step(3, rows=slice(0, 1))
+        c.call(c.b.fork, 0, 2, at)
+        return c
+
+    for at in (None, 200):   # n == p, and n < p with a partial tail
+        c = forked(f"paged_fork_at_{at or 'p'}", at=at)
+        c.kv(2, at or 300)
+        c.step(2)
+        c.done()
+    c = forked("paged_fork_rewound_set_position")
+    c.call(c.b.set_position, 2, 200, 5)
+    c.kv(2, 200)
+    c.step()
+    c.done()
+    c = forked("paged_append_into_shared_page")
+    c.tok(c.b.append, 2, ids(spec, 102, 20), 130, rows=slice(2, 3))
+    c.kv(2, 150)
+    c.kv(0, 300)
+    c.step()
+    c.done()
+    c = forked("paged_verify_below_fork_point")
+    c.call(c.b.set_position, 2, 125, 5)                         # page 0 private; rows 125..132 reach shared page 1
+    c.kv(2, 125)
+    c.verify(c.b, 2, ids(spec, 103, 7), Q.GREEDY)
+    c.state()
+    c.step()
+    c.done()
+    c = forked("paged_prefix_save_load_append_drop")
+    hist = c.b.history(0, 300).tolist()
+    pf = c.call(c.b.save_prefix, 0, 256)
+    c.call(c.b.release, 0)
+    c.call(c.b.load_prefix, pf, 1, hist[128], 128)
+    c.tok(c.b.append, 1, hist[128:300] + ids(spec, 104, 17), 128, rows=slice(1, 2))
+    c.kv(1, 317)
+    c.call(pf.drop)
+    c.step()
+    c.done()
+    # slots 1 and 2 share two pages with each other (and with slot 0), then both start new prompts;
+    # in a full pool the same call is refused (the shared pages count as returned by neither)
+    for n_pages in (0, 5):
+        c = forked(f"paged_prefill_batch_over_sharing_slots_{n_pages or 'roomy'}", n_pages)
+        c.call(c.b.fork, 0, 1, 256)
+        if n_pages:
+            c.refused(c.b.prefill_batch, 1, [ids(spec, 108, 200), ids(spec, 109, 200)])
+            c.refused(c.b.decode_step)                          # slot 1 at 256 needs a third page
+        else:
+            c.tok(c.b.prefill_batch, 1, [ids(spec, 108, 200), ids(spec, 109, 200)], rows=slice(1, 3))
+            c.step(2)
+        c.kv(0, 300)
+        c.done()
+    c = forked("paged_both_rewound_into_one_page", at=256)
+    c.call(c.b.set_position, 0, 130, 5)
+    c.call(c.b.set_position, 2, 130, 6)
+    c.step()
+    c.kv(0, 131)
+    c.kv(2, 131)
+    c.done()
+    # a pool with no free page (scratch + 3 for the source + the fork's tail page): every refusal,
+    # then a decode step
+    c = forked("paged_refusals_in_a_full_pool", n_pages=5)
+    c.refused(c.b.set_position, 2, 200, 5)
+    c.refused(c.b.append, 2, ids(spec, 110, 20), 130)
+    tok300 = int(c.b.history(0, 301)[300])
+    c.call(c.b.set_position, 0, 380, 5)                         # within slot 0's own third page
+    c.refused(c.b.verify, 0, ids(spec, 111, 7))                 # rows 380..387 need a fourth
+    c.call(c.b.set_position, 0, 300, tok300)
+    c.refused(c.b.fork, 0, 1, 300)
+    c.refused(c.b.prefill, 1, ids(spec, 112, 10))
+    c.refused(c.b.prefill_batch, 1, [ids(spec, 113, 140), ids(spec, 114, 140)])
+    c.refused(c.b.reserve, 1, 10)
+    c.refused(c.b.set_position, 1, 10, 5)
+    c.refused(c.b.decode, 100)
+    c.step()
+    c.done()
+    c = PagedCase("paged_reserve", eng)
+    c.call(c.b.reserve, 1, 300)
+    c.tok(c.b.prefill, 0, ids(spec, 115, 40), rows=slice(0, 1))
+    c.call(c.b.reserve, 0, 129)
+    c.call(c.b.reserve, 1, 100)
+    c.step()
+    c.done()
 
 
 def main():
@@ -239,6 +390,10 @@ def main():
     c.took(b.append(0, ids(spec, 85, 50), 5), b)
     c.decode(b, 2)
     c.done(b)
+    eng.close()
+    # paged batches whose slots share pages (tests/test_gpu_fork.py's model and geometry)
+    eng = Q.Engine(spec, max_ctx=512).init_synthetic(SYN)
+    paged_cases(eng, spec)
     eng.close()
     # decode mode 1: the persistent step (tests/test_gpu_persist.py's qk-norm model)
     eng = Q.Engine(PERSIST, max_ctx=64).init_synthetic(SYN)

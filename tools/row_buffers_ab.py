@@ -9,6 +9,9 @@ bf16, synthetic weights.  One JSON line:
   verify_ms    one qie_verify with 7 drafts at position about 2,048 (captured step)
   step_us      graph decode step, 64 steps per sample
 
+--page-tokens T measures the same figures on paged batches (pages of T tokens): the page pool's
+reservation is then on every call's host path.
+
 Host clock around calls that end in a stream synchronise; per figure the median of its calls after
 warm-up calls (tools/score_bench.py's method)."""
 import argparse
@@ -42,15 +45,17 @@ def ms(eng, fn, n, warm):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--layers", type=int, default=None, help="fewer layers than Qwen2-7B's 28 (rehearsal)")
+    ap.add_argument("--page-tokens", type=int, default=None,
+                    help="every batch paged with pages of this many tokens (default: contiguous)")
     args = ap.parse_args()
     spec = S.QWEN2_7B if args.layers is None else S.QWEN2_7B.replace(n_layers=args.layers)
     eng = Q.Engine(spec, max_ctx=MAX_CTX).init_synthetic(W.SynthParams(seed=0))
-    r = {"lib": os.environ.get("QIE_LIB", "default")}
+    r = {"lib": os.environ.get("QIE_LIB", "default"), "page_tokens": args.page_tokens}
     made = []
-    r["create_ms"] = ms(eng, lambda: made.append(eng.batch(8, MAX_CTX)), 5, 1)
+    r["create_ms"] = ms(eng, lambda: made.append(eng.batch(8, MAX_CTX, page_tokens=args.page_tokens)), 5, 1)
     for b in made:
         b.close()
-    b = eng.batch(1, MAX_CTX)
+    b = eng.batch(1, MAX_CTX, page_tokens=args.page_tokens)
     ids = [int(t) for t in np.random.default_rng(3).integers(0, spec.vocab, N)]
     r["prefill_ms"] = ms(eng, lambda: b.prefill(0, ids), 7, 2)
     r["score_ms"] = ms(eng, lambda: b.score_rows(0, ids, ids[1:] + [-1]), 5, 2)
