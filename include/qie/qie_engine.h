@@ -291,6 +291,37 @@ int qie_batch_set_position(qie_batch* b, int32_t seq, int32_t pos, int32_t token
  * collective under tensor parallelism (every rank decides alike). */
 typedef struct qie_kv_prefix qie_kv_prefix;
 int qie_batch_fork(qie_batch* b, int32_t src, int32_t dst, int32_t n_tokens, int32_t step_offset);
+
+/* ------------------------------------------------------- per-slot sampling
+ * Every slot may hold its own sampling entry (qie_slot_sampling, qie_types.h; the numerics
+ * contract is stated at qie_sample_rows in qie_ops.h): top-k / temperature /
+ * top-p / min-p / seed, repetition, presence and frequency penalties over a window of the slot's
+ * own token history, and a logit bias list.  set: slot seq's entry := *p, NULL clears it.  -22
+ * with nothing changed for seq out of range, n_bias outside [0, QIE_SLOT_BIAS_MAX], a bias id
+ * outside [0, vocab) or listed twice, a bias that is NaN or +inf, a non-finite temperature or
+ * penalty, repetition_penalty <= 0, min_p outside [0, 1], a negative penalty_start or
+ * penalty_last_n.  get: the entry (zeroes without one) and whether one is set.
+ *
+ * An entry belongs to the slot until it is replaced or cleared: qie_batch_release, qie_prefill
+ * and qie_batch_prefix_load leave it alone; qie_batch_fork gives dst what src has (its entry, or
+ * none), so a decode step still produces in dst exactly what it produces in src, and
+ * step_offset still moves the draw.  Every call that samples honours it — qie_prefill, _batch,
+ * _append, qie_score (its sampled last row), qie_decode_step, qie_decode, qie_verify,
+ * qie_batch_debug_step: a row whose slot has an entry samples under it (window end q: the
+ * position of the row's input token; verify row i sees the history up to the pending token and
+ * the drafts d1 .. di, exactly what a decode step there would see); a row whose slot has none
+ * uses the call's qie_sampling.  When no row of a launch has an entry the launches are exactly
+ * those of a batch that never had one.
+ *
+ * The entries live in a device table made at the first set (one fixed allocation, with the
+ * sampler's own workspace beside it); a set is a copy ordered on the engine's stream.  The
+ * captured decode graph and captured verify steps READ the table: changing an entry's values
+ * never re-captures; "some slot has an entry" flipping does, as a change of the call's
+ * qie_sampling does.  Tensor parallelism / comm_always: rows of a launch with an entry take the
+ * gathered-row path of the sampled head, every rank samples the same full row — the caller
+ * sets the same entries on every rank. */
+int qie_batch_set_slot_sampling(qie_batch* b, int32_t seq, const qie_slot_sampling* p);
+int qie_batch_slot_sampling(const qie_batch* b, int32_t seq, qie_slot_sampling* out, int32_t* is_set);
 /* Paged batches: the holder count of pool pages 0 .. n-1 (host; 0 = free; page 0, the scratch
  * page, is always 0). */
 int qie_batch_page_refs(qie_batch* b, int32_t* host_refs, int32_t n);

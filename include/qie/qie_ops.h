@@ -256,6 +256,58 @@ int qie_sample(const void* logits, int64_t M, int64_t V, int64_t ld, const qie_s
 /* Decode fused arg-max keys (see qie_linear_args.argmax_keys) into ids. */
 int qie_keys_to_ids(const uint64_t* keys, int64_t M, int32_t* out_ids, void* stream);
 
+/* ------------------------------------------------- per-row sampling entries
+ * qie_sample_rows: every one of the M bf16 logit rows [M][ld] is processed and sampled under
+ * its OWN entry of a device table (qie_slot_sampling, qie_types.h).  The
+ * reference has no such path (one host-side parameter set, logit_decode.cu:149-274).
+ *
+ * Numerics contract.  A row l[0..V) has an entry e and a window W, a multiset of token ids with
+ * c[j] the count of j in W.  The processed row l' is computed in fp32 with IEEE operations, every
+ * step rounded, no FMA contraction, plain division:
+ *     v = f32(l[j])
+ *     if c[j] > 0:
+ *         v = (v > 0) ? v / e.repetition_penalty : v * e.repetition_penalty   (skipped when == 1)
+ *         t = e.frequency_penalty * (float)c[j];  t = e.presence_penalty + t;  v = v - t
+ *     if j is in the bias list:  v = v + bias                                  (-inf bans j)
+ *     l'[j] = bf16_rne(v)            (an element with c[j] == 0 and no bias keeps its bits)
+ * Rounding back to bf16 makes everything after it what qie_sample does on a bf16 row:
+ *   greedy (top_k <= 1 or !(temperature > 0)): the maximum selection key (the reference tie rule);
+ *   sampled: the min(top_k, 256, V) largest keys in descending order, v_i = l'_i / T, m = max,
+ *     w_i = expf(v_i - m); min_p in (0, 1]: the leading entries with w_i >= min_p stay (entry 0
+ *     always); then top_p and the one XORWOW draw from seed + step exactly as qie_sample.
+ * A row with no selectable element (NaN / -inf only) yields -1.
+ * Window of row m: the ids at positions [lo, q] of its slot's history row, q = q_dev[m],
+ *     lo = max(e.penalty_start, e.penalty_last_n > 0 ? q + 1 - e.penalty_last_n : 0, 0);
+ * with a tail (tail_len_dev[m] = n > 0) the positions (q - n, q] hold tail_dev[0 .. n) instead
+ * of the history's words (a verify row's drafts).  Positions at or past hist_stride are not read,
+ * ids outside [0, V) are ignored, so an arbitrary history never indexes out of range.  With the
+ * three penalties neutral the window is not walked.
+ *
+ * Row m reads table[slot0 + m * slot_stride] and history row slot0 + m * slot_stride (decode:
+ * stride 1; a verify step: stride 0, one slot for all rows).  An entry with n_bias < 0 stands
+ * for "none": the row runs a neutral entry with the four values of `fallback` (host; may be
+ * NULL = greedy).  step_dev as in qie_sample.  ws holds qie_sample_rows_workspace_bytes(M, V)
+ * bytes; V <= 64 * 4096.  No float atomics (integer LDS counts): two runs are bit-identical.
+ * Neither allocates nor synchronises; graph-capturable, and every entry value is read from the
+ * table at run time. */
+typedef struct qie_sample_rows_args {
+    const void* logits;                   /* device bf16 [M][ld] */
+    int64_t M, V, ld;
+    const qie_slot_sampling* table;       /* device */
+    int32_t slot0, slot_stride;
+    const qie_sampling* fallback;         /* host, or NULL */
+    const int32_t* hist;                  /* device [slots][hist_stride] */
+    int64_t hist_stride;
+    const int32_t* q_dev;                 /* device [M] */
+    const int32_t* tail_dev;              /* device, or NULL */
+    const int32_t* tail_len_dev;          /* device [M], or NULL */
+    const int32_t* step_dev;              /* device [M], or NULL */
+    int32_t* out_ids;                     /* device [M] */
+    void* ws;
+} qie_sample_rows_args;
+int64_t qie_sample_rows_workspace_bytes(int64_t M, int64_t V);
+int qie_sample_rows(const qie_sample_rows_args* a, void* stream);
+
 /* ----------------------------------------------------------------- scoring
  * Per-token log-probabilities of the vocabulary head (the reference has no such path: its head,
  * qwen_main.cu:224-241, samples one token from the last row).  Numerics contract (DESIGN.md

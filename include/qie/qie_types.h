@@ -94,6 +94,33 @@ typedef struct qie_sampling {
     uint64_t seed;           /* reference: prefill 1234, decode 1234 + step      */
 } qie_sampling;
 
+/* Per-slot sampling entry (qie_batch_set_slot_sampling, qie_sample_rows; the numerics contract
+ * is stated at qie_sample_rows in qie_ops.h).  top_k / temperature / top_p / seed as in
+ * qie_sampling.  min_p in (0, 1] keeps the candidates whose softmax weight relative to the
+ * best one is at least min_p; 0 = off.  The penalties look at the ids of the slot's own history
+ * in a window [lo, q], q the position of the row's input token and
+ *     lo = max(penalty_start, penalty_last_n > 0 ? q + 1 - penalty_last_n : 0):
+ * penalty_start = the prompt's length penalises generated tokens only, penalty_last_n is a
+ * sliding window.  bias_ids / bias: n_bias distinct token ids whose logit gets bias[i] added
+ * (-inf bans the token).  In a DEVICE table n_bias < 0 marks a slot without an entry (its rows
+ * use the call's qie_sampling); the engine tier never accepts such an entry from a caller. */
+#define QIE_SLOT_BIAS_MAX 32
+typedef struct qie_slot_sampling {
+    int32_t top_k;
+    float temperature;
+    float top_p;
+    float min_p;
+    uint64_t seed;
+    float repetition_penalty;   /* 1 = off: v > 0 ? v / r : v * r for every id in the window   */
+    float presence_penalty;     /* 0 = off: subtracted once for an id in the window            */
+    float frequency_penalty;    /* 0 = off: subtracted once per occurrence in the window       */
+    int32_t penalty_start;
+    int32_t penalty_last_n;     /* 0 = no limit */
+    int32_t n_bias;
+    int32_t bias_ids[QIE_SLOT_BIAS_MAX];
+    float bias[QIE_SLOT_BIAS_MAX];
+} qie_slot_sampling;
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,7 @@ thin Python layer.  See DESIGN.md.
 """
 from .spec import ModelSpec, PRESETS, QWEN2_0_5B, QWEN2_7B, QWEN2_72B, QWEN3_14B, tiny  # noqa: F401
 from .weights import HostWeights, SynthParams, synthetic_index, parse_meta, format_meta  # noqa: F401
-from .engine import Engine, Batch, Prefix, Comm, Sampling, GREEDY  # noqa: F401
+from .engine import Engine, Batch, Prefix, Comm, Sampling, SlotSampling, GREEDY  # noqa: F401
 from .speculative import NgramDrafter, ModelDrafter, SpeculativeDecoder  # noqa: F401
 
 __version__ = "0.1.0"

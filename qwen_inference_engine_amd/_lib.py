@@ -59,6 +59,25 @@ class SamplingC(C.Structure):
                 ("seed", C.c_uint64)]
 
 
+QIE_SLOT_BIAS_MAX = 32
+
+
+class SlotSamplingC(C.Structure):
+    _fields_ = [("top_k", C.c_int32), ("temperature", C.c_float), ("top_p", C.c_float), ("min_p", C.c_float),
+                ("seed", C.c_uint64), ("repetition_penalty", C.c_float), ("presence_penalty", C.c_float),
+                ("frequency_penalty", C.c_float), ("penalty_start", C.c_int32), ("penalty_last_n", C.c_int32),
+                ("n_bias", C.c_int32), ("bias_ids", C.c_int32 * QIE_SLOT_BIAS_MAX),
+                ("bias", C.c_float * QIE_SLOT_BIAS_MAX)]
+
+
+class SampleRowsArgsC(C.Structure):
+    _fields_ = [("logits", C.c_void_p), ("M", C.c_int64), ("V", C.c_int64), ("ld", C.c_int64),
+                ("table", C.c_void_p), ("slot0", C.c_int32), ("slot_stride", C.c_int32),
+                ("fallback", C.POINTER(SamplingC)), ("hist", C.c_void_p), ("hist_stride", C.c_int64),
+                ("q_dev", C.c_void_p), ("tail_dev", C.c_void_p), ("tail_len_dev", C.c_void_p),
+                ("step_dev", C.c_void_p), ("out_ids", C.c_void_p), ("ws", C.c_void_p)]
+
+
 class LinearArgsC(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("ldx", C.c_int64), ("w", C.c_void_p * 3), ("bias", C.c_void_p * 3),
@@ -135,6 +154,8 @@ SIGNATURES = [
     ("qie_sample_workspace_bytes", C.c_int64, [_I64, _I64]),
     ("qie_sample", C.c_int, [_P, _I64, _I64, _I64, C.POINTER(SamplingC), _P, _P, _P, _P]),
     ("qie_keys_to_ids", C.c_int, [_P, _I64, _P, _P]),
+    ("qie_sample_rows_workspace_bytes", C.c_int64, [_I64, _I64]),
+    ("qie_sample_rows", C.c_int, [C.POINTER(SampleRowsArgsC), _P]),
     ("qie_logprob_rows", C.c_int, [_P, _I64, _I64, _I64, _P, _P, _P, _P]),
     ("qie_score_rows_workspace_bytes", C.c_int64, [_I64, _I64]),
     ("qie_score_rows", C.c_int, [_P, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
@@ -202,6 +223,8 @@ SIGNATURES = [
     ("qie_batch_history", C.c_int, [_P, _I32, _PI32, _I32]),
     ("qie_batch_set_position", C.c_int, [_P, _I32, _I32, _I32]),
     ("qie_batch_fork", C.c_int, [_P, _I32, _I32, _I32, _I32]),
+    ("qie_batch_set_slot_sampling", C.c_int, [_P, _I32, C.POINTER(SlotSamplingC)]),
+    ("qie_batch_slot_sampling", C.c_int, [_P, _I32, C.POINTER(SlotSamplingC), _PI32]),
     ("qie_batch_page_refs", C.c_int, [_P, _PI32, _I32]),
     ("qie_batch_prefix_save", C.c_int, [_P, _I32, _I32, C.POINTER(_P)]),
     ("qie_batch_prefix_load", C.c_int, [_P, _P, _I32, _I32, _I32]),

@@ -24,6 +24,7 @@
 #include "page_pool.hpp"
 
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <fstream>
 #include <functional>
@@ -193,6 +194,7 @@ struct qie_batch {
     VerifyRows v;
     struct VerifyGraph {
         int seq, M;
+        bool entries;   // the slot held an entry: the call's sampling is not part of the step
         bool greedy;
         qie_sampling smp;
         hipGraphExec_t exec;
@@ -203,6 +205,17 @@ struct qie_batch {
     // greedy ids of sc.rows rows, and the fused head's workspace; grown before any launch
     ScoreRows sc;
     DevBlock sc_ws;
+    // per-slot sampling entries (qie_batch_set_slot_sampling): the host copies, and
+    // from the first set on the device table [B] (n_bias < 0: no entry) followed by the verify
+    // rows' tail lengths 0 .. kVerifyMaxRows - 1, and qie_sample_rows' own workspace.  Both are
+    // made once and never reallocated: captured steps hold their pointers.
+    std::vector<qie_slot_sampling> slot_h;
+    std::vector<char> slot_set;
+    int n_slot_set = 0;
+    qie_slot_sampling* d_slots = nullptr;
+    int32_t* d_tail_len = nullptr;
+    void* rows_ws = nullptr;
+    bool g_entries = false;   // the decode graph was captured on the entry path
 };
 
 namespace qie {
@@ -765,14 +778,30 @@ static qie_linear_args head_args(const qie_engine* e, const uint16_t* x, int64_t
     return a;
 }
 
+// The rows of a head launch that sample under per-slot entries: row m belongs to slot
+// slot0 + m * slot_stride and its input token sits at position q[m]; a verify step's rows carry
+// the drafts as a tail (tail_len[m] = m).
+struct EntryRows {
+    int slot0, slot_stride;
+    const int32_t *q, *tail, *tail_len;
+};
+// does a slot of [m0, m0 + M) hold an entry?
+static bool any_entry(const qie_batch* b, int m0, int M) {
+    if (b->n_slot_set == 0) return false;
+    for (int m = m0; m < m0 + M; m++)
+        if (b->slot_set[m]) return true;
+    return false;
+}
+
 // lm_head over M rows of x (already the residual stream), then the sampler; leaves the
-// choices in hb.keys (greedy) or hb.ids.
+// choices in hb.keys (greedy without entries) or hb.ids.  er: the rows sample through
+// qie_sample_rows (smp is what rows without an entry use); null: the fused keys / qie_sample.
 static int enqueue_head_rows(qie_batch* b, const uint16_t* x, int64_t ldx, int M, const qie_sampling* smp,
-                             const HeadBufs& hb) {
+                             const HeadBufs& hb, const EntryRows* er = nullptr) {
     qie_engine* e = b->e;
     const qie_model_spec& s = e->spec;
     hipStream_t st = e->stream;
-    const bool greedy = is_greedy(smp);
+    const bool greedy = !er && is_greedy(smp);
     qie_linear_args a = head_args(e, x, ldx, M, greedy, hb);
     QIE_TRY(prenorm(b, a, hb.xn));
     QIE_TRY(linear(&a, LinearExtras{}, st));
@@ -783,7 +812,18 @@ static int enqueue_head_rows(qie_batch* b, const uint16_t* x, int64_t ldx, int M
             QIE_TRY(gather_rows(b, hb, M));
             lg = hb.logits_full + (int64_t)hb.full_row0 * s.vocab;
         }
-        QIE_TRY(qie_sample(lg, M, s.vocab, s.vocab, smp, hb.step, hb.ids, hb.samp_ws, st));
+        if (er) {
+            qie_sample_rows_args ra{};
+            ra.logits = lg, ra.M = M, ra.V = s.vocab, ra.ld = s.vocab;
+            ra.table = b->d_slots, ra.slot0 = er->slot0, ra.slot_stride = er->slot_stride;
+            ra.fallback = smp;
+            ra.hist = b->dec.hist, ra.hist_stride = b->max_ctx;
+            ra.q_dev = er->q, ra.tail_dev = er->tail, ra.tail_len_dev = er->tail_len;
+            ra.step_dev = hb.step, ra.out_ids = hb.ids, ra.ws = b->rows_ws;
+            QIE_TRY(qie_sample_rows(&ra, st));
+        } else {
+            QIE_TRY(qie_sample(lg, M, s.vocab, s.vocab, smp, hb.step, hb.ids, hb.samp_ws, st));
+        }
     }
     return 0;
 }
@@ -793,8 +833,11 @@ static int enqueue_head(qie_batch* b, const uint16_t* x, int64_t ldx, int m0, in
     qie_engine* e = b->e;
     const qie_model_spec& s = e->spec;
     hipStream_t st = e->stream;
-    QIE_TRY(enqueue_head_rows(b, x, ldx, M, smp, head_bufs(b->dec, m0, b->e->sh.vocab)));
-    const bool greedy = is_greedy(smp);
+    // a slot's position is its pending token's: the window's last position
+    const EntryRows er{m0, 1, b->dec.pos + m0, nullptr, nullptr};
+    const bool entries = any_entry(b, m0, M);
+    QIE_TRY(enqueue_head_rows(b, x, ldx, M, smp, head_bufs(b->dec, m0, b->e->sh.vocab), entries ? &er : nullptr));
+    const bool greedy = !entries && is_greedy(smp);
     hipLaunchKernelGGL(finalize_kernel, dim3(M), dim3(256), 0, st, m0, greedy ? b->dec.keys : nullptr,
                        b->dec.ids, b->dec.ids, b->dec.pos, b->dec.step, b->dec.hist, b->max_ctx,
                        (const uint4*)e->w.embed, (uint4*)b->dec.x, (int64_t)s.hidden / 8, s.vocab, rope_cur_args(b),
@@ -1412,6 +1455,89 @@ int qie_batch_set_position(qie_batch* b, int32_t seq, int32_t pos, int32_t token
 // --- forks and prefix handles: they share pages (a fork draws at most its tail page, after its
 // own check) and write no rows, so they use the pool directly
 
+// ------------------------------------------------------------ per-slot sampling
+static qie_slot_sampling no_entry() {
+    qie_slot_sampling z{};
+    z.n_bias = -1;
+    z.repetition_penalty = 1.f;
+    return z;
+}
+
+// The device table and the sampler's workspace, at the first set: fixed for the batch's lifetime
+static int ensure_slot_table(qie_batch* b) {
+    if (b->d_slots) return 0;
+    qie_engine* e = b->e;
+    const size_t tb = (size_t)b->B * sizeof(qie_slot_sampling);
+    void *tab = nullptr, *ws = nullptr;
+    if (dmalloc(&tab, tb + kVerifyMaxRows * 4) ||
+        dmalloc(&ws, (size_t)qie_sample_rows_workspace_bytes(std::max(b->B, kVerifyMaxRows), e->spec.vocab))) {
+        hipFree(tab);
+        return fail(-2, "qie_batch_set_slot_sampling: device allocation failed: %s", qie_last_error());
+    }
+    std::vector<qie_slot_sampling> none(b->B, no_entry());
+    int32_t iota[kVerifyMaxRows];
+    for (int i = 0; i < kVerifyMaxRows; i++) iota[i] = i;
+    hipError_t he = hipMemcpyAsync(tab, none.data(), tb, hipMemcpyHostToDevice, e->stream);
+    if (he == hipSuccess) he = hipMemcpyAsync((char*)tab + tb, iota, sizeof(iota), hipMemcpyHostToDevice, e->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);   // the host sources go out of scope
+    if (he != hipSuccess) {
+        hipFree(tab);
+        hipFree(ws);
+        return fail((int)he, "qie_batch_set_slot_sampling: table init: %s", hipGetErrorString(he));
+    }
+    b->d_slots = (qie_slot_sampling*)tab;
+    b->d_tail_len = (int32_t*)((char*)tab + tb);
+    b->rows_ws = ws;
+    return 0;
+}
+
+// Slot seq's entry := *p (null: none), host copy and device table; the copy is ordered on the
+// engine's stream behind the steps already enqueued, outside any graph.  Already validated.
+static int write_slot_entry(qie_batch* b, int seq, const qie_slot_sampling* p) {
+    if (!p && !b->d_slots) return 0;
+    QIE_TRY(ensure_slot_table(b));
+    const qie_slot_sampling v = p ? *p : no_entry();
+    QIE_HIP(hipMemcpyAsync(b->d_slots + seq, &v, sizeof(v), hipMemcpyHostToDevice, b->e->stream));
+    QIE_HIP(hipStreamSynchronize(b->e->stream));   // `v` goes out of scope
+    b->n_slot_set += (p ? 1 : 0) - (b->slot_set[seq] ? 1 : 0);
+    b->slot_set[seq] = p ? 1 : 0;
+    b->slot_h[seq] = p ? *p : qie_slot_sampling{};
+    return 0;
+}
+
+int qie_batch_set_slot_sampling(qie_batch* b, int32_t seq, const qie_slot_sampling* p) {
+    QIE_REQUIRE(b && seq >= 0 && seq < b->B, "qie_batch_set_slot_sampling: bad arguments");
+    if (p) {
+        const int64_t V = b->e->spec.vocab;
+        QIE_REQUIRE(p->n_bias >= 0 && p->n_bias <= QIE_SLOT_BIAS_MAX, "qie_batch_set_slot_sampling: n_bias %d outside [0, %d]",
+                    p->n_bias, QIE_SLOT_BIAS_MAX);
+        for (int i = 0; i < p->n_bias; i++) {
+            QIE_REQUIRE(p->bias_ids[i] >= 0 && p->bias_ids[i] < V, "qie_batch_set_slot_sampling: bias id %d out of range",
+                        p->bias_ids[i]);
+            for (int j = 0; j < i; j++)
+                QIE_REQUIRE(p->bias_ids[j] != p->bias_ids[i], "qie_batch_set_slot_sampling: bias id %d listed twice",
+                            p->bias_ids[i]);
+            QIE_REQUIRE(p->bias[i] == p->bias[i] && p->bias[i] != INFINITY,
+                        "qie_batch_set_slot_sampling: the bias of id %d is NaN or +inf", p->bias_ids[i]);
+        }
+        QIE_REQUIRE(std::isfinite(p->temperature) && std::isfinite(p->repetition_penalty) &&
+                        std::isfinite(p->presence_penalty) && std::isfinite(p->frequency_penalty),
+                    "qie_batch_set_slot_sampling: temperature and penalties must be finite");
+        QIE_REQUIRE(p->repetition_penalty > 0.f, "qie_batch_set_slot_sampling: repetition_penalty must be > 0 (1 = off)");
+        QIE_REQUIRE(p->min_p >= 0.f && p->min_p <= 1.f, "qie_batch_set_slot_sampling: min_p outside [0, 1]");
+        QIE_REQUIRE(p->penalty_start >= 0 && p->penalty_last_n >= 0,
+                    "qie_batch_set_slot_sampling: penalty_start and penalty_last_n must be >= 0");
+    }
+    return write_slot_entry(b, seq, p);
+}
+
+int qie_batch_slot_sampling(const qie_batch* b, int32_t seq, qie_slot_sampling* out, int32_t* is_set) {
+    QIE_REQUIRE(b && seq >= 0 && seq < b->B && (out || is_set), "qie_batch_slot_sampling: bad arguments");
+    if (out) *out = b->slot_h[seq];
+    if (is_set) *is_set = b->slot_set[seq];
+    return 0;
+}
+
 int qie_batch_fork(qie_batch* b, int32_t src, int32_t dst, int32_t n_tokens, int32_t step_offset) {
     QIE_REQUIRE(b && src >= 0 && src < b->B && dst >= 0 && dst < b->B && src != dst,
                 "qie_batch_fork: bad arguments (two different slots of the batch)");
@@ -1448,7 +1574,10 @@ int qie_batch_fork(qie_batch* b, int32_t src, int32_t dst, int32_t n_tokens, int
     if (n == p)   // the pending token's logits: row dst of qie_batch_logits equals row src
         QIE_HIP(hipMemcpyAsync(b->dec.logits + (int64_t)dst * e->sh.vocab, b->dec.logits + (int64_t)src * e->sh.vocab,
                                (size_t)e->sh.vocab * 2, hipMemcpyDeviceToDevice, st));
-    return start_slot(b, dst, n, tok_step[1] + step_offset, tok);
+    QIE_TRY(start_slot(b, dst, n, tok_step[1] + step_offset, tok));
+    // dst samples as src does: src's entry, or none
+    if (b->slot_set[src] || b->slot_set[dst]) QIE_TRY(write_slot_entry(b, dst, b->slot_set[src] ? &b->slot_h[src] : nullptr));
+    return 0;
 }
 
 int qie_batch_page_refs(qie_batch* b, int32_t* host_refs, int32_t n) {
@@ -1552,6 +1681,8 @@ static int batch_create(qie_engine* e, int32_t batch, int32_t max_ctx, int32_t p
     // and are rewound before they would pass max_ctx (prepare_steps).
     b->idle.assign(batch, 1);
     b->h_pos.assign(batch, 0);
+    b->slot_h.assign(batch, qie_slot_sampling{});
+    b->slot_set.assign(batch, 0);
     // the KV pools, the block table, and the slots' rows: one block, zero but for the RoPE rows'
     // tags (-1: no position).  Never reallocated: the decode graph and the persistent step's
     // attention table hold pointers into it.
@@ -1608,7 +1739,7 @@ void qie_batch_destroy(qie_batch* b) {
     free_rows(b->v);
     free_rows(b->sc);
     for (void* p : {(void*)b->kc, (void*)b->vc, (void*)b->d_table, b->pk_mem, (void*)b->d_layers, b->d_attp,
-                    (void*)b->pk_ts})
+                    (void*)b->pk_ts, (void*)b->d_slots, b->rows_ws})
         if (p) hipFree(p);
     // (the DevBlock workspaces free themselves)
     for (qie_kv_prefix* p : b->prefixes) delete p;   // handles still open: their pages go with the pool
@@ -1872,12 +2003,14 @@ static int capture_graph(qie_engine* e, const char* who, const std::function<int
 static int launch_step(qie_batch* b, const qie_sampling* smp) {
     qie_engine* e = b->e;
     if (!e->opts.use_graph) return enqueue_decode(b, smp);
-    if (!b->graph_ok || !same_sampling(b->gs, smp)) {
+    // (entry VALUES are read from the device table: only "some slot has an entry" is captured)
+    if (!b->graph_ok || !same_sampling(b->gs, smp) || b->g_entries != (b->n_slot_set > 0)) {
         if (b->gexec) hipGraphExecDestroy(b->gexec);
         b->gexec = nullptr;
         b->graph_ok = false;
         QIE_TRY(capture_graph(e, "", [&] { return enqueue_decode(b, smp); }, &b->gexec));
         b->gs = smp ? *smp : qie_sampling{1, 0.f, 1.f, 0};
+        b->g_entries = b->n_slot_set > 0;
         b->graph_ok = true;
     }
     QIE_HIP(hipGraphLaunch(b->gexec, e->stream));
@@ -2009,8 +2142,11 @@ static int enqueue_verify(qie_batch* b, int seq, int M, const qie_sampling* smp)
     const LayerRows r = layer_rows(b->v, M, M);
     for (int l = 0; l < s.n_layers; l++)
         QIE_TRY(enqueue_layer_rows(b, l, r, decode_path(e), cache, qie_attention_extend, b->v.attn_ws));
-    QIE_TRY(enqueue_head_rows(b, b->v.x, s.hidden, M, smp, head_bufs(b->v, 0, b->e->sh.vocab)));
-    const bool greedy = is_greedy(smp);
+    // with an entry: row i's window ends at p + i, history [.. p] and then the drafts d1 .. di
+    const EntryRows er{seq, 0, b->v.pos, b->v.draft, b->d_tail_len};
+    const bool entries = any_entry(b, seq, 1);
+    QIE_TRY(enqueue_head_rows(b, b->v.x, s.hidden, M, smp, head_bufs(b->v, 0, b->e->sh.vocab), entries ? &er : nullptr));
+    const bool greedy = !entries && is_greedy(smp);
     VerifyCommitArgs ca{seq, M, greedy ? b->v.keys : nullptr, b->v.ids, b->v.draft, s.vocab, b->dec.pos, b->dec.step,
                         b->dec.hist, b->max_ctx, b->dec.ids, (const uint4*)e->w.embed, (uint4*)b->dec.x, H8,
                         rope_cur_args(b), b->v.logits, b->dec.logits, (int64_t)e->sh.vocab, b->v.res};
@@ -2022,9 +2158,10 @@ static int enqueue_verify(qie_batch* b, int seq, int M, const qie_sampling* smp)
 static int launch_verify(qie_batch* b, int seq, int M, const qie_sampling* smp) {
     qie_engine* e = b->e;
     if (!e->opts.use_graph) return enqueue_verify(b, seq, M, smp);
-    const bool greedy = is_greedy(smp);
+    const bool greedy = is_greedy(smp), entries = any_entry(b, seq, 1);
     for (const auto& g : b->v_graphs)
-        if (g.seq == seq && g.M == M && g.greedy == greedy && (greedy || same_sampling(g.smp, smp))) {
+        if (g.seq == seq && g.M == M && g.entries == entries &&
+            (entries || (g.greedy == greedy && (greedy || same_sampling(g.smp, smp))))) {
             QIE_HIP(hipGraphLaunch(g.exec, e->stream));
             return 0;
         }
@@ -2034,7 +2171,7 @@ static int launch_verify(qie_batch* b, int seq, int M, const qie_sampling* smp) 
     }
     hipGraphExec_t exec = nullptr;
     QIE_TRY(capture_graph(e, "qie_verify: ", [&] { return enqueue_verify(b, seq, M, smp); }, &exec));
-    b->v_graphs.push_back({seq, M, greedy, smp ? *smp : qie_sampling{1, 0.f, 1.f, 0}, exec});
+    b->v_graphs.push_back({seq, M, entries, greedy, smp ? *smp : qie_sampling{1, 0.f, 1.f, 0}, exec});
     QIE_HIP(hipGraphLaunch(exec, e->stream));
     return 0;
 }

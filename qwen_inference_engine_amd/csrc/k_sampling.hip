@@ -12,6 +12,9 @@
 //     winners; the sorted keys reproduce the reference's k rounds exactly;
 //   * softmax + draw on one lane with the reference's sequential order and a
 //     cuRAND-XORWOW restatement (curand_init(seed, 0, 0); curand_uniform).
+//   * qie_sample_rows: the same two launches with every row under its own entry of a device
+//     table (penalties over a window of the slot's token history, logit bias, min-p;
+//     DESIGN.md §19) — the reference has one host-side parameter set per call.
 #include "qie_common.hpp"
 #include "launch_util.hpp"
 #include "../../include/qie/qie_ops.h"
@@ -20,6 +23,7 @@ namespace qie {
 
 constexpr int kSlice = 4096;
 constexpr int kMaxTopK = 256;
+constexpr int kMaxTail = 256;   // qie_sample_rows: ids a row may carry beside its history
 
 __global__ __launch_bounds__(256) void argmax_keys_kernel(const uint16_t* __restrict__ logits,
                                                           int64_t V, int64_t ld,
@@ -101,22 +105,14 @@ __device__ __forceinline__ float xorwow_uniform_first(uint64_t seed) {
     return x * 2.3283064e-10f + (2.3283064e-10f / 2.0f);
 }
 
-__global__ __launch_bounds__(256) void topk_merge_sample_kernel(const unsigned long long* __restrict__ cand,
-                                                                int nb, int k, int n2, float temperature,
-                                                                float top_p, uint64_t seed,
-                                                                const int32_t* step, int32_t* ids) {
+// Softmax at temperature T over the k largest keys sk[0..k) (sorted descending), the optional
+// min-p and top-p cuts, one draw from seed sd: logit_decode.cu:225-272 (thread 0).  One lane.
+__device__ __forceinline__ int32_t draw_sorted(const unsigned long long* sk, int k, float temperature, float top_p,
+                                               float min_p, uint64_t sd) {
 #pragma clang fp contract(off)
-    extern __shared__ __attribute__((aligned(16))) unsigned long long sk[];
-    const int64_t m = blockIdx.x;
-    const int total = nb * k;
-    for (int i = threadIdx.x; i < n2; i += 256) sk[i] = i < total ? cand[m * total + i] : 0ull;
-    __syncthreads();
-    bitonic_desc(sk, n2);
-    if (threadIdx.x != 0) return;
-    // logit_decode.cu:225-272 (thread 0): temperature, softmax, one draw.
     int n = 0;
     while (n < k && sk[n] != 0ull) n++;
-    if (n == 0) { ids[m] = -1; return; }
+    if (n == 0) return -1;
     float vals[kMaxTopK];
     float T = temperature > 0.0f ? temperature : 1.0f;
     float max_val = key_val(sk[0]) / T;
@@ -131,6 +127,15 @@ __global__ __launch_bounds__(256) void topk_merge_sample_kernel(const unsigned l
         vals[i] = expf(vals[i] - max_val);
         sum += vals[i];
     }
+    if (min_p > 0.0f && min_p <= 1.0f) {   // the leading entries at least min_p of the best (entry 0 stays)
+        int keep = 1;
+        while (keep < n && vals[keep] >= min_p) keep++;
+        if (keep < n) {
+            n = keep;
+            sum = 0.0f;
+            for (int i = 0; i < n; i++) sum += vals[i];
+        }
+    }
     if (top_p > 0.0f && top_p < 1.0f) {
         float cum = 0.0f;
         int keep = n;
@@ -142,7 +147,6 @@ __global__ __launch_bounds__(256) void topk_merge_sample_kernel(const unsigned l
         sum = 0.0f;
         for (int i = 0; i < n; i++) sum += vals[i];
     }
-    const uint64_t sd = seed + (step ? (uint64_t)(int64_t)step[m] : 0ull);
     float u = xorwow_uniform_first(sd) * sum;
     float cum = 0.0f;
     int picked = key_idx(sk[n - 1]);
@@ -150,7 +154,185 @@ __global__ __launch_bounds__(256) void topk_merge_sample_kernel(const unsigned l
         cum += vals[i];
         if (u <= cum) { picked = key_idx(sk[i]); break; }
     }
-    ids[m] = picked;
+    return picked;
+}
+
+__global__ __launch_bounds__(256) void topk_merge_sample_kernel(const unsigned long long* __restrict__ cand,
+                                                                int nb, int k, int n2, float temperature,
+                                                                float top_p, uint64_t seed,
+                                                                const int32_t* step, int32_t* ids) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long sk[];
+    const int64_t m = blockIdx.x;
+    const int total = nb * k;
+    for (int i = threadIdx.x; i < n2; i += 256) sk[i] = i < total ? cand[m * total + i] : 0ull;
+    __syncthreads();
+    bitonic_desc(sk, n2);
+    if (threadIdx.x != 0) return;
+    const uint64_t sd = seed + (step ? (uint64_t)(int64_t)step[m] : 0ull);
+    ids[m] = draw_sorted(sk, k, temperature, top_p, 0.0f, sd);
+}
+
+// ------------------------------------------------------------ per-row entries (qie_sample_rows)
+// What a row runs under: its slot's table entry, or (n_bias < 0: none) a neutral entry with the
+// call's four values.  Uniform per block.
+struct RowParams {
+    int k;   // candidates per slice and in the draw: 1 = greedy
+    float T, top_p, min_p;
+    uint64_t seed;
+    float rep, pres, freq;
+    int start, last_n, n_bias;
+    bool pen;
+};
+struct RowsArgs {
+    const uint16_t* logits;
+    int64_t V, ld;
+    const qie_slot_sampling* table;
+    int slot0, slot_stride;
+    qie_sampling fb;
+    const int32_t* hist;
+    int64_t hist_stride;
+    const int32_t *q, *tail, *tail_len, *step;
+    int32_t* ids;
+    unsigned long long* cand;   // [M][nb][kMaxTopK] (a row's slices packed at its own k)
+    int nb;
+};
+
+__device__ __forceinline__ RowParams row_params(const qie_slot_sampling* e, const qie_sampling& fb, int64_t V) {
+    RowParams p;
+    p.n_bias = e->n_bias;
+    int top_k;
+    if (p.n_bias < 0) {
+        top_k = fb.top_k, p.T = fb.temperature, p.top_p = fb.top_p, p.min_p = 0.f, p.seed = fb.seed;
+        p.rep = 1.f, p.pres = 0.f, p.freq = 0.f, p.start = 0, p.last_n = 0, p.n_bias = 0;
+    } else {
+        top_k = e->top_k, p.T = e->temperature, p.top_p = e->top_p, p.min_p = e->min_p, p.seed = e->seed;
+        p.rep = e->repetition_penalty, p.pres = e->presence_penalty, p.freq = e->frequency_penalty;
+        p.start = e->penalty_start, p.last_n = e->penalty_last_n;
+        if (p.n_bias > QIE_SLOT_BIAS_MAX) p.n_bias = QIE_SLOT_BIAS_MAX;
+    }
+    const bool greedy = top_k <= 1 || !(p.T > 0.f);
+    p.k = greedy ? 1 : (int)min((int64_t)min(top_k, kMaxTopK), V);
+    p.pen = p.rep != 1.f || p.pres != 0.f || p.freq != 0.f;
+    return p;
+}
+
+// the contract's penalty step on an id seen c > 0 times (qie_ops.h)
+__device__ __forceinline__ float penalise(float v, int c, const RowParams& p) {
+#pragma clang fp contract(off)
+    if (p.rep != 1.f) v = v > 0.f ? v / p.rep : v * p.rep;
+    float t = p.freq * (float)c;
+    t = p.pres + t;
+    return v - t;
+}
+
+__device__ __forceinline__ unsigned long long block_max_key(unsigned long long best, unsigned long long* red) {
+    best = wave_max(best);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
+    __syncthreads();
+    unsigned long long b = red[0];
+    for (int w = 1; w < 4; w++) b = red[w] > b ? red[w] : b;
+    return b;
+}
+
+// Block (slice, row): counts the window's ids that fall in its 4096-id slice (integer LDS
+// atomics: order-independent), builds the keys of the processed bf16 values, and leaves the
+// slice's k best (sorted; greedy: its one maximum) in cand.
+__global__ __launch_bounds__(256) void rows_slice_kernel(RowsArgs a) {
+#pragma clang fp contract(off)
+    __shared__ unsigned long long keys[kSlice];
+    __shared__ int cnt[kSlice];
+    __shared__ unsigned long long red[4];
+    const int64_t m = blockIdx.y;
+    const int64_t base = (int64_t)blockIdx.x * kSlice;
+    const int slot = a.slot0 + (int)m * a.slot_stride;
+    const qie_slot_sampling* e = a.table + slot;
+    const RowParams p = row_params(e, a.fb, a.V);
+    const uint16_t* row = a.logits + m * a.ld;
+    if (p.pen) {
+        for (int i = threadIdx.x; i < kSlice; i += 256) cnt[i] = 0;
+        __syncthreads();
+        const int64_t q = a.q[m];
+        int64_t tl = a.tail && a.tail_len ? a.tail_len[m] : 0;
+        tl = tl < 0 ? 0 : (tl > kMaxTail ? kMaxTail : tl);
+        int64_t lo = p.last_n > 0 ? q + 1 - p.last_n : 0;
+        lo = lo > p.start ? lo : p.start;
+        lo = lo > 0 ? lo : 0;
+        const int64_t hh = min(q - tl, a.hist_stride - 1);   // last position read from the history
+        const int32_t* h = a.hist + (int64_t)slot * a.hist_stride;
+        for (int64_t pos = lo + threadIdx.x; pos <= hh; pos += 256) {
+            const int64_t d = (int64_t)h[pos] - base;
+            if (d >= 0 && d < kSlice && base + d < a.V) atomicAdd(&cnt[d], 1);
+        }
+        // tail word t sits at position q - tl + 1 + t
+        const int64_t t0 = lo - (q - tl + 1);
+        for (int64_t t = (t0 > 0 ? t0 : 0) + threadIdx.x; t < tl; t += 256) {
+            const int64_t d = (int64_t)a.tail[t] - base;
+            if (d >= 0 && d < kSlice && base + d < a.V) atomicAdd(&cnt[d], 1);
+        }
+        __syncthreads();
+    }
+    for (int i = threadIdx.x; i < kSlice; i += 256) {
+        const int64_t idx = base + i;
+        unsigned long long key = 0ull;
+        if (idx < a.V) {
+            uint16_t bits = row[idx];
+            const int c = p.pen ? cnt[i] : 0;
+            if (c > 0) bits = f2bf(penalise(bf2f(bits), c, p));
+            key = sel_key(bf2f(bits), (uint32_t)idx);
+        }
+        keys[i] = key;
+    }
+    if (p.n_bias > 0) {   // at most 32 ids: each redone from the logit, after the sweep
+        __syncthreads();
+        if ((int)threadIdx.x < p.n_bias) {
+            const int64_t id = e->bias_ids[threadIdx.x];
+            const int64_t d = id - base;
+            if (d >= 0 && d < kSlice && id < a.V) {
+                float v = bf2f(row[id]);
+                const int c = p.pen ? cnt[d] : 0;
+                if (c > 0) v = penalise(v, c, p);
+                v = v + e->bias[threadIdx.x];
+                keys[d] = sel_key(bf2f(f2bf(v)), (uint32_t)id);
+            }
+        }
+    }
+    __syncthreads();
+    unsigned long long* out = a.cand + (m * a.nb * kMaxTopK) + (int64_t)blockIdx.x * p.k;
+    if (p.k == 1) {   // a max-reduce, not the sort (the branch is uniform per block)
+        unsigned long long best = 0ull;
+        for (int i = threadIdx.x; i < kSlice; i += 256) best = keys[i] > best ? keys[i] : best;
+        best = block_max_key(best, red);
+        if (threadIdx.x == 0) out[0] = best;
+        return;
+    }
+    bitonic_desc(keys, kSlice);
+    for (int i = threadIdx.x; i < p.k; i += 256) out[i] = keys[i];
+}
+
+// Block m: merges row m's nb * k slice winners and draws under the row's own parameters.
+// Dynamic LDS is sized for k = kMaxTopK; the sort runs over the row's own count.
+__global__ __launch_bounds__(256) void rows_merge_sample_kernel(RowsArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long sk[];   // all of the kernel's LDS (up to 160 KiB)
+    const int64_t m = blockIdx.x;
+    const int slot = a.slot0 + (int)m * a.slot_stride;
+    const RowParams p = row_params(a.table + slot, a.fb, a.V);
+    const unsigned long long* cand = a.cand + m * a.nb * kMaxTopK;
+    const int total = a.nb * p.k;
+    if (p.k == 1) {
+        unsigned long long best = 0ull;
+        for (int i = threadIdx.x; i < total; i += 256) best = cand[i] > best ? cand[i] : best;
+        best = block_max_key(best, sk);   // (the sort's LDS is free on this path; at least 4 words)
+        if (threadIdx.x == 0) a.ids[m] = key_idx(best);
+        return;
+    }
+    int n2 = 1;
+    while (n2 < total) n2 <<= 1;
+    for (int i = threadIdx.x; i < n2; i += 256) sk[i] = i < total ? cand[i] : 0ull;
+    __syncthreads();
+    bitonic_desc(sk, n2);
+    if (threadIdx.x != 0) return;
+    const uint64_t sd = p.seed + (a.step ? (uint64_t)(int64_t)a.step[m] : 0ull);
+    a.ids[m] = draw_sorted(sk, p.k, p.T, p.top_p, p.min_p, sd);
 }
 
 static int pow2_at_least(int x) {
@@ -207,6 +389,37 @@ int qie_sample(const void* logits, int64_t M, int64_t V, int64_t ld, const qie_s
     if (shm > 65536) QIE_TRY(raise_dynamic_lds((const void*)topk_merge_sample_kernel, 160 * 1024));
     hipLaunchKernelGGL(topk_merge_sample_kernel, dim3((unsigned)M), dim3(256), shm, st, cand, nb, k, n2,
                        s->temperature, s->top_p, (uint64_t)s->seed, step_dev, out_ids);
+    QIE_LAUNCH_CHECK();
+    return 0;
+}
+
+int64_t qie_sample_rows_workspace_bytes(int64_t M, int64_t V) {
+    const int64_t nb = (V + kSlice - 1) / kSlice;
+    return M * nb * kMaxTopK * 8 + 64;
+}
+
+int qie_sample_rows(const qie_sample_rows_args* a, void* stream) {
+    QIE_REQUIRE(a && a->logits && a->table && a->hist && a->q_dev && a->out_ids && a->ws && a->M >= 0 && a->V > 0 &&
+                    a->ld >= a->V && a->hist_stride > 0 && a->slot0 >= 0 && a->slot_stride >= 0,
+                "qie_sample_rows: bad arguments");
+    const int64_t V = a->V;
+    const int nb = (int)((V + kSlice - 1) / kSlice);
+    // the merge sorts up to nb * 256 keys in LDS
+    QIE_REQUIRE(nb <= 64, "qie_sample_rows: V %lld exceeds %d ids", (long long)V, 64 * kSlice);
+    if (a->M == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    RowsArgs r{};
+    r.logits = (const uint16_t*)a->logits, r.V = V, r.ld = a->ld;
+    r.table = a->table, r.slot0 = a->slot0, r.slot_stride = a->slot_stride;
+    r.fb = a->fallback ? *a->fallback : qie_sampling{1, 0.f, 1.f, 0};
+    r.hist = a->hist, r.hist_stride = a->hist_stride;
+    r.q = a->q_dev, r.tail = a->tail_dev, r.tail_len = a->tail_len_dev, r.step = a->step_dev;
+    r.ids = a->out_ids, r.cand = (unsigned long long*)a->ws, r.nb = nb;
+    hipLaunchKernelGGL(rows_slice_kernel, dim3(nb, (unsigned)a->M), dim3(256), 0, st, r);
+    QIE_LAUNCH_CHECK();
+    const size_t shm = (size_t)std::max(4, pow2_at_least(nb * (int)std::min<int64_t>(kMaxTopK, V))) * 8;
+    if (shm > 65536) QIE_TRY(raise_dynamic_lds((const void*)rows_merge_sample_kernel, 160 * 1024));
+    hipLaunchKernelGGL(rows_merge_sample_kernel, dim3((unsigned)a->M), dim3(256), shm, st, r);
     QIE_LAUNCH_CHECK();
     return 0;
 }

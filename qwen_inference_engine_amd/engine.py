@@ -39,6 +39,44 @@ class Sampling:
 
 GREEDY = Sampling()
 
+
+@dataclasses.dataclass
+class SlotSampling:
+    """One slot's own sampling entry (qie_slot_sampling; Batch.set_sampling): the four values of
+    Sampling, min-p, the repetition / presence / frequency penalties over the window
+    [max(penalty_start, q + 1 - penalty_last_n), q] of the slot's token history, and a logit
+    bias per token id (-inf bans the token)."""
+    top_k: int = 1
+    temperature: float = 1.0
+    top_p: float = 1.0
+    min_p: float = 0.0
+    seed: int = 1234
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    penalty_start: int = 0
+    penalty_last_n: int = 0
+    bias: Dict[int, float] = dataclasses.field(default_factory=dict)
+
+    def to_c(self) -> _lib.SlotSamplingC:
+        if len(self.bias) > _lib.QIE_SLOT_BIAS_MAX:
+            raise ValueError(f"SlotSampling: {len(self.bias)} biased ids, at most {_lib.QIE_SLOT_BIAS_MAX}")
+        s = _lib.SlotSamplingC()
+        s.top_k, s.temperature, s.top_p, s.min_p, s.seed = self.top_k, self.temperature, self.top_p, self.min_p, self.seed
+        s.repetition_penalty, s.presence_penalty = self.repetition_penalty, self.presence_penalty
+        s.frequency_penalty = self.frequency_penalty
+        s.penalty_start, s.penalty_last_n = self.penalty_start, self.penalty_last_n
+        s.n_bias = len(self.bias)
+        for i, (tok, v) in enumerate(self.bias.items()):
+            s.bias_ids[i], s.bias[i] = int(tok), float(v)
+        return s
+
+    @staticmethod
+    def from_c(s: _lib.SlotSamplingC) -> "SlotSampling":
+        return SlotSampling(s.top_k, s.temperature, s.top_p, s.min_p, s.seed, s.repetition_penalty,
+                            s.presence_penalty, s.frequency_penalty, s.penalty_start, s.penalty_last_n,
+                            {int(s.bias_ids[i]): float(s.bias[i]) for i in range(s.n_bias)})
+
 _ROLE_FIELDS = {
     "input_layernorm.weight": "attn_norm", "self_attn.q_proj.weight": "wq",
     "self_attn.k_proj.weight": "wk", "self_attn.v_proj.weight": "wv",
@@ -266,6 +304,20 @@ class Batch:
         else:
             _lib.check(self.lib.qie_batch_create(engine.h, batch, max_ctx, C.byref(h)), "qie_batch_create")
         self.h = h
+
+    def set_sampling(self, seq: int, sampling: Optional[SlotSampling]) -> None:
+        """Slot `seq` samples under its own entry from now on, in every call that samples
+        (prefill, append, score, decode, verify), until it is replaced or cleared (None); a slot
+        without one uses the call's Sampling.  A fork copies it; release and prefill keep it."""
+        sc = sampling.to_c() if sampling is not None else None
+        _lib.check(self.lib.qie_batch_set_slot_sampling(self.h, seq, C.byref(sc) if sc is not None else None),
+                   "qie_batch_set_slot_sampling")
+
+    def slot_sampling(self, seq: int) -> Optional[SlotSampling]:
+        sc, is_set = _lib.SlotSamplingC(), C.c_int32(0)
+        _lib.check(self.lib.qie_batch_slot_sampling(self.h, seq, C.byref(sc), C.byref(is_set)),
+                   "qie_batch_slot_sampling")
+        return SlotSampling.from_c(sc) if is_set.value else None
 
     def prefill(self, seq: int, ids: Sequence[int], sampling: Sampling = GREEDY, chunk: Optional[int] = None) -> int:
         """Start sequence `seq` with the prompt `ids`.  chunk: feed the prompt in pieces of at

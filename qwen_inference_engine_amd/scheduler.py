@@ -16,8 +16,12 @@ seen on shared KV pages (``Batch.save_prefix``) and starts a request that begins
 from those pages (``Batch.load_prefix`` + ``append`` of the remainder) instead of prefilling the
 same ids again.
 
-One sampling configuration per batcher (``qie_sampling`` is per step); slot rows are
-independent, so a request's tokens do not depend on what the other slots hold.
+Sampling is per request: ``submit(..., sampling=SlotSampling(...))`` sets that request's entry on
+its slot (``Batch.set_sampling``) when it takes the slot — before its first prefill, append or
+prefix load — and clears it when the request finishes; a request without one samples under the
+batcher's ``sampling`` (``qie_sampling``, per step).  ``penalize_prompt=False`` starts the
+penalty window behind the prompt.  Slot rows are independent, so a request's tokens do not
+depend on what the other slots hold.
 """
 from __future__ import annotations
 
@@ -25,7 +29,7 @@ import collections
 import dataclasses
 from typing import Deque, Dict, List, Optional, Sequence
 
-from .engine import GREEDY, Batch, Engine, Sampling
+from .engine import GREEDY, Batch, Engine, Sampling, SlotSampling
 
 
 @dataclasses.dataclass
@@ -42,6 +46,7 @@ class Request:
     done: bool = False
     chunks: list = dataclasses.field(default_factory=list)   # (offset, length) prompt pieces still to prefill
     matched: int = 0          # prompt ids taken from the prefix cache (a multiple of page_tokens)
+    sampling: Optional[SlotSampling] = None   # the request's own entry (None: the batcher's sampling)
 
 
 def prefill_runs(admitted: Sequence[Request]) -> List[List[Request]]:
@@ -142,20 +147,30 @@ class ContinuousBatcher:
     def _pages(self, n_tokens: int) -> int:
         return -(-n_tokens // self.page_tokens)
 
-    def submit(self, prompt: Sequence[int], max_new_tokens: int, stop_ids: Sequence[int] = ()) -> int:
+    def submit(self, prompt: Sequence[int], max_new_tokens: int, stop_ids: Sequence[int] = (),
+               sampling: Optional[SlotSampling] = None, penalize_prompt: bool = True) -> int:
         n = len(prompt)
         if n < 1 or max_new_tokens < 1 or n + max_new_tokens > self.max_ctx - 1:
             raise ValueError(f"request of {n} + {max_new_tokens} tokens does not fit max_ctx {self.max_ctx}")
         if self._pages(n + max_new_tokens) > self.budget + sum(r.pages for r in self.slots if r):
             raise ValueError("request larger than the whole page pool")
         r = Request(self._next, [int(t) for t in prompt], int(max_new_tokens), tuple(int(s) for s in stop_ids))
+        if sampling is not None:   # penalize_prompt=False: the penalties see generated tokens only
+            r.sampling = sampling if penalize_prompt else dataclasses.replace(sampling, penalty_start=n)
         self._next += 1
         self.requests[r.rid] = r
         self.waiting.append(r)
         return r.rid
 
+    def _take_slot(self, r: Request) -> None:
+        """The request's own entry goes onto its slot before anything of it is prefilled."""
+        if r.sampling is not None:
+            self.batch.set_sampling(r.slot, r.sampling)
+
     def _finish(self, r: Request) -> None:
         r.done = True
+        if r.sampling is not None:
+            self.batch.set_sampling(r.slot, None)
         self.batch.release(r.slot)
         self.slots[r.slot] = None
         self.budget += r.pages
@@ -280,6 +295,7 @@ class ContinuousBatcher:
             r.slot, r.pages, r.matched = free_slot, need, n
             self.budget -= need
             self.slots[free_slot] = r
+            self._take_slot(r)
             if n:
                 self._clock += 1
                 entry.used = self._clock
@@ -318,6 +334,7 @@ class ContinuousBatcher:
             r.slot, r.pages = free_slot, need
             self.budget -= need
             self.slots[free_slot] = r
+            self._take_slot(r)
             admitted.append(r)
         # equal-length prompts landing in consecutive slots prefill in one pass
         # (qie_prefill_batch); tokens are emitted in admission order afterwards
