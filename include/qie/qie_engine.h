@@ -154,7 +154,7 @@ void qie_batch_destroy(qie_batch* b);
  * n_pages 0 = enough for every slot at max_ctx.  Pages are taken on demand by
  * qie_prefill / qie_decode* / qie_batch_set_position and returned by
  * qie_batch_release; running out of pages fails the call with nothing launched and nothing
- * changed: -28 from qie_prefill_append, qie_score at pos0 >= 1, qie_verify, qie_batch_fork
+ * changed: -28 from qie_prefill_append, qie_prefill_ragged, qie_score at pos0 >= 1, qie_verify, qie_batch_fork
  * and a qie_batch_set_position into a shared page; -22 from qie_prefill, qie_prefill_batch,
  * qie_score at pos0 = 0, qie_decode_step, qie_decode, qie_batch_reserve and a
  * qie_batch_set_position that only grows.
@@ -197,6 +197,28 @@ int qie_prefill_batch(qie_batch* b, int32_t seq0, int32_t n_seqs, const int32_t*
  * numerics are defined for a prefill from position 0 only. */
 int qie_prefill_append(qie_batch* b, int32_t seq, const int32_t* ids, int32_t n, int32_t pos0,
                        const qie_sampling* s, int32_t* next_id);
+/* Ragged prefill: up to QIE_RAGGED_MAX_SEGS segments — each its own slot, length
+ * and start position, fresh prompts and appends mixed — in ONE pass over the weights.  ids: host,
+ * the segments' ids laid end to end.  Segment z with pos0 == 0 does to slot seq what qie_prefill
+ * does (a new sequence; the pages only that slot holds go back to the pool first), with
+ * pos0 >= 1 what qie_prefill_append does (a live slot, pos0 <= its position, rows from pos0 on
+ * overwritten, shared pages of the write range made private first).  Every integer is exactly
+ * what the sequence of single calls leaves: positions, history, the current token, the step
+ * counter, pages per slot, free pages and holder counts; per-slot sampling entries are honoured;
+ * row seq of qie_batch_logits holds the logits behind the segment's token, next_ids[z] (host
+ * [n_segs] or NULL: then nothing is synchronised) is segment z's token.  Logits and K/V are NOT
+ * bit-equal to the single calls (the GEMM kernels are picked by the total row count and the
+ * attention split follows it); they meet the same oracle parity bar.  A segment's results do not
+ * depend on the other segments' ids.
+ * Preconditions: seq strictly increasing across segments, 1 <= n_segs <= B, n >= 1,
+ * pos0 + n < max_ctx, ids in range.  All-or-nothing, before anything is launched or allocated:
+ * -22 for bad arguments, an append segment on an idle or released slot, pos0 past the slot's
+ * position, an engine created with prefill_fp8, and a batch in decode mode 1 with n_segs > 1;
+ * -28 when the pool cannot hold every segment's rows together.  After either every slot continues
+ * as if the call had not been made.  Collective under tensor parallelism, like qie_prefill. */
+typedef struct qie_prefill_seg { int32_t seq, n, pos0; } qie_prefill_seg;
+int qie_prefill_ragged(qie_batch* b, const qie_prefill_seg* segs, int32_t n_segs, const int32_t* ids,
+                       const qie_sampling* s, int32_t* next_ids);
 /* Scoring: the log-probability of a given text (numerics contract in qie_ops.h,
  * "scoring").  qie_score IS qie_prefill (pos0 == 0) or qie_prefill_append (pos0 >= 1) of the n
  * ids in every effect on the sequence — KV rows, pages, history, position, the current token, the

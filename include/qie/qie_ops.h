@@ -145,6 +145,25 @@ int qie_qkv_post(const void* qkv, int64_t M, const int32_t* pos, int32_t rows_pe
                  const float* rope_sin, int32_t n_heads, const qie_kv_cache* cache,
                  int32_t layer, float eps, int32_t numerics, void* q_out, void* stream);
 
+/* Ragged rows: M rows that are up to QIE_RAGGED_MAX_SEGS segments of any lengths laid end to
+ * end, each segment the rows of one cache sequence.  The table is host memory and is copied by
+ * value into the kernel arguments: no device table, no allocation, no synchronisation. */
+#define QIE_RAGGED_MAX_SEGS 8
+typedef struct qie_row_segs {
+    int32_t n;                                   /* 1 .. QIE_RAGGED_MAX_SEGS segments              */
+    int32_t row0[QIE_RAGGED_MAX_SEGS + 1];       /* rows of segment z: [row0[z], row0[z+1]);
+                                                    row0[0] = 0, strictly increasing, row0[n] = M  */
+    int32_t seq[QIE_RAGGED_MAX_SEGS];            /* the cache's sequence index of segment z; distinct */
+} qie_row_segs;
+
+/* qie_qkv_post with row m's sequence = segs->seq[z] of the segment z that holds it; the per-row
+ * arithmetic is qie_qkv_post's.  -22 for a malformed table (n out of range, row0 not strictly
+ * increasing from 0 to M, a repeated seq), nothing written. */
+int qie_qkv_post_ragged(const void* qkv, int64_t M, const int32_t* pos, const qie_row_segs* segs,
+                        const void* q_norm, const void* k_norm, const float* rope_cos,
+                        const float* rope_sin, int32_t n_heads, const qie_kv_cache* cache,
+                        int32_t layer, float eps, int32_t numerics, void* q_out, void* stream);
+
 /* -------------------------------------------------------------- attention
  * Replaces launch_attn / selfattention (helpers.cuh:121-130,
  * self_attension.cu:10-149): GQA attention of query rows over the cache.
@@ -172,6 +191,21 @@ int64_t qie_attention_extend_workspace_bytes(int64_t M, int32_t n_heads, int32_t
                                              int32_t max_ctx);
 int32_t qie_attention_extend_split_tokens(int64_t M, int32_t max_ctx);
 int qie_attention_extend(const void* q, int64_t M, const int32_t* pos, int32_t rows_per_seq,
+                         const qie_kv_cache* cache, int32_t layer, int32_t n_heads, void* out,
+                         void* ws, void* stream);
+
+/* qie_attention_extend over ragged rows (qie_row_segs above; M = segs->row0[segs->n]): row m
+ * attends to [0, pos[m]] of sequence segs->seq[z] of its segment, positions non-decreasing
+ * within a segment, the rows' own K/V already in the cache; head_dim 64 or 128, contiguous and
+ * paged caches, ws need not be initialised.  One workgroup per (block of 128 flattened rows of
+ * one segment, key split, kv head): grid x is the sum of the segments' block counts, so a short
+ * segment beside a long one launches no empty block.  The split length and the workspace are
+ * qie_attention_extend_split_tokens(M, max_ctx) and qie_attention_extend_workspace_bytes(M, ..)
+ * at the total row count M; inside a segment the rows are packed as the extend kernel packs a
+ * sequence's, so a segment's result equals, bit for bit, that of qie_attention_extend on those
+ * rows alone whenever the two calls use the same split length.  -22 for a malformed table, a
+ * bad head shape or layer, or more workgroups than a grid holds; nothing is launched. */
+int qie_attention_ragged(const void* q, const int32_t* pos, const qie_row_segs* segs,
                          const qie_kv_cache* cache, int32_t layer, int32_t n_heads, void* out,
                          void* ws, void* stream);
 

@@ -95,6 +95,18 @@ class KvCacheC(C.Structure):
                 ("max_pages", C.c_int32)]
 
 
+QIE_RAGGED_MAX_SEGS = 8
+
+
+class RowSegsC(C.Structure):
+    _fields_ = [("n", C.c_int32), ("row0", C.c_int32 * (QIE_RAGGED_MAX_SEGS + 1)),
+                ("seq", C.c_int32 * QIE_RAGGED_MAX_SEGS)]
+
+
+class PrefillSegC(C.Structure):
+    _fields_ = [("seq", C.c_int32), ("n", C.c_int32), ("pos0", C.c_int32)]
+
+
 class EngineOptsC(C.Structure):
     _fields_ = [("device", C.c_int32), ("max_ctx", C.c_int32), ("use_graph", C.c_int32),
                 ("tp_rank", C.c_int32), ("tp_size", C.c_int32), ("tp_comm", C.c_void_p),
@@ -132,11 +144,14 @@ SIGNATURES = [
     ("qie_debug_linear_plan", C.c_int, [C.POINTER(LinearArgsC), C.c_char_p, C.c_int]),
     ("qie_qkv_post", C.c_int, [_P, _I64, _P, _I32, _P, _P, _P, _P, _I32, C.POINTER(KvCacheC),
                                _I32, _F, _I32, _P, _P]),
+    ("qie_qkv_post_ragged", C.c_int, [_P, _I64, _P, C.POINTER(RowSegsC), _P, _P, _P, _P, _I32, C.POINTER(KvCacheC),
+                                      _I32, _F, _I32, _P, _P]),
     ("qie_attention_workspace_bytes", C.c_int64, [_I64, _I32, _I32, _I32]),
     ("qie_attention", C.c_int, [_P, _I64, _P, _I32, C.POINTER(KvCacheC), _I32, _I32, _P, _P, _P]),
     ("qie_attention_extend_workspace_bytes", C.c_int64, [_I64, _I32, _I32, _I32]),
     ("qie_attention_extend_split_tokens", C.c_int32, [_I64, _I32]),
     ("qie_attention_extend", C.c_int, [_P, _I64, _P, _I32, C.POINTER(KvCacheC), _I32, _I32, _P, _P, _P]),
+    ("qie_attention_ragged", C.c_int, [_P, _P, C.POINTER(RowSegsC), C.POINTER(KvCacheC), _I32, _I32, _P, _P, _P]),
     ("qie_attention_decode_workspace_bytes", C.c_int64, [_I64, _I32, _I32, _I32, _I32]),
     ("qie_attention_decode", C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _I32, C.POINTER(KvCacheC), _I32, _F, _I32,
                                        _P, _P, _P]),
@@ -212,6 +227,7 @@ SIGNATURES = [
     ("qie_prefill", C.c_int, [_P, _I32, _PI32, _I32, C.POINTER(SamplingC), _PI32]),
     ("qie_prefill_batch", C.c_int, [_P, _I32, _I32, _PI32, _I32, C.POINTER(SamplingC), _PI32]),
     ("qie_prefill_append", C.c_int, [_P, _I32, _PI32, _I32, _I32, C.POINTER(SamplingC), _PI32]),
+    ("qie_prefill_ragged", C.c_int, [_P, C.POINTER(PrefillSegC), _I32, _PI32, C.POINTER(SamplingC), _PI32]),
     ("qie_score", C.c_int, [_P, _I32, _PI32, _I32, _I32, _PI32, C.POINTER(SamplingC), _I32, _PF, _PI32, _PI32]),
     ("qie_batch_logprobs", C.c_int, [_P, _PI32, _PF]),
     ("qie_verify", C.c_int, [_P, _I32, _PI32, _I32, C.POINTER(SamplingC), _PI32, _PI32]),

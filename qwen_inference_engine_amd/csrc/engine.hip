@@ -276,6 +276,24 @@ __global__ void copy_ids_kernel(const int32_t* src, int32_t* dst, int len, int64
     if (i < len) dst[blockIdx.y * dst_stride + i] = src[(int64_t)blockIdx.y * len + i];
 }
 
+// qie_prefill_ragged's form of the two kernels above: row i of segment z (the table travels by
+// value) sits at pos0[z] + i - row0[z], and its id lands there in history row seq[z]
+struct RaggedRows {
+    qie_row_segs segs;
+    int32_t pos0[QIE_RAGGED_MAX_SEGS];
+};
+__global__ void ragged_rows_kernel(RaggedRows t, const int32_t* ids, int32_t* pos, int32_t* hist, int64_t hist_stride) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= t.segs.row0[QIE_RAGGED_MAX_SEGS]) return;   // the caller repeats M in the unused entries
+    int row0 = 0, seq = t.segs.seq[0], p0 = t.pos0[0];   // constant indices only
+#pragma unroll
+    for (int z = 1; z < QIE_RAGGED_MAX_SEGS; z++)
+        if (z < t.segs.n && i >= t.segs.row0[z]) row0 = t.segs.row0[z], seq = t.segs.seq[z], p0 = t.pos0[z];
+    const int p = p0 + i - row0;
+    pos[i] = p;
+    hist[seq * hist_stride + p] = ids[i];
+}
+
 static RopeCurArgs rope_cur_args(const qie_batch* b) {
     const qie_engine* e = b->e;
     return RopeCurArgs{b->dec.rope_cur, e->rope_cos, e->rope_sin, (int)e->spec.head_dim, e->rope_rows};
@@ -711,7 +729,9 @@ static int enqueue_layer_decode(qie_batch* b, int l) {
 // The layer of the multi-row forms (prefill, append, the verify step): the q/k post-projection
 // writes the rows' K/V at their positions r.pos, then `attend` runs over them — qie_attention
 // from position 0 (the rows are the whole context), qie_attention_extend where the rows
-// continue a cached prefix (each row sees the prefix and the rows before it).
+// continue a cached prefix (each row sees the prefix and the rows before it).  r.segs set
+// (qie_prefill_ragged): the rows are segments of any lengths, each of its own sequence, and both
+// steps take their ragged forms (`attend` is not consulted).
 using AttentionFn = decltype(&qie_attention);
 static int enqueue_layer_rows(qie_batch* b, int l, const LayerRows& r, const LayerPath& p, const qie_kv_cache& cache,
                               AttentionFn attend, void* attn_ws) {
@@ -720,9 +740,15 @@ static int enqueue_layer_rows(qie_batch* b, int l, const LayerRows& r, const Lay
     const qie_layer_weights& L = p.layers[l];
     hipStream_t st = e->stream;
     QIE_TRY(run_proj(b, qkv_args(e, L, p.flags, r), p.in, r));
-    QIE_TRY(qie_qkv_post(r.qkv, r.M, r.pos, r.rows_per_seq, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, e->sh.nq,
-                         &cache, l, s.rms_eps, s.numerics, r.q, st));
-    QIE_TRY(attend(r.q, r.M, r.pos, r.rows_per_seq, &cache, l, e->sh.nq, r.att, attn_ws, st));
+    if (r.segs) {
+        QIE_TRY(qie_qkv_post_ragged(r.qkv, r.M, r.pos, r.segs, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, e->sh.nq,
+                                    &cache, l, s.rms_eps, s.numerics, r.q, st));
+        QIE_TRY(qie_attention_ragged(r.q, r.pos, r.segs, &cache, l, e->sh.nq, r.att, attn_ws, st));
+    } else {
+        QIE_TRY(qie_qkv_post(r.qkv, r.M, r.pos, r.rows_per_seq, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, e->sh.nq,
+                             &cache, l, s.rms_eps, s.numerics, r.q, st));
+        QIE_TRY(attend(r.q, r.M, r.pos, r.rows_per_seq, &cache, l, e->sh.nq, r.att, attn_ws, st));
+    }
     QIE_TRY(run_row_proj(b, o_args(e, L, p.flags, r), p.in, r));
     QIE_TRY(run_proj(b, gate_up_args(e, L, p.flags, r), p.in, r));
     return run_row_proj(b, down_args(e, L, p.flags, r), p.in, r);
@@ -1808,6 +1834,25 @@ static int enqueue_score(qie_batch* b, int seq, int n, const ScoreReq& rq) {
     return qie_logprob_rows(last, 1, V, V, b->sc.tgt + (n - 1), b->sc.lp + (n - 1), b->sc.ids + (n - 1), st);
 }
 
+// The embedding of the r.M ids in pf.ids_in and the layer stack over those rows of b->pf: what
+// every prefill form runs between its bookkeeping and its head.
+static int enqueue_prompt_layers(qie_batch* b, const LayerRows& r, const qie_kv_cache& cache, AttentionFn attend) {
+    qie_engine* e = b->e;
+    const qie_model_spec& s = e->spec;
+    const int64_t n = r.M;
+    QIE_TRY(qie_embedding(e->w.embed, b->pf.ids_in, b->pf.x, n, s.hidden, e->stream));
+    // opts.prefill_fp8: every projection on fp8 codes x fp8 weights (e->layers: the fp8 arena).
+    // Otherwise bf16 rows; on an fp8 engine at >= 256 rows the GEMMs run on the dequantised bf16
+    // copy (layers_pf), and with tiled fp8 projections (readable by the batched-decode kernel
+    // only) every prefill of more than 16 rows does
+    const bool pf16 = e->fp8 && !e->layers_pf.empty() && (n >= 256 || (e->fp8_t16 && n > 16));
+    LayerPath path{e->layers.data(), proj_flags(e), prefill_mx(e) ? InputForm::Fp8 : InputForm::Normed};
+    if (pf16 && path.in == InputForm::Normed)
+        path = LayerPath{e->layers_pf.data(), path.flags & ~(QIE_LINEAR_FP8 | QIE_LINEAR_FP8_T16), InputForm::Normed};
+    for (int l = 0; l < s.n_layers; l++) QIE_TRY(enqueue_layer_rows(b, l, r, path, cache, attend, b->pf_ws.p));
+    return 0;
+}
+
 // Prefill of n_seqs prompts of len ids each into slots seq0 .. seq0+n_seqs-1 (ids laid end
 // to end): every GEMM runs once over all n_seqs * len rows, attention and the KV append see
 // the prompts as sequences of rows_per_seq = len, and the head samples the n_seqs last rows
@@ -1870,19 +1915,8 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
     hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b->pf.pos, (int)n, len, pos0);
     hipLaunchKernelGGL(copy_ids_kernel, dim3((len + 255) / 256, n_seqs), dim3(256), 0, st, b->pf.ids_in,
                        b->dec.hist + (int64_t)seq0 * b->max_ctx + pos0, len, (int64_t)b->max_ctx);
-    QIE_TRY(qie_embedding(e->w.embed, b->pf.ids_in, b->pf.x, n, H, st));
-    const qie_kv_cache cache = batch_cache(b, seq0);
-    const LayerRows r = layer_rows(b->pf, n, len);
-    // opts.prefill_fp8: every projection on fp8 codes x fp8 weights (e->layers: the fp8 arena).
-    // Otherwise bf16 rows; on an fp8 engine at >= 256 rows the GEMMs run on the dequantised bf16
-    // copy (layers_pf), and with tiled fp8 projections (readable by the batched-decode kernel
-    // only) every prefill of more than 16 rows does
-    const bool pf16 = e->fp8 && !e->layers_pf.empty() && (n >= 256 || (e->fp8_t16 && n > 16));
-    LayerPath path{e->layers.data(), proj_flags(e), prefill_mx(e) ? InputForm::Fp8 : InputForm::Normed};
-    if (pf16 && path.in == InputForm::Normed)
-        path = LayerPath{e->layers_pf.data(), path.flags & ~(QIE_LINEAR_FP8 | QIE_LINEAR_FP8_T16), InputForm::Normed};
-    for (int l = 0; l < s.n_layers; l++)
-        QIE_TRY(enqueue_layer_rows(b, l, r, path, cache, append ? qie_attention_extend : qie_attention, b->pf_ws.p));
+    QIE_TRY(enqueue_prompt_layers(b, layer_rows(b->pf, n, len), batch_cache(b, seq0),
+                                  append ? qie_attention_extend : qie_attention));
     // position of each last prompt token; finalize advances it to pos0 + len (the new token).
     for (int z = 0; z < n_seqs; z++)
         QIE_TRY(set_slot_state(b, seq0 + z, pos0 + len - 1, 0, ids[(int64_t)z * len + len - 1], 0));
@@ -1921,6 +1955,82 @@ int qie_prefill_append(qie_batch* b, int32_t seq, const int32_t* ids, int32_t n,
 int qie_prefill_batch(qie_batch* b, int32_t seq0, int32_t n_seqs, const int32_t* ids, int32_t len,
                       const qie_sampling* smp, int32_t* next_ids) {
     return prefill_rows(b, seq0, n_seqs, ids, len, 0, smp, next_ids, "qie_prefill_batch");
+}
+
+// Prompts and appends of any lengths in one pass: prefill_rows with a segment
+// table in place of the rectangle.  The rows' positions and history come from ragged_rows_kernel,
+// the layers run the ragged q/k post-projection and attention (LayerRows::segs), and the head
+// runs once per maximal run of consecutive slots over that run's packed last rows.
+int qie_prefill_ragged(qie_batch* b, const qie_prefill_seg* segs, int32_t n_segs, const int32_t* ids,
+                       const qie_sampling* smp, int32_t* next_ids) {
+    const char* who = "qie_prefill_ragged";
+    QIE_REQUIRE(b && segs && ids && n_segs >= 1 && n_segs <= b->B && n_segs <= QIE_RAGGED_MAX_SEGS,
+                "%s: bad arguments (1 .. min(B, %d) segments)", who, QIE_RAGGED_MAX_SEGS);
+    qie_engine* e = b->e;
+    const qie_model_spec& s = e->spec;
+    QIE_REQUIRE(!e->opts.prefill_fp8,
+                "%s: not available on a prefill_fp8 engine (block-scaled fp8 activations are defined for a "
+                "prefill from position 0 only: an append has no reference to be checked against)", who);
+    QIE_REQUIRE(b->decode_mode != 1 || n_segs == 1, "%s: one segment per call in decode mode 1", who);
+    RaggedRows t{};
+    PagePool::Span spans[kMaxBatchSlots];   // n_segs <= B <= kMaxBatchSlots
+    int64_t n = 0;                          // rows
+    for (int z = 0; z < n_segs; z++) {
+        const qie_prefill_seg& g = segs[z];
+        QIE_REQUIRE(g.seq >= 0 && g.seq < b->B && g.n >= 1 && g.pos0 >= 0 && (z == 0 || g.seq > segs[z - 1].seq),
+                    "%s: segment %d: bad arguments (slots strictly increasing, n >= 1, pos0 >= 0)", who, z);
+        QIE_REQUIRE((int64_t)g.pos0 + g.n < b->max_ctx, "%s: %d tokens from position %d do not fit max_ctx %d", who,
+                    g.n, g.pos0, b->max_ctx);
+        if (g.pos0 > 0) {
+            QIE_REQUIRE(!b->idle[g.seq], "%s: slot %d holds no live sequence", who, g.seq);
+            QIE_REQUIRE(g.pos0 <= b->h_pos[g.seq], "%s: pos0 %d is past sequence %d's current position %d", who,
+                        g.pos0, g.seq, b->h_pos[g.seq]);
+        }
+        t.segs.row0[z] = (int32_t)n, t.segs.seq[z] = g.seq, t.pos0[z] = g.pos0;
+        spans[z] = PagePool::Span{g.seq, g.pos0, (int64_t)g.pos0 + g.n - 1, g.pos0 == 0};
+        n += g.n;
+    }
+    t.segs.n = n_segs;
+    for (int z = n_segs; z <= QIE_RAGGED_MAX_SEGS; z++) t.segs.row0[z] = (int32_t)n;
+    for (int64_t i = 0; i < n; i++)
+        QIE_REQUIRE(ids[i] >= 0 && ids[i] < s.vocab, "%s: token id %d out of range", who, ids[i]);
+    hipStream_t st = e->stream;
+    // all-or-nothing, before anything is allocated or launched: one reservation over every segment
+    KvWrites kv;
+    QIE_TRY(plan_kv_writes(b, spans, n_segs, kv));
+    if (!kv.fits())
+        return fail(-28, "%s: KV pool exhausted (%lld more pages needed for %lld rows in %d segments, %lld free)", who,
+                    (long long)kv.r.need, (long long)n, n_segs, (long long)kv.free);
+    QIE_TRY(ensure_prefill_scratch(b, n, true));
+    QIE_TRY(commit_kv_writes(b, kv));
+    for (int z = 0; z < n_segs; z++) b->idle[segs[z].seq] = 0;
+    const int64_t H = s.hidden;
+    QIE_HIP(hipMemcpyAsync(b->pf.ids_in, ids, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(ragged_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, t, b->pf.ids_in,
+                       b->pf.pos, b->dec.hist, (int64_t)b->max_ctx);
+    QIE_LAUNCH_CHECK();
+    QIE_TRY(enqueue_prompt_layers(b, layer_rows(b->pf, n, 0, &t.segs), batch_cache(b, 0), nullptr));
+    // position of each last id (finalize advances it to pos0 + n: the new token), and the last rows
+    // packed in segment order into pf.xn, which is free after the layer loop
+    for (int z = 0; z < n_segs; z++) {
+        const qie_prefill_seg& g = segs[z];
+        const int64_t last = t.segs.row0[z + 1] - 1;
+        QIE_TRY(set_slot_state(b, g.seq, g.pos0 + g.n - 1, 0, ids[last], 0));
+        QIE_HIP(hipMemcpyAsync(b->pf.xn + z * H, b->pf.x + last * H, (size_t)H * 2, hipMemcpyDeviceToDevice, st));
+    }
+    for (int z0 = 0, z1; z0 < n_segs; z0 = z1) {   // one head per run of consecutive slots
+        for (z1 = z0 + 1; z1 < n_segs && segs[z1].seq == segs[z1 - 1].seq + 1;) z1++;
+        QIE_TRY(enqueue_head(b, b->pf.xn + z0 * H, H, segs[z0].seq, z1 - z0, smp));
+    }
+    for (int z = 0; z < n_segs; z++) b->h_pos[segs[z].seq] = segs[z].pos0 + segs[z].n;
+    if (next_ids) {
+        int32_t all[kMaxBatchSlots];
+        QIE_HIP(hipMemcpyAsync(all, b->dec.ids, (size_t)b->B * 4, hipMemcpyDeviceToHost, st));
+        QIE_HIP(hipStreamSynchronize(st));
+        QIE_TRY(comm_check(e, who));
+        for (int z = 0; z < n_segs; z++) next_ids[z] = all[segs[z].seq];
+    }
+    return 0;
 }
 
 int qie_score(qie_batch* b, int32_t seq, const int32_t* ids, int32_t n, int32_t pos0, const int32_t* targets,

@@ -15,12 +15,14 @@
 //     tile looks its own page up);
 //   * every workgroup leaves fp32 partials (O, running max, sum) in the workspace and a
 //     second, ordinary launch merges them — no hand-off inside a launch.
+// One workgroup's work is attn_extend_block (attn_extend_block.hpp), shared with the ragged
+// form (k_attn_ragged.hip).
 // Arithmetic, LDS images (LDS-DMA staging, XOR chunk swizzles, ds_read_b64_tr_b16 V reads)
 // and the per-tile softmax are attn_mfma_walk (attn_mfma_tile.hpp), the walk
 // attn_prefill_mfma2_kernel runs from key 0; that header documents the operand layouts.
 #include "qie_common.hpp"
 #include "../../include/qie/qie_ops.h"
-#include "attn_mfma_tile.hpp"
+#include "attn_extend_block.hpp"
 
 namespace qie {
 
@@ -28,7 +30,6 @@ constexpr int kExtSplitLong = 512;    // keys per split
 constexpr int kExtSplitShort = 256;   // ... for calls of <= kExtShortRows rows (more workgroups)
 constexpr int kExtShortRows = 32;
 constexpr int kExtMaxSplits = 64;     // longer contexts take longer splits
-constexpr int kExtBlockRows = 128;    // flattened rows per workgroup (4 waves x 2 groups x 16)
 
 // split length and count for a call of M rows on a max_ctx-key cache; a function of
 // (M, max_ctx) only, so the workspace can be sized before the call.  The length is a power of
@@ -45,125 +46,14 @@ static void extend_split(int64_t M, int32_t max_ctx, int* len, int* count) {
     *count = n < 1 ? 1 : n;
 }
 
-struct ExtendAttnParams {
-    const uint16_t* q;       // [M][nq*HD]
-    const int32_t* pos;      // [M]; non-decreasing within each sequence's rows
-    int rows_per_seq;
-    int64_t M;
-    const uint16_t* kc;
-    const uint16_t* vc;
-    KvMap km;
-    int layer, nkv, nq;
-    int nsplit, split_len;
-    float* part_o;    // [M][nq][nsplit][HD]; merged by attn_combine_kernel<HD, true>
-    float* part_ml;   // [M][nq][nsplit][2]: running max (log2 domain), sum
-    uint16_t* out;    // [M][nq*HD]
-};
-
-// Grid (row blocks, splits, n_seqs * nkv), 256 threads.  Wave w owns the block's 16-row
-// groups (w, 7 - w): positions are non-decreasing in the flattened row index, so the pair
-// evens out the rows' own causal triangle as in the prefill kernel; the rectangle over the
-// prefix is the same for every group.
+// Grid (row blocks, splits, n_seqs * nkv), 256 threads: sequence z owns rows
+// [z * rows_per_seq, (z + 1) * rows_per_seq) of the call; the workgroup is attn_extend_block.
 template <int HD, bool PG>
 __global__ __launch_bounds__(256, 2) void attn_extend_kernel(ExtendAttnParams a) {
-    constexpr int NW = 4;
-    constexpr int KT = 64;
-    constexpr int KSTEPS = HD / 32;
-    constexpr int DT = HD / 16;
-    constexpr int QG = 2;                  // 16-row query groups per wave
-    constexpr int NGB = QG * NW;           // groups per block
-    static_assert(16 * NGB == kExtBlockRows, "attn_extend: block rows");
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int fr = lane & 15, g = lane >> 4;
-    const int s = blockIdx.y;
     const int kvh = blockIdx.z % a.nkv, seq = blockIdx.z / a.nkv;
-    const int G = a.nq / a.nkv;
     const int64_t row0 = (int64_t)seq * a.rows_per_seq;
     const int R = (int)min((int64_t)a.rows_per_seq, a.M - row0);   // a short last sequence
-    const int RG = R * G;                                         // flattened rows of this kv head
-    const int f0 = blockIdx.x * kExtBlockRows;
-    if (f0 >= RG) return;
-    // flattened row f = token f / G, head kvh * G + f % G
-    const int64_t ns = a.nsplit;
-    auto part_idx = [&](int f) { return ((row0 + f / G) * a.nq + kvh * G + f % G) * ns + s; };
-
-    // the block's last position bounds the keys any of its rows can see
-    const int kmax = __builtin_amdgcn_readfirstlane(a.pos[row0 + (min(f0 + kExtBlockRows, RG) - 1) / G]);
-    const int k0 = s * a.split_len;
-    if (k0 > kmax) {
-        // no row of the block sees this split: (-inf, 0) in every slot the combine reads (it
-        // skips the O of such a slot); splits >= 1 only, so partials exist
-        if (tid < kExtBlockRows && f0 + tid < RG) {
-            const int64_t pi = part_idx(f0 + tid);
-            a.part_ml[pi * 2] = -INFINITY;
-            a.part_ml[pi * 2 + 1] = 0.f;
-        }
-        return;
-    }
-    const int nkt = min((k0 + a.split_len) / KT, kmax / KT + 1);   // tiles [k0 / KT, nkt); past kmax: not loaded
-
-    const int64_t head_off = kv_run_off(a.km, (int64_t)a.layer * a.nkv + kvh, HD);
-    const uint16_t* kb = a.kc + head_off;
-    const uint16_t* vb = a.vc + head_off;
-
-    const int grp[QG] = {wave, NGB - 1 - wave};
-    bool gact[QG];
-    int qpos[QG], gpos[QG], gmin[QG];
-    bf16x8_t qf[QG][KSTEPS];
-#pragma unroll
-    for (int q = 0; q < QG; q++) {
-        gact[q] = f0 + 16 * grp[q] < RG;
-        const int fb = gact[q] ? f0 + 16 * grp[q] : f0;
-        const int f = min(fb + fr, RG - 1);                 // padded rows repeat the last one
-        const int t = f / G, hq = f - t * G;
-        qpos[q] = a.pos[row0 + t];
-        gpos[q] = __builtin_amdgcn_readfirstlane(gact[q] ? a.pos[row0 + min(fb + 15, RG - 1) / G] : -1);   // -1: no tile
-        // the group's first position: a key tile ending at or before it needs no causal mask
-        gmin[q] = __builtin_amdgcn_readfirstlane(a.pos[row0 + fb / G]);
-        const uint16_t* qp = a.q + (row0 + t) * (int64_t)a.nq * HD + (int64_t)(kvh * G + hq) * HD;
-#pragma unroll
-        for (int ks = 0; ks < KSTEPS; ks++) qf[q][ks] = *reinterpret_cast<const bf16x8_t*>(qp + ks * 32 + g * 8);
-    }
-
-    f32x4_t oacc[QG][DT];
-    float m_run[QG], l_run[QG];
-    attn_mfma_walk<HD, PG, NW, true>(kb, vb, a.km, seq, kmax, k0, nkt, qf, qpos, gpos, gmin, oacc, m_run, l_run);
-
-    // every real row of the block leaves its slot, also the rows this split showed no key
-    // ((-inf, 0) and a zero O): the workspace is never assumed initialised
-#pragma unroll
-    for (int q = 0; q < QG; q++) {
-        if (!gact[q]) continue;
-        const int fb = f0 + 16 * grp[q];
-        if (a.nsplit == 1) {
-            float lr[4];
-#pragma unroll
-            for (int r = 0; r < 4; r++) lr[r] = __shfl(l_run[q], g * 4 + r, 64);
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int f = fb + g * 4 + r;
-                if (f >= RG) continue;
-                uint16_t* orow = a.out + (row0 + f / G) * (int64_t)a.nq * HD + (int64_t)(kvh * G + f % G) * HD;
-#pragma unroll
-                for (int d = 0; d < DT; d++) orow[16 * d + fr] = f2bf(oacc[q][d][r] / lr[r]);
-            }
-            continue;
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int f = fb + g * 4 + r;
-            if (f >= RG) continue;
-            float* prow = a.part_o + part_idx(f) * HD;
-#pragma unroll
-            for (int d = 0; d < DT; d++) prow[16 * d + fr] = oacc[q][d][r];
-        }
-        if (g == 0 && fb + fr < RG) {   // lanes of equal fr hold the same row statistics
-            const int64_t pi = part_idx(fb + fr);
-            a.part_ml[pi * 2] = m_run[q];
-            a.part_ml[pi * 2 + 1] = l_run[q];
-        }
-    }
+    attn_extend_block<HD, PG>(a, seq, row0, R, blockIdx.x, blockIdx.y, kvh);
 }
 
 }  // namespace qie

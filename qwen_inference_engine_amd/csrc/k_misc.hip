@@ -203,8 +203,22 @@ struct QkvPostArgs {
 // nine in a row per wave at Qwen2-7B widths); the arithmetic per element is unchanged.
 constexpr int kQkvBatch = 10;
 
-template <bool PG, bool HF>
-__global__ __launch_bounds__(256) void qkv_post_kernel(QkvPostArgs a) {
+// The ragged form (qie_qkv_post_ragged): the row's sequence comes from a segment table held by
+// value in the arguments instead of m / rows_per_seq; nothing else differs.
+struct QkvPostRaggedArgs : QkvPostArgs {
+    qie_row_segs segs;
+};
+__device__ __forceinline__ int64_t qkv_row_seq(const QkvPostArgs& a, int64_t m) { return m / a.rows_per_seq; }
+__device__ __forceinline__ int64_t qkv_row_seq(const QkvPostRaggedArgs& a, int64_t m) {
+    int seq = a.segs.seq[0];   // constant indices only: the table stays in scalar registers
+#pragma unroll
+    for (int z = 1; z < QIE_RAGGED_MAX_SEGS; z++)
+        if (z < a.segs.n && m >= a.segs.row0[z]) seq = a.segs.seq[z];
+    return seq;
+}
+
+template <bool PG, bool HF, class Args = QkvPostArgs>
+__global__ __launch_bounds__(256) void qkv_post_kernel(Args a) {
 #pragma clang fp contract(off)
     const int64_t m = blockIdx.x;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -212,7 +226,7 @@ __global__ __launch_bounds__(256) void qkv_post_kernel(QkvPostArgs a) {
     const int QD = a.nq * hd, KD = a.nkv * hd;
     const int ptot = a.nq + 2 * a.nkv;
     const int p = a.pos[m];
-    const int64_t seq = m / a.rows_per_seq;
+    const int64_t seq = qkv_row_seq(a, m);
     const uint16_t* row = a.qkv + m * (int64_t)(QD + 2 * KD);
     const bool active = lane < half;
     const int i0 = HF ? lane : 2 * lane;
@@ -583,6 +597,48 @@ int kv_map_make(const qie_kv_cache* c, KvMap* out, const char* who) {
     *out = m;
     return 0;
 }
+
+bool row_segs_ok(const qie_row_segs* t, int64_t M) {
+    if (!t || t->n < 1 || t->n > QIE_RAGGED_MAX_SEGS || t->row0[0] != 0 || t->row0[t->n] != M) return false;
+    for (int z = 0; z < t->n; z++) {
+        if (t->row0[z + 1] <= t->row0[z] || t->seq[z] < 0) return false;
+        for (int y = 0; y < z; y++)
+            if (t->seq[y] == t->seq[z]) return false;
+    }
+    return true;
+}
+
+// validation, the shared fields and the launch of either form; a.rows_per_seq / a.segs are the caller's
+template <class Args>
+static int qkv_post_launch(const char* who, Args& a, const void* qkv, int64_t M, const int32_t* pos,
+                           const void* q_norm, const void* k_norm, const float* rope_cos, const float* rope_sin,
+                           int32_t n_heads, const qie_kv_cache* cache, int32_t layer, float eps, int32_t numerics,
+                           void* q_out, void* stream) {
+    QIE_REQUIRE(cache->head_dim % 2 == 0 && cache->head_dim <= 128, "%s: head_dim must be even and <= 128", who);
+    if (M == 0) return 0;
+    a.qkv = (const uint16_t*)qkv;
+    a.pos = pos;
+    a.q_norm = (const uint16_t*)q_norm;
+    a.k_norm = (const uint16_t*)k_norm;
+    a.cs = rope_cos;
+    a.sn = rope_sin;
+    a.nq = n_heads;
+    a.nkv = cache->n_kv_heads;
+    a.hd = cache->head_dim;
+    a.kc = (uint16_t*)cache->k;
+    a.vc = (uint16_t*)cache->v;
+    QIE_TRY(kv_map_make(cache, &a.km, who));
+    a.layer = layer;
+    a.eps = eps;
+    a.numerics = numerics;
+    a.q_out = (uint16_t*)q_out;
+    const bool hf = numerics == QIE_NUMERICS_HF;
+    auto fn = a.km.table ? (hf ? qkv_post_kernel<true, true, Args> : qkv_post_kernel<true, false, Args>)
+                         : (hf ? qkv_post_kernel<false, true, Args> : qkv_post_kernel<false, false, Args>);
+    hipLaunchKernelGGL(fn, dim3((unsigned)M), dim3(256), 0, (hipStream_t)stream, a);
+    QIE_LAUNCH_CHECK();
+    return 0;
+}
 }  // namespace qie
 
 extern "C" {
@@ -716,33 +772,27 @@ int qie_qkv_post(const void* qkv, int64_t M, const int32_t* pos, int32_t rows_pe
                     M >= 0 && rows_per_seq > 0 && n_heads > 0 && cache->n_kv_heads > 0 &&
                     n_heads % cache->n_kv_heads == 0 && layer >= 0 && layer < cache->n_layers,
                 "qie_qkv_post: bad arguments");
-    QIE_REQUIRE(cache->head_dim % 2 == 0 && cache->head_dim <= 128,
-                "qie_qkv_post: head_dim must be even and <= 128");
-    if (M == 0) return 0;
     QkvPostArgs a;
-    a.qkv = (const uint16_t*)qkv;
-    a.pos = pos;
     a.rows_per_seq = rows_per_seq;
-    a.q_norm = (const uint16_t*)q_norm;
-    a.k_norm = (const uint16_t*)k_norm;
-    a.cs = rope_cos;
-    a.sn = rope_sin;
-    a.nq = n_heads;
-    a.nkv = cache->n_kv_heads;
-    a.hd = cache->head_dim;
-    a.kc = (uint16_t*)cache->k;
-    a.vc = (uint16_t*)cache->v;
-    QIE_TRY(kv_map_make(cache, &a.km, "qie_qkv_post"));
-    a.layer = layer;
-    a.eps = eps;
-    a.numerics = numerics;
-    a.q_out = (uint16_t*)q_out;
-    const bool hf = numerics == QIE_NUMERICS_HF;
-    auto fn = a.km.table ? (hf ? qkv_post_kernel<true, true> : qkv_post_kernel<true, false>)
-                         : (hf ? qkv_post_kernel<false, true> : qkv_post_kernel<false, false>);
-    hipLaunchKernelGGL(fn, dim3((unsigned)M), dim3(256), 0, (hipStream_t)stream, a);
-    QIE_LAUNCH_CHECK();
-    return 0;
+    return qkv_post_launch("qie_qkv_post", a, qkv, M, pos, q_norm, k_norm, rope_cos, rope_sin, n_heads, cache, layer,
+                           eps, numerics, q_out, stream);
+}
+
+int qie_qkv_post_ragged(const void* qkv, int64_t M, const int32_t* pos, const qie_row_segs* segs,
+                        const void* q_norm, const void* k_norm, const float* rope_cos,
+                        const float* rope_sin, int32_t n_heads, const qie_kv_cache* cache, int32_t layer,
+                        float eps, int32_t numerics, void* q_out, void* stream) {
+    QIE_REQUIRE(qkv && pos && segs && cache && cache->k && cache->v && rope_cos && rope_sin && q_out &&
+                    M >= 1 && M <= INT32_MAX && n_heads > 0 && cache->n_kv_heads > 0 &&
+                    n_heads % cache->n_kv_heads == 0 && layer >= 0 && layer < cache->n_layers,
+                "qie_qkv_post_ragged: bad arguments");
+    QIE_REQUIRE(row_segs_ok(segs, M), "qie_qkv_post_ragged: malformed segment table (1 .. %d segments, row0 strictly "
+                "increasing from 0 to M = %lld, distinct sequences)", QIE_RAGGED_MAX_SEGS, (long long)M);
+    QkvPostRaggedArgs a;
+    a.rows_per_seq = 0;
+    a.segs = *segs;
+    return qkv_post_launch("qie_qkv_post_ragged", a, qkv, M, pos, q_norm, k_norm, rope_cos, rope_sin, n_heads, cache,
+                           layer, eps, numerics, q_out, stream);
 }
 
 int qie_memcpy_d2d(void* dst, const void* src, int64_t bytes, void* stream) {

@@ -11,6 +11,7 @@
 
 struct qie_kv_cache;
 struct qie_linear_args;
+struct qie_row_segs;
 
 namespace qie {
 
@@ -238,6 +239,9 @@ __device__ __forceinline__ int64_t kv_tok(const KvMap& k, int64_t seq, int tok, 
 }
 // Validated KvMap of a public cache descriptor (k_misc.hip); `who` names the caller.
 int kv_map_make(const qie_kv_cache* c, KvMap* out, const char* who);
+// A well-formed segment table of M rows (qie_ops.h, "ragged rows"): 1 .. QIE_RAGGED_MAX_SEGS
+// segments, row0 strictly increasing from 0 to M, distinct non-negative sequences (k_misc.hip)
+bool row_segs_ok(const qie_row_segs* t, int64_t M);
 
 // run-relative offset of the first element of (layer, kv head) lg
 __host__ __device__ __forceinline__ int64_t kv_run_off(const KvMap& k, int64_t lg, int hd) {

@@ -11,6 +11,8 @@
 #include <cstdint>
 #include <vector>
 
+struct qie_row_segs;
+
 namespace qie {
 
 // Every piece starts at a multiple of this (the kernels need 16 bytes; 256 is what the verify
@@ -94,9 +96,10 @@ struct LayerRows {
     float* part;                            // [M][H] fp32 partials (exchange path only)
     const int32_t* pos;                     // [M] positions on device; consecutive runs of
     int32_t rows_per_seq;                   //   rows_per_seq rows belong to one sequence
+    const qie_row_segs* segs;               // set (host table): segments of any lengths instead
 };
-inline LayerRows layer_rows(const RowBufs& r, int64_t M, int32_t rows_per_seq) {
-    return LayerRows{M, r.x, r.xn, r.qkv, r.q, r.att, r.h, r.part, r.pos, rows_per_seq};
+inline LayerRows layer_rows(const RowBufs& r, int64_t M, int32_t rows_per_seq, const qie_row_segs* segs = nullptr) {
+    return LayerRows{M, r.x, r.xn, r.qkv, r.q, r.att, r.h, r.part, r.pos, rows_per_seq, segs};
 }
 
 // What a head launch reads and writes, from row m0 of a block on (the batch's slots m0 ..; a

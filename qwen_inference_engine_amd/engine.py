@@ -417,6 +417,21 @@ class Batch:
                                               C.byref(sc), out), "qie_prefill_batch")
         return list(out)
 
+    def prefill_ragged(self, segments: Sequence[tuple], sampling: Sampling = GREEDY) -> List[int]:
+        """Prompts and appends of any lengths in one pass (qie_prefill_ragged).  segments: a list
+        of (seq, ids) or (seq, ids, pos0), slots strictly increasing; pos0 omitted or 0 starts
+        the sequence as prefill does, pos0 >= 1 extends the live sequence as append does.
+        Returns each segment's sampled token, in segment order."""
+        from .scheduler import ragged_segments
+        segs = ragged_segments(segments)
+        arr = (_lib.PrefillSegC * len(segs))(*[_lib.PrefillSegC(seq, len(ids), pos0) for seq, ids, pos0 in segs])
+        flat = [t for _, ids, _ in segs for t in ids]
+        ids_c = (C.c_int32 * len(flat))(*flat)
+        out = (C.c_int32 * len(segs))()
+        sc = sampling.to_c()
+        _lib.check(self.lib.qie_prefill_ragged(self.h, arr, len(segs), ids_c, C.byref(sc), out), "qie_prefill_ragged")
+        return list(out)
+
     def decode_step(self, sampling: Sampling = GREEDY) -> List[int]:
         out = (C.c_int32 * self.B)()
         sc = sampling.to_c()

@@ -62,6 +62,33 @@ def prefill_runs(admitted: Sequence[Request]) -> List[List[Request]]:
     return runs
 
 
+def ragged_segments(segments: Sequence[tuple]) -> List[tuple]:
+    """Batch.prefill_ragged's argument check: (seq, ids) or (seq, ids, pos0) items -> a list of
+    (seq, ids, pos0) with ids a list of ints and pos0 = 0 where omitted.  ValueError for an empty
+    list, an empty ids, a malformed item or slots that are not strictly increasing."""
+    out: List[tuple] = []
+    for item in segments:
+        if len(item) not in (2, 3):
+            raise ValueError("prefill_ragged: a segment is (seq, ids) or (seq, ids, pos0)")
+        seq, ids = int(item[0]), [int(t) for t in item[1]]
+        pos0 = int(item[2] or 0) if len(item) == 3 else 0
+        if not ids:
+            raise ValueError(f"prefill_ragged: segment of slot {seq} has no ids")
+        if out and seq <= out[-1][0]:
+            raise ValueError("prefill_ragged: slots must be strictly increasing")
+        out.append((seq, ids, pos0))
+    if not out:
+        raise ValueError("prefill_ragged: needs one or more segments")
+    return out
+
+
+def ragged_group(pieces: Sequence[tuple]) -> List[tuple]:
+    """Prompt pieces (request, offset, length) that would be prefilled back to back -> the
+    segments of the one Batch.prefill_ragged call that replaces those calls: (slot, ids, pos0) in
+    slot order; a piece at offset 0 starts its sequence, a later one extends it at its offset."""
+    return sorted(((r.slot, r.prompt[off:off + n], off) for r, off, n in pieces), key=lambda s: s[0])
+
+
 def prefill_chunks(n: int, chunk: Optional[int]) -> List[tuple]:
     """(offset, length) pieces in which a prompt of n ids is prefilled: the whole prompt when
     chunk is None, else pieces of `chunk` ids with a shorter last one.  The first piece starts
@@ -116,7 +143,13 @@ class CacheEntry:
 class ContinuousBatcher:
     def __init__(self, engine: Engine, slots: int = 8, max_ctx: Optional[int] = None, page_tokens: int = 128,
                  n_pages: int = 0, sampling: Sampling = GREEDY, keep_logits: bool = False,
-                 prefill_chunk: Optional[int] = None, keep_logprobs: bool = False, prefix_cache_pages: int = 0):
+                 prefill_chunk: Optional[int] = None, keep_logprobs: bool = False, prefix_cache_pages: int = 0,
+                 ragged_prefill: bool = False):
+        # ragged_prefill: wherever several prefill / append calls would follow each other with
+        # nothing in between (an admitted group, a flush of whole prompts, the chunks advanced in
+        # one step), ONE Batch.prefill_ragged call over the group instead — one pass over the
+        # weights.  A group of one stays the plain call.  False: exactly the calls made without it.
+        self.ragged_prefill = bool(ragged_prefill)
         # prefix_cache_pages > 0: prompts' page-aligned prefixes stay cached on shared KV pages
         # (Batch.save_prefix) and a later prompt that begins alike loads them instead of
         # prefilling them again; at most that many pages are held by the cache alone.  0: off,
@@ -241,11 +274,24 @@ class ContinuousBatcher:
         self.cache.append(CacheEntry(self.batch.save_prefix(r.slot, n), r.prompt[:n], pages, self._clock))
         self._trim_cache()
 
-    def _flush_whole(self, whole: List[Request], out: list) -> None:
-        """Prefills the admitted whole prompts without a match (grouped as prefill_runs groups
-        them), saves them and emits their first tokens in admission order."""
-        if not whole:
-            return
+    def _prefill_pieces(self, pieces: List[tuple]) -> Dict[int, int]:
+        """ragged_prefill: the (request, offset, length) pieces in one pass; returns the token
+        after each piece by request id.  One piece is the plain call."""
+        if len(pieces) == 1:
+            r, off, n = pieces[0]
+            ids = r.prompt[off:off + n]
+            if off:
+                return {r.rid: self.batch.append(r.slot, ids, off, self.sampling)}
+            return {r.rid: self.batch.prefill(r.slot, ids, self.sampling)}
+        toks = self.batch.prefill_ragged(ragged_group(pieces), self.sampling)
+        by_slot = {r.slot: r for r, _, _ in pieces}
+        return {by_slot[slot].rid: tok for slot, tok in zip(sorted(by_slot), toks)}
+
+    def _prefill_whole(self, whole: List[Request]) -> Dict[int, int]:
+        """First tokens of whole prompts by request id: one ragged pass, or the runs
+        prefill_runs groups them into."""
+        if self.ragged_prefill:
+            return self._prefill_pieces([(r, 0, len(r.prompt)) for r in whole])
         first: Dict[int, int] = {}
         for run in prefill_runs(whole):
             if len(run) == 1:
@@ -253,6 +299,14 @@ class ContinuousBatcher:
             else:
                 toks = self.batch.prefill_batch(run[0].slot, [r.prompt for r in run], self.sampling)
                 first.update((r.rid, t) for r, t in zip(run, toks))
+        return first
+
+    def _flush_whole(self, whole: List[Request], out: list) -> None:
+        """Prefills the admitted whole prompts without a match (grouped as prefill_runs groups
+        them), saves them and emits their first tokens in admission order."""
+        if not whole:
+            return
+        first = self._prefill_whole(whole)
         lg = self.batch.logits() if self.keep_logits else None
         lps = self._logprobs({r.slot: first[r.rid] for r in whole})
         for r in whole:
@@ -338,21 +392,24 @@ class ContinuousBatcher:
             admitted.append(r)
         # equal-length prompts landing in consecutive slots prefill in one pass
         # (qie_prefill_batch); tokens are emitted in admission order afterwards
+        # (ragged_prefill: the first pieces and the whole prompts in one pass)
         first: Dict[int, int] = {}
         whole: List[Request] = []
+        started: List[tuple] = []
         for r in admitted:
             pieces = prefill_chunks(len(r.prompt), self.prefill_chunk)
             if len(pieces) > 1:   # chunked: the first piece now, its token is not the request's
-                self.batch.prefill(r.slot, r.prompt[:pieces[0][1]], self.sampling)
+                if self.ragged_prefill:
+                    started.append((r, 0, pieces[0][1]))
+                else:
+                    self.batch.prefill(r.slot, r.prompt[:pieces[0][1]], self.sampling)
                 r.chunks = pieces[1:]
             else:
                 whole.append(r)
-        for run in prefill_runs(whole):
-            if len(run) == 1:
-                first[run[0].rid] = self.batch.prefill(run[0].slot, run[0].prompt, self.sampling)
-            else:
-                toks = self.batch.prefill_batch(run[0].slot, [r.prompt for r in run], self.sampling)
-                first.update((r.rid, t) for r, t in zip(run, toks))
+        if self.ragged_prefill and started:
+            first = self._prefill_pieces(started + [(r, 0, len(r.prompt)) for r in whole])
+        elif whole:
+            first = self._prefill_whole(whole)
         lg = self.batch.logits() if self.keep_logits and whole else None
         lps = self._logprobs({r.slot: first[r.rid] for r in whole})
         for r in whole:
@@ -363,11 +420,16 @@ class ContinuousBatcher:
         admitted in this step: they took their piece at admission).  pos0 is explicit: the
         decode step that ran since the last piece wrote one row at the slot's position, and this
         piece overwrites it."""
-        for r in self.slots:
-            if r is None or not r.chunks or r.rid in fresh:
-                continue
-            off, n = r.chunks.pop(0)
-            tok = self.batch.append(r.slot, r.prompt[off:off + n], off, self.sampling)
+        due = [r for r in self.slots if r is not None and r.chunks and r.rid not in fresh]
+        toks: Dict[int, int] = {}
+        if self.ragged_prefill and due:   # every piece of this step in one pass
+            toks = self._prefill_pieces([(r,) + r.chunks.pop(0) for r in due])
+        for r in due:
+            if self.ragged_prefill:
+                tok = toks[r.rid]
+            else:
+                off, n = r.chunks.pop(0)
+                tok = self.batch.append(r.slot, r.prompt[off:off + n], off, self.sampling)
             if not r.chunks:
                 if self.prefix_cache_pages > 0:
                     self._save(r)
