@@ -154,7 +154,7 @@ void qie_batch_destroy(qie_batch* b);
  * n_pages 0 = enough for every slot at max_ctx.  Pages are taken on demand by
  * qie_prefill / qie_decode* / qie_batch_set_position and returned by
  * qie_batch_release; running out of pages fails the call with nothing launched and nothing
- * changed: -28 from qie_prefill_append, qie_prefill_ragged, qie_score at pos0 >= 1, qie_verify, qie_batch_fork
+ * changed: -28 from qie_prefill_append, qie_prefill_ragged, qie_score at pos0 >= 1, qie_verify, qie_verify_batch, qie_batch_fork
  * and a qie_batch_set_position into a shared page; -22 from qie_prefill, qie_prefill_batch,
  * qie_score at pos0 = 0, qie_decode_step, qie_decode, qie_batch_reserve and a
  * qie_batch_set_position that only grows.
@@ -270,6 +270,43 @@ int qie_verify(qie_batch* b, int32_t seq, const int32_t* draft, int32_t n_draft,
 /* Logits of every row of the last qie_verify: host bf16 [n_draft + 1][V].  Works wherever
  * qie_batch_logits does (collective under tensor parallelism). */
 int qie_verify_logits(qie_batch* b, void* host_out);
+/* qie_verify for several slots in ONE weight pass.  Segment z runs the rows c_z,
+ * d1 .. dn of slot seq_z (n = n_draft_z >= 0) at positions p_z .. p_z + n; row0[z], the running
+ * sum of n_draft + 1, is its first row and M = row0[n_segs] <= QIE_VERIFY_MAX_ROWS.  draft: host,
+ * the segments' drafts laid end to end (may be NULL when there are none).  Per segment the
+ * semantics are exactly qie_verify's: the choices t_i (fused arg-max keys, or sampled with row i's
+ * counter = the slot's step counter + i; a slot's sampling entry is honoured, row i seeing that
+ * slot's history and that segment's d1 .. di), the accepted length a_z, and the slot left as after
+ * a_z + 1 decode steps — position, current token, history, step counter, the next input row, the
+ * current-position RoPE row, and qie_batch_logits row seq_z = the step's row row0[z] + a_z.
+ * out_ids (host [M]) receives segment z's t_0 .. t_a at out_ids[row0[z] ..], n_out (host [n_segs])
+ * a_z + 1 >= 1.  Slots that are not in the call are untouched, bit for bit: they do not advance.
+ * K/V rows of rejected drafts fall under the qie_batch_set_position rule.  qie_verify_logits
+ * afterwards returns the M rows in row order.  A segment's results do not depend on the other
+ * segments' ids; a call of one segment equals qie_verify of that slot bit for bit (the same M,
+ * hence the same kernels and split length).  The call synchronises once, with one device-to-host
+ * copy of every segment's {n_out, ids}.  With use_graph the step is captured once per (segment
+ * table, sampling kind, entries) in qie_verify's bounded cache and replayed.  Collective under
+ * tensor parallelism, like qie_verify.
+ * Preconditions: 1 <= n_segs <= min(B, QIE_RAGGED_MAX_SEGS), seq strictly increasing, n_draft >= 0.
+ * All-or-nothing, before anything is allocated or launched: -22 for a bad table, an idle or
+ * released slot, a draft id out of range, any segment with p + n_draft + 1 >= max_ctx, M > 16, an
+ * engine created with prefill_fp8, a batch in decode mode 1; -28 when the pool cannot hold all
+ * segments' rows together (one reservation over n_segs spans, private copies of shared pages of
+ * the write ranges included).  After either code every slot continues as if the call had not been
+ * made. */
+typedef struct qie_verify_seg { int32_t seq, n_draft; } qie_verify_seg;
+int qie_verify_batch(qie_batch* b, const qie_verify_seg* segs, int32_t n_segs, const int32_t* draft,
+                     const qie_sampling* s, int32_t* out_ids, int32_t* n_out);
+/* qie_batch_logprobs over the rows qie_verify_logits would return: out[m] (host float [rows]) =
+ * the log-probability of ids[m] (host [rows]; -1 = skip: 0.0f) under row m of the last qie_verify
+ * or qie_verify_batch (qie_logprob_rows on the step's logits; gathered under tensor parallelism:
+ * collective).  -22 when no verify step's rows are held. */
+int qie_verify_logprobs(qie_batch* b, const int32_t* ids, float* out);
+/* Diagnostics: how many verify steps (qie_verify and qie_verify_batch together) this batch has
+ * captured so far; stays 0 without use_graph.  A call that replays a captured step leaves it
+ * unchanged.  -22 for a NULL batch. */
+int qie_batch_debug_verify_captures(const qie_batch* b);
 /* One decode step for all B sequences (hipGraph replay when enabled);
  * next_ids: host [B] or NULL (then nothing is synchronised). */
 int qie_decode_step(qie_batch* b, const qie_sampling* s, int32_t* next_ids);

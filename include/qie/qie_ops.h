@@ -341,6 +341,14 @@ typedef struct qie_sample_rows_args {
 } qie_sample_rows_args;
 int64_t qie_sample_rows_workspace_bytes(int64_t M, int64_t V);
 int qie_sample_rows(const qie_sample_rows_args* a, void* stream);
+/* The mapped form (a batched verify step): qie_sample_rows under the same
+ * numerics contract, with row m's slot and tail read from device arrays instead of the stride —
+ * row m reads table[row_slot_dev[m]] and history row row_slot_dev[m], and its tail words are
+ * tail_dev[tail_off_dev[m] .. + tail_len_dev[m]).  slot0 / slot_stride are not used.
+ * row_slot_dev: device [M], every value a slot of the table; tail_off_dev: device [M], may be NULL
+ * when tail_dev is.  Same workspace, same two launches, capturable. */
+int qie_sample_rows_mapped(const qie_sample_rows_args* a, const int32_t* row_slot_dev,
+                           const int32_t* tail_off_dev, void* stream);
 
 /* ----------------------------------------------------------------- scoring
  * Per-token log-probabilities of the vocabulary head (the reference has no such path: its head,

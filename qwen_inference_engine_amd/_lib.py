@@ -107,6 +107,10 @@ class PrefillSegC(C.Structure):
     _fields_ = [("seq", C.c_int32), ("n", C.c_int32), ("pos0", C.c_int32)]
 
 
+class VerifySegC(C.Structure):
+    _fields_ = [("seq", C.c_int32), ("n_draft", C.c_int32)]
+
+
 class EngineOptsC(C.Structure):
     _fields_ = [("device", C.c_int32), ("max_ctx", C.c_int32), ("use_graph", C.c_int32),
                 ("tp_rank", C.c_int32), ("tp_size", C.c_int32), ("tp_comm", C.c_void_p),
@@ -171,6 +175,7 @@ SIGNATURES = [
     ("qie_keys_to_ids", C.c_int, [_P, _I64, _P, _P]),
     ("qie_sample_rows_workspace_bytes", C.c_int64, [_I64, _I64]),
     ("qie_sample_rows", C.c_int, [C.POINTER(SampleRowsArgsC), _P]),
+    ("qie_sample_rows_mapped", C.c_int, [C.POINTER(SampleRowsArgsC), _P, _P, _P]),
     ("qie_logprob_rows", C.c_int, [_P, _I64, _I64, _I64, _P, _P, _P, _P]),
     ("qie_score_rows_workspace_bytes", C.c_int64, [_I64, _I64]),
     ("qie_score_rows", C.c_int, [_P, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P]),
@@ -232,6 +237,9 @@ SIGNATURES = [
     ("qie_batch_logprobs", C.c_int, [_P, _PI32, _PF]),
     ("qie_verify", C.c_int, [_P, _I32, _PI32, _I32, C.POINTER(SamplingC), _PI32, _PI32]),
     ("qie_verify_logits", C.c_int, [_P, _P]),
+    ("qie_verify_batch", C.c_int, [_P, C.POINTER(VerifySegC), _I32, _PI32, C.POINTER(SamplingC), _PI32, _PI32]),
+    ("qie_verify_logprobs", C.c_int, [_P, _PI32, _PF]),
+    ("qie_batch_debug_verify_captures", C.c_int, [_P]),
     ("qie_decode_step", C.c_int, [_P, C.POINTER(SamplingC), _PI32]),
     ("qie_decode", C.c_int, [_P, _I32, C.POINTER(SamplingC), _PI32]),
     ("qie_batch_logits", C.c_int, [_P, _P]),

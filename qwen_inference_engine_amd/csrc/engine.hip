@@ -198,9 +198,18 @@ struct qie_batch {
         bool greedy;
         qie_sampling smp;
         hipGraphExec_t exec;
+        qie_row_segs segs{};   // qie_verify_batch: the table (n >= 1, and seq = -1); qie_verify: n = 0
+        bool all_entries = false;   // qie_verify_batch: EVERY segment's slot held an entry (else the
+                                    // call's sampling is captured for the rows of slots without one)
     };
+    int v_captures = 0;   // verify steps captured so far, both kinds (qie_batch_debug_verify_captures)
     std::vector<VerifyGraph> v_graphs;
-    int v_rows = 0;   // rows of the last qie_verify (what qie_verify_logits returns)
+    int v_rows = 0;   // rows of the last qie_verify / qie_verify_batch (what qie_verify_logits returns)
+    // the batched step (qie_verify_batch) runs on the same rows `v`, and its
+    // captured steps live in v_graphs under (seq = -1, rows, the segment table, sampling).
+    // vb_aux (made once by the first call): the result words [kVerifyBatchResWords], then the
+    // rows' slots, tail offsets and tail lengths [kVerifyMaxRows] each
+    int32_t* vb_aux = nullptr;
     // scoring (qie_score, qie_batch_logprobs): device targets, log-probabilities and
     // greedy ids of sc.rows rows, and the fused head's workspace; grown before any launch
     ScoreRows sc;
@@ -806,10 +815,12 @@ static qie_linear_args head_args(const qie_engine* e, const uint16_t* x, int64_t
 
 // The rows of a head launch that sample under per-slot entries: row m belongs to slot
 // slot0 + m * slot_stride and its input token sits at position q[m]; a verify step's rows carry
-// the drafts as a tail (tail_len[m] = m).
+// the drafts as a tail (tail_len[m] = m).  row_slot set (a batched verify step): row m's slot and
+// its tail's first word come from the device arrays row_slot / tail_off (qie_sample_rows_mapped).
 struct EntryRows {
     int slot0, slot_stride;
     const int32_t *q, *tail, *tail_len;
+    const int32_t *row_slot = nullptr, *tail_off = nullptr;
 };
 // does a slot of [m0, m0 + M) hold an entry?
 static bool any_entry(const qie_batch* b, int m0, int M) {
@@ -846,7 +857,8 @@ static int enqueue_head_rows(qie_batch* b, const uint16_t* x, int64_t ldx, int M
             ra.hist = b->dec.hist, ra.hist_stride = b->max_ctx;
             ra.q_dev = er->q, ra.tail_dev = er->tail, ra.tail_len_dev = er->tail_len;
             ra.step_dev = hb.step, ra.out_ids = hb.ids, ra.ws = b->rows_ws;
-            QIE_TRY(qie_sample_rows(&ra, st));
+            if (er->row_slot) QIE_TRY(qie_sample_rows_mapped(&ra, er->row_slot, er->tail_off, st));
+            else QIE_TRY(qie_sample_rows(&ra, st));
         } else {
             QIE_TRY(qie_sample(lg, M, s.vocab, s.vocab, smp, hb.step, hb.ids, hb.samp_ws, st));
         }
@@ -1765,7 +1777,7 @@ void qie_batch_destroy(qie_batch* b) {
     free_rows(b->v);
     free_rows(b->sc);
     for (void* p : {(void*)b->kc, (void*)b->vc, (void*)b->d_table, b->pk_mem, (void*)b->d_layers, b->d_attp,
-                    (void*)b->pk_ts, (void*)b->d_slots, b->rows_ws})
+                    (void*)b->pk_ts, (void*)b->d_slots, b->rows_ws, (void*)b->vb_aux})
         if (p) hipFree(p);
     // (the DevBlock workspaces free themselves)
     for (qie_kv_prefix* p : b->prefixes) delete p;   // handles still open: their pages go with the pool
@@ -2281,6 +2293,7 @@ static int launch_verify(qie_batch* b, int seq, int M, const qie_sampling* smp) 
     }
     hipGraphExec_t exec = nullptr;
     QIE_TRY(capture_graph(e, "qie_verify: ", [&] { return enqueue_verify(b, seq, M, smp); }, &exec));
+    b->v_captures++;
     b->v_graphs.push_back({seq, M, entries, greedy, smp ? *smp : qie_sampling{1, 0.f, 1.f, 0}, exec});
     QIE_HIP(hipGraphLaunch(exec, e->stream));
     return 0;
@@ -2341,6 +2354,189 @@ int qie_verify_logits(qie_batch* b, void* host_out) {
     QIE_HIP(hipStreamSynchronize(e->stream));
     QIE_TRY(comm_check(e, "qie_verify_logits"));
     QIE_HIP(d2h(e, host_out, src, (size_t)b->v_rows * e->spec.vocab * 2));
+    return 0;
+}
+
+// ------------------------------------------------------------ the batched verify step
+// the step's words beside the rows `v`: made once, never reallocated (captured steps hold them)
+static int ensure_verify_batch_bufs(qie_batch* b) {
+    QIE_TRY(ensure_verify_bufs(b));
+    if (b->vb_aux) return 0;
+    const size_t bytes = (size_t)(kVerifyBatchResWords + 3 * kVerifyMaxRows) * 4;
+    void* p = nullptr;
+    QIE_TRY(dmalloc(&p, bytes));
+    hipError_t he = hipMemsetAsync(p, 0, bytes, b->e->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(b->e->stream);
+    if (he != hipSuccess) {
+        hipFree(p);
+        return fail((int)he, "qie_verify_batch: buffer init: %s", hipGetErrorString(he));
+    }
+    b->vb_aux = (int32_t*)p;
+    return 0;
+}
+
+static bool any_entry_segs(const qie_batch* b, const qie_row_segs& t) {
+    if (b->n_slot_set == 0) return false;
+    for (int z = 0; z < t.n; z++)
+        if (b->slot_set[t.seq[z]]) return true;
+    return false;
+}
+
+// enqueue_verify over segments: rows -> the decode-form layers in their ragged forms -> one head
+// over all M rows -> commit per segment; a linear chain on device state, capturable
+static int enqueue_verify_batch(qie_batch* b, const qie_row_segs& t, const qie_sampling* smp) {
+    qie_engine* e = b->e;
+    const qie_model_spec& s = e->spec;
+    hipStream_t st = e->stream;
+    const int64_t H8 = (int64_t)s.hidden / 8;
+    const int M = t.row0[t.n];
+    int32_t* res = b->vb_aux;
+    int32_t *row_slot = res + kVerifyBatchResWords, *tail_off = row_slot + kVerifyMaxRows,
+            *tail_len = tail_off + kVerifyMaxRows;
+    VerifyBatchRowsArgs ra{t, b->v.draft, s.vocab, (const uint4*)e->w.embed, (const uint4*)b->dec.x, H8, b->dec.pos,
+                           b->dec.step, (uint4*)b->v.x, b->v.pos, b->v.step, row_slot, tail_off, tail_len};
+    QIE_TRY(launch_verify_batch_rows(ra, st));
+    const qie_kv_cache cache = batch_cache(b, 0);   // the table names the batch's slots
+    const LayerRows r = layer_rows(b->v, M, 0, &t);
+    for (int l = 0; l < s.n_layers; l++)
+        QIE_TRY(enqueue_layer_rows(b, l, r, decode_path(e), cache, nullptr, b->v.attn_ws));
+    // with an entry: row i of a segment sees its slot's history [.. p] and then that segment's d1 .. di
+    EntryRows er{0, 0, b->v.pos, b->v.draft, tail_len};
+    er.row_slot = row_slot, er.tail_off = tail_off;
+    const bool entries = any_entry_segs(b, t);
+    QIE_TRY(enqueue_head_rows(b, b->v.x, s.hidden, M, smp, head_bufs(b->v, 0, e->sh.vocab), entries ? &er : nullptr));
+    const bool greedy = !entries && is_greedy(smp);
+    VerifyBatchCommitArgs ca{t, greedy ? b->v.keys : nullptr, b->v.ids, b->v.draft, s.vocab, b->dec.pos, b->dec.step,
+                             b->dec.hist, b->max_ctx, b->dec.ids, (const uint4*)e->w.embed, (uint4*)b->dec.x, H8,
+                             rope_cur_args(b), b->v.logits, b->dec.logits, (int64_t)e->sh.vocab, res};
+    return launch_verify_batch_commit(ca, st);
+}
+
+static bool every_entry_segs(const qie_batch* b, const qie_row_segs& t) {
+    for (int z = 0; z < t.n; z++)
+        if (!b->slot_set[t.seq[z]]) return false;
+    return true;
+}
+
+static bool same_segs(const qie_row_segs& a, const qie_row_segs& b) {
+    if (a.n != b.n) return false;
+    for (int z = 0; z < a.n; z++)
+        if (a.seq[z] != b.seq[z] || a.row0[z + 1] != b.row0[z + 1]) return false;
+    return true;
+}
+
+// eager, or the captured step of (segment table, sampling kind, entries) in v_graphs (launch_verify's
+// cache and bound; seq = -1 keeps the two kinds apart).  The call's sampling is part of the step
+// unless EVERY segment's slot holds an entry: rows of a slot without one sample under it
+// (qie_sample_rows' fallback, a by-value launch argument), as the decode graph's do.
+static int launch_verify_batch(qie_batch* b, const qie_row_segs& t, const qie_sampling* smp) {
+    qie_engine* e = b->e;
+    if (!e->opts.use_graph) return enqueue_verify_batch(b, t, smp);
+    const bool greedy = is_greedy(smp), entries = any_entry_segs(b, t), all = entries && every_entry_segs(b, t);
+    for (const auto& g : b->v_graphs)
+        if (g.seq == -1 && same_segs(g.segs, t) && g.entries == entries && g.all_entries == all &&
+            (all || (g.greedy == greedy && (greedy || same_sampling(g.smp, smp))))) {
+            QIE_HIP(hipGraphLaunch(g.exec, e->stream));
+            return 0;
+        }
+    if (b->v_graphs.size() >= 64) {   // bounded: drop the oldest captured step
+        hipGraphExecDestroy(b->v_graphs.front().exec);
+        b->v_graphs.erase(b->v_graphs.begin());
+    }
+    hipGraphExec_t exec = nullptr;
+    QIE_TRY(capture_graph(e, "qie_verify_batch: ", [&] { return enqueue_verify_batch(b, t, smp); }, &exec));
+    b->v_graphs.push_back({-1, t.row0[t.n], entries, greedy, smp ? *smp : qie_sampling{1, 0.f, 1.f, 0}, exec, t, all});
+    b->v_captures++;
+    QIE_HIP(hipGraphLaunch(exec, e->stream));
+    return 0;
+}
+
+int qie_verify_batch(qie_batch* b, const qie_verify_seg* segs, int32_t n_segs, const int32_t* draft,
+                     const qie_sampling* smp, int32_t* out_ids, int32_t* n_out) {
+    const char* who = "qie_verify_batch";
+    QIE_REQUIRE(b && segs && out_ids && n_out && n_segs >= 1 && n_segs <= b->B && n_segs <= QIE_RAGGED_MAX_SEGS,
+                "%s: bad arguments (1 .. min(B, %d) segments)", who, QIE_RAGGED_MAX_SEGS);
+    qie_engine* e = b->e;
+    const qie_model_spec& s = e->spec;
+    QIE_REQUIRE(!(e->fp8 && e->opts.prefill_fp8),
+                "%s: not available on a prefill_fp8 engine (block-scaled fp8 activations are defined for a "
+                "prefill from position 0 only)", who);
+    QIE_REQUIRE(b->decode_mode == 0, "%s: the batch is in decode mode 1 (the persistent step); verify runs "
+                                     "the five-launch layer, set mode 0 first", who);
+    qie_row_segs t{};
+    PagePool::Span spans[kMaxBatchSlots];   // n_segs <= B <= kMaxBatchSlots
+    int M = 0;
+    for (int z = 0; z < n_segs; z++) {
+        const qie_verify_seg& g = segs[z];
+        QIE_REQUIRE(g.seq >= 0 && g.seq < b->B && g.n_draft >= 0 && (z == 0 || g.seq > segs[z - 1].seq),
+                    "%s: segment %d: bad arguments (slots strictly increasing, n_draft >= 0)", who, z);
+        QIE_REQUIRE(!b->idle[g.seq], "%s: slot %d holds no live sequence", who, g.seq);
+        QIE_REQUIRE(g.n_draft < QIE_VERIFY_MAX_ROWS && M + g.n_draft + 1 <= QIE_VERIFY_MAX_ROWS,
+                    "%s: the segments' rows (a current token and the drafts each) exceed the %d rows of a step", who,
+                    QIE_VERIFY_MAX_ROWS);
+        const int p = b->h_pos[g.seq];
+        QIE_REQUIRE((int64_t)p + g.n_draft + 1 < b->max_ctx, "%s: %d rows of slot %d from position %d do not fit max_ctx %d",
+                    who, g.n_draft + 1, g.seq, p, b->max_ctx);
+        t.row0[z] = M, t.seq[z] = g.seq;
+        spans[z] = PagePool::Span{g.seq, p, (int64_t)p + g.n_draft, false};
+        M += g.n_draft + 1;
+    }
+    t.n = n_segs;
+    for (int z = n_segs; z <= QIE_RAGGED_MAX_SEGS; z++) t.row0[z] = M;
+    const int n_drafts = M - n_segs;
+    QIE_REQUIRE(n_drafts == 0 || draft, "%s: bad arguments (drafts without ids)", who);
+    for (int i = 0; i < n_drafts; i++)
+        QIE_REQUIRE(draft[i] >= 0 && draft[i] < s.vocab, "%s: draft id %d out of range", who, draft[i]);
+    // all-or-nothing, before anything is allocated or launched: one reservation over every segment
+    // (growth + a private copy of every shared page of the write ranges)
+    KvWrites kv;
+    QIE_TRY(plan_kv_writes(b, spans, n_segs, kv));
+    if (!kv.fits())
+        return fail(-28, "%s: KV pool exhausted (%lld more pages needed for %d rows in %d segments, %lld free)", who,
+                    (long long)kv.r.need, M, n_segs, (long long)kv.free);
+    QIE_TRY(ensure_verify_batch_bufs(b));
+    QIE_TRY(commit_kv_writes(b, kv));
+    hipStream_t st = e->stream;
+    if (n_drafts > 0) QIE_HIP(hipMemcpyAsync(b->v.draft, draft, (size_t)n_drafts * 4, hipMemcpyHostToDevice, st));
+    QIE_TRY(launch_verify_batch(b, t, smp));
+    // every segment's accepted count and ids (and the exchange error word) in one stream-ordered batch
+    int32_t res[kVerifyBatchResWords] = {0};
+    QIE_TRY(read_back(b, res, b->vb_aux, (size_t)(kVerifyMaxSegs + M) * 4, who));
+    for (int z = 0; z < n_segs; z++)
+        if (res[z] < 1 || res[z] > segs[z].n_draft + 1)
+            return fail(-5, "%s: the step reported %d accepted rows of %d in segment %d", who, res[z],
+                        segs[z].n_draft + 1, z);
+    for (int z = 0; z < n_segs; z++) {
+        for (int i = 0; i < res[z]; i++) out_ids[t.row0[z] + i] = res[kVerifyMaxSegs + t.row0[z] + i];
+        n_out[z] = res[z];
+        b->h_pos[segs[z].seq] += res[z];
+    }
+    b->v_rows = M;
+    return 0;
+}
+
+int qie_batch_debug_verify_captures(const qie_batch* b) { return b ? b->v_captures : -22; }
+
+int qie_verify_logprobs(qie_batch* b, const int32_t* ids, float* out) {
+    QIE_REQUIRE(b && ids && out, "qie_verify_logprobs: bad arguments");
+    QIE_REQUIRE(b->v.mem && b->v_rows > 0, "qie_verify_logprobs: no qie_verify or qie_verify_batch has run on this batch");
+    qie_engine* e = b->e;
+    const int64_t V = e->spec.vocab;
+    const int rows = b->v_rows;
+    for (int m = 0; m < rows; m++)
+        QIE_REQUIRE(ids[m] >= -1 && ids[m] < V, "qie_verify_logprobs: id %d of row %d is neither -1 nor a token id",
+                    ids[m], m);
+    QIE_TRY(ensure_score_scratch(b, rows, false));
+    const uint16_t* src = b->v.logits;
+    if (use_comm(e)) {   // collective: every rank calls this at the same point
+        QIE_TRY(gather_rows(b, head_bufs(b->v, 0, e->sh.vocab), rows));
+        src = b->v.logits_full;
+    }
+    QIE_HIP(hipMemcpyAsync(b->sc.tgt, ids, (size_t)rows * 4, hipMemcpyHostToDevice, e->stream));
+    QIE_TRY(qie_logprob_rows(src, rows, V, V, b->sc.tgt, b->sc.lp, nullptr, e->stream));
+    QIE_HIP(hipStreamSynchronize(e->stream));
+    QIE_TRY(comm_check(e, "qie_verify_logprobs"));
+    QIE_HIP(d2h(e, out, b->sc.lp, (size_t)rows * 4));
     return 0;
 }
 

@@ -195,7 +195,21 @@ struct RowsArgs {
     int32_t* ids;
     unsigned long long* cand;   // [M][nb][kMaxTopK] (a row's slices packed at its own k)
     int nb;
+    // qie_sample_rows_mapped (the MAPPED kernels only): row m's slot and where its tail begins
+    const int32_t *row_slot, *tail_off;
 };
+// Row m's slot, and its tail's first word.  MAPPED is a template parameter of the two kernels, so
+// the strided form's code is what it was before the mapped form existed.
+template <bool MAPPED>
+__device__ __forceinline__ int row_slot_of(const RowsArgs& a, int64_t m) {
+    if (MAPPED) return a.row_slot[m];
+    return a.slot0 + (int)m * a.slot_stride;
+}
+template <bool MAPPED>
+__device__ __forceinline__ const int32_t* row_tail_of(const RowsArgs& a, int64_t m) {
+    if (MAPPED) return a.tail ? a.tail + a.tail_off[m] : nullptr;
+    return a.tail;
+}
 
 __device__ __forceinline__ RowParams row_params(const qie_slot_sampling* e, const qie_sampling& fb, int64_t V) {
     RowParams p;
@@ -237,6 +251,7 @@ __device__ __forceinline__ unsigned long long block_max_key(unsigned long long b
 // Block (slice, row): counts the window's ids that fall in its 4096-id slice (integer LDS
 // atomics: order-independent), builds the keys of the processed bf16 values, and leaves the
 // slice's k best (sorted; greedy: its one maximum) in cand.
+template <bool MAPPED>
 __global__ __launch_bounds__(256) void rows_slice_kernel(RowsArgs a) {
 #pragma clang fp contract(off)
     __shared__ unsigned long long keys[kSlice];
@@ -244,7 +259,7 @@ __global__ __launch_bounds__(256) void rows_slice_kernel(RowsArgs a) {
     __shared__ unsigned long long red[4];
     const int64_t m = blockIdx.y;
     const int64_t base = (int64_t)blockIdx.x * kSlice;
-    const int slot = a.slot0 + (int)m * a.slot_stride;
+    const int slot = row_slot_of<MAPPED>(a, m);
     const qie_slot_sampling* e = a.table + slot;
     const RowParams p = row_params(e, a.fb, a.V);
     const uint16_t* row = a.logits + m * a.ld;
@@ -252,7 +267,8 @@ __global__ __launch_bounds__(256) void rows_slice_kernel(RowsArgs a) {
         for (int i = threadIdx.x; i < kSlice; i += 256) cnt[i] = 0;
         __syncthreads();
         const int64_t q = a.q[m];
-        int64_t tl = a.tail && a.tail_len ? a.tail_len[m] : 0;
+        const int32_t* tail = row_tail_of<MAPPED>(a, m);
+        int64_t tl = tail && a.tail_len ? a.tail_len[m] : 0;
         tl = tl < 0 ? 0 : (tl > kMaxTail ? kMaxTail : tl);
         int64_t lo = p.last_n > 0 ? q + 1 - p.last_n : 0;
         lo = lo > p.start ? lo : p.start;
@@ -266,7 +282,7 @@ __global__ __launch_bounds__(256) void rows_slice_kernel(RowsArgs a) {
         // tail word t sits at position q - tl + 1 + t
         const int64_t t0 = lo - (q - tl + 1);
         for (int64_t t = (t0 > 0 ? t0 : 0) + threadIdx.x; t < tl; t += 256) {
-            const int64_t d = (int64_t)a.tail[t] - base;
+            const int64_t d = (int64_t)tail[t] - base;
             if (d >= 0 && d < kSlice && base + d < a.V) atomicAdd(&cnt[d], 1);
         }
         __syncthreads();
@@ -311,10 +327,11 @@ __global__ __launch_bounds__(256) void rows_slice_kernel(RowsArgs a) {
 
 // Block m: merges row m's nb * k slice winners and draws under the row's own parameters.
 // Dynamic LDS is sized for k = kMaxTopK; the sort runs over the row's own count.
+template <bool MAPPED>
 __global__ __launch_bounds__(256) void rows_merge_sample_kernel(RowsArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long sk[];   // all of the kernel's LDS (up to 160 KiB)
     const int64_t m = blockIdx.x;
-    const int slot = a.slot0 + (int)m * a.slot_stride;
+    const int slot = row_slot_of<MAPPED>(a, m);
     const RowParams p = row_params(a.table + slot, a.fb, a.V);
     const unsigned long long* cand = a.cand + m * a.nb * kMaxTopK;
     const int total = a.nb * p.k;
@@ -398,14 +415,19 @@ int64_t qie_sample_rows_workspace_bytes(int64_t M, int64_t V) {
     return M * nb * kMaxTopK * 8 + 64;
 }
 
-int qie_sample_rows(const qie_sample_rows_args* a, void* stream) {
+}  // extern "C"
+
+// qie_sample_rows and its mapped form: the same two launches, MAPPED reading row_slot / tail_off
+template <bool MAPPED>
+static int sample_rows(const qie_sample_rows_args* a, const int32_t* row_slot, const int32_t* tail_off, void* stream,
+                       const char* who) {
     QIE_REQUIRE(a && a->logits && a->table && a->hist && a->q_dev && a->out_ids && a->ws && a->M >= 0 && a->V > 0 &&
                     a->ld >= a->V && a->hist_stride > 0 && a->slot0 >= 0 && a->slot_stride >= 0,
-                "qie_sample_rows: bad arguments");
+                "%s: bad arguments", who);
     const int64_t V = a->V;
     const int nb = (int)((V + kSlice - 1) / kSlice);
     // the merge sorts up to nb * 256 keys in LDS
-    QIE_REQUIRE(nb <= 64, "qie_sample_rows: V %lld exceeds %d ids", (long long)V, 64 * kSlice);
+    QIE_REQUIRE(nb <= 64, "%s: V %lld exceeds %d ids", who, (long long)V, 64 * kSlice);
     if (a->M == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     RowsArgs r{};
@@ -415,13 +437,26 @@ int qie_sample_rows(const qie_sample_rows_args* a, void* stream) {
     r.hist = a->hist, r.hist_stride = a->hist_stride;
     r.q = a->q_dev, r.tail = a->tail_dev, r.tail_len = a->tail_len_dev, r.step = a->step_dev;
     r.ids = a->out_ids, r.cand = (unsigned long long*)a->ws, r.nb = nb;
-    hipLaunchKernelGGL(rows_slice_kernel, dim3(nb, (unsigned)a->M), dim3(256), 0, st, r);
+    r.row_slot = row_slot, r.tail_off = tail_off;
+    hipLaunchKernelGGL(rows_slice_kernel<MAPPED>, dim3(nb, (unsigned)a->M), dim3(256), 0, st, r);
     QIE_LAUNCH_CHECK();
     const size_t shm = (size_t)std::max(4, pow2_at_least(nb * (int)std::min<int64_t>(kMaxTopK, V))) * 8;
-    if (shm > 65536) QIE_TRY(raise_dynamic_lds((const void*)rows_merge_sample_kernel, 160 * 1024));
-    hipLaunchKernelGGL(rows_merge_sample_kernel, dim3((unsigned)a->M), dim3(256), shm, st, r);
+    if (shm > 65536) QIE_TRY(raise_dynamic_lds((const void*)rows_merge_sample_kernel<MAPPED>, 160 * 1024));
+    hipLaunchKernelGGL(rows_merge_sample_kernel<MAPPED>, dim3((unsigned)a->M), dim3(256), shm, st, r);
     QIE_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" {
+
+int qie_sample_rows(const qie_sample_rows_args* a, void* stream) {
+    return sample_rows<false>(a, nullptr, nullptr, stream, "qie_sample_rows");
+}
+
+int qie_sample_rows_mapped(const qie_sample_rows_args* a, const int32_t* row_slot_dev, const int32_t* tail_off_dev,
+                           void* stream) {
+    QIE_REQUIRE(row_slot_dev && (tail_off_dev || !(a && a->tail_dev)), "qie_sample_rows_mapped: bad arguments");
+    return sample_rows<true>(a, row_slot_dev, tail_off_dev, stream, "qie_sample_rows_mapped");
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 #pragma once
 
 #include "qie_common.hpp"
+#include "../../include/qie/qie_ops.h"
 
 namespace qie {
 
@@ -46,7 +47,55 @@ struct VerifyCommitArgs {
     int32_t* res;               // [1 + M]: n_out, then the M chosen ids
 };
 
+// ---- the batched step (qie_verify_batch): the rows are segments, segment z the
+// rows c, d1 .. dn of slot seq[z].  The table travels by value (the ragged layer's qie_row_segs);
+// the drafts lie end to end, so segment z's begin at draft[row0[z] - z].
+constexpr int kVerifyMaxSegs = QIE_RAGGED_MAX_SEGS;
+
+// The batched step's result words: [z] = n_out of segment z, [kVerifyMaxSegs + m] = row m's id
+constexpr int kVerifyBatchResWords = kVerifyMaxSegs + kVerifyMaxRows;
+
+struct VerifyBatchRowsArgs {
+    qie_row_segs segs;      // entries past n repeat M (as the ragged layer takes it)
+    const int32_t* draft;   // [M - n] the segments' drafts end to end (device)
+    int32_t vocab;
+    const uint4* E;
+    const uint4* x_res;     // [B][H8]
+    int64_t H8;
+    const int32_t* pos;     // [B]
+    const int32_t* step;    // [B]
+    uint4* vx;              // [M][H8]
+    int32_t* vpos;          // [M] = pos[seq] + i (i: the row's index within its segment)
+    int32_t* vstep;         // [M] = step[seq] + i
+    int32_t* row_slot;      // [M] = seq: the slot whose entry and history the row samples under
+    int32_t* tail_off;      // [M] = row0[z] - z: where the row's segment begins in draft
+    int32_t* tail_len;      // [M] = i: the drafts d1 .. di before the row
+};
+
+struct VerifyBatchCommitArgs {
+    qie_row_segs segs;
+    unsigned long long* keys;   // greedy: [M] fused arg-max keys (left zero), else null
+    const int32_t* ids;         // sampled: [M]
+    const int32_t* draft;       // [M - n]
+    int32_t vocab;
+    int32_t* pos;
+    int32_t* step;
+    int32_t* hist;
+    int hist_stride;
+    int32_t* ids_out;
+    const uint4* E;
+    uint4* x_res;
+    int64_t H8;
+    RopeCurArgs rca;
+    const uint16_t* vlogits;    // [M][Vl]
+    uint16_t* logits;           // [B][Vl]
+    int64_t Vl;
+    int32_t* res;               // [kVerifyBatchResWords]
+};
+
 int launch_verify_rows(const VerifyRowsArgs& a, hipStream_t st);
 int launch_verify_commit(const VerifyCommitArgs& a, hipStream_t st);
+int launch_verify_batch_rows(const VerifyBatchRowsArgs& a, hipStream_t st);
+int launch_verify_batch_commit(const VerifyBatchCommitArgs& a, hipStream_t st);
 
 }  // namespace qie

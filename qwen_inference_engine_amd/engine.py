@@ -285,6 +285,20 @@ class Prefix:
         self.h = None
 
 
+def verify_segments(items: Sequence[tuple]) -> List[tuple]:
+    """Batch.verify_batch's argument shape: (seq, draft) items -> a list of (seq, [ids]).
+    ValueError for an empty list or a malformed item; the table itself (slot order, row count, id
+    range) is checked by the engine, all-or-nothing."""
+    out: List[tuple] = []
+    for item in items:
+        if len(item) != 2:
+            raise ValueError("verify_batch: a segment is (seq, draft)")
+        out.append((int(item[0]), [int(t) for t in item[1]]))
+    if not out:
+        raise ValueError("verify_batch: needs one or more segments")
+    return out
+
+
 class Batch:
     def __init__(self, engine: Engine, batch: int, max_ctx: int, page_tokens: Optional[int] = None,
                  n_pages: int = 0):
@@ -460,9 +474,52 @@ class Batch:
         self._verify_rows = n + 1
         return [int(t) for t in out[:n_out.value]]
 
+    def verify_batch(self, items: Sequence[tuple], sampling: Sampling = GREEDY) -> List[List[int]]:
+        """verify() for several slots in one pass over the weights (qie_verify_batch).  items: a
+        list of (seq, draft), slots strictly increasing, every slot with its current token and
+        its drafts, at most 16 rows together.  Returns each segment's tokens t_0 .. t_a in item
+        order; every slot of the call is then exactly as after len(its result) decode steps,
+        every other slot untouched.  verify_logits() returns the rows in item order."""
+        segs = verify_segments(items)
+        arr = (_lib.VerifySegC * len(segs))(*[_lib.VerifySegC(seq, len(d)) for seq, d in segs])
+        flat = [t for _, d in segs for t in d]
+        rows = len(flat) + len(segs)
+        draft = (C.c_int32 * max(len(flat), 1))(*flat)
+        out = (C.c_int32 * rows)()
+        n_out = (C.c_int32 * len(segs))()
+        sc = sampling.to_c()
+        _lib.check(self.lib.qie_verify_batch(self.h, arr, len(segs), draft, C.byref(sc), out, n_out),
+                   "qie_verify_batch")
+        self._verify_rows = rows
+        res, r0 = [], 0
+        for z, (_, d) in enumerate(segs):
+            res.append([int(t) for t in out[r0:r0 + n_out[z]]])
+            r0 += len(d) + 1
+        return res
+
+    def verify_captures(self) -> int:
+        """Verify steps (verify and verify_batch together) this batch has captured so far
+        (diagnostics: a replayed step leaves the count unchanged; 0 without use_graph)."""
+        return int(self.lib.qie_batch_debug_verify_captures(self.h))
+
+    def verify_logprobs(self, ids: Sequence[int]) -> np.ndarray:
+        """Log-probability of ids[m] (-1: skip, 0.0) under row m of the last verify() or
+        verify_batch() (the rows verify_logits() returns), float32 [rows]."""
+        rows = getattr(self, "_verify_rows", 0)
+        if rows <= 0:
+            raise _lib.QieError("verify_logprobs: no verify() has run on this batch")
+        if len(ids) != rows:
+            raise ValueError(f"verify_logprobs: one id per row ({rows})")
+        arr = (C.c_int32 * rows)(*[int(i) for i in ids])
+        out = np.zeros(rows, dtype=np.float32)
+        _lib.check(self.lib.qie_verify_logprobs(self.h, arr, out.ctypes.data_as(C.POINTER(C.c_float))),
+                   "qie_verify_logprobs")
+        return out
+
     def verify_logits(self) -> np.ndarray:
         """bf16 logits [len(draft) + 1][V] of every row of the last verify() (row i scored
-        the token after the current token + i drafts)."""
+        the token after the current token + i drafts); after verify_batch() the rows of all
+        segments in item order."""
         rows = getattr(self, "_verify_rows", 0)
         if rows <= 0:
             raise _lib.QieError("verify_logits: no verify() has run on this batch")

@@ -22,6 +22,11 @@ prefix load — and clears it when the request finishes; a request without one s
 batcher's ``sampling`` (``qie_sampling``, per step).  ``penalize_prompt=False`` starts the
 penalty window behind the prompt.  Slot rows are independent, so a request's tokens do not
 depend on what the other slots hold.
+
+With ``drafter`` the step speculates for the whole batch: every emitting slot
+proposes up to ``draft_tokens`` ids and one ``Batch.verify_batch`` call — up to 8 slots and 16
+rows, dealt by ``deal_verify_rows`` — takes the decode step's place; a step without any draft is
+the plain decode step.
 """
 from __future__ import annotations
 
@@ -89,6 +94,45 @@ def ragged_group(pieces: Sequence[tuple]) -> List[tuple]:
     return sorted(((r.slot, r.prompt[off:off + n], off) for r, off, n in pieces), key=lambda s: s[0])
 
 
+VERIFY_MAX_ROWS = 16   # QIE_VERIFY_MAX_ROWS: rows of one verify step
+VERIFY_MAX_SEGS = 8    # QIE_RAGGED_MAX_SEGS: slots of one verify step
+
+
+def draft_cap(draft_tokens: int, max_new_tokens: int, emitted: int, pos: int, max_ctx: int) -> int:
+    """How many drafts a slot may propose: min(draft_tokens, max_new_tokens - emitted - 1, context
+    room), never negative.  A verify step of k drafts emits at most k + 1 tokens and writes K/V
+    rows pos .. pos + k, so the request never over-emits and its writes stay inside the pages
+    promised at admission (prompt + max_new_tokens); room: pos + k + 1 < max_ctx."""
+    return max(0, min(int(draft_tokens), max_new_tokens - emitted - 1, max_ctx - pos - 2))
+
+
+def deal_verify_rows(proposed: Sequence[tuple], max_rows: int = VERIFY_MAX_ROWS,
+                     max_segs: int = VERIFY_MAX_SEGS) -> List[tuple]:
+    """The table of one batcher step's Batch.verify_batch call.  proposed: (slot, ids) of every
+    slot that emits this step, in slot order, ids already capped (draft_cap); at most max_segs of
+    them (a batch has no more slots: ValueError).  Returns a list of (slot, draft): every slot has
+    its one row, and the max_rows - (segments) spare rows are dealt one at a time in slot order,
+    round-robin, among the slots that still have proposed ids left.  [] when no slot proposed
+    anything: the step is then the plain decode step."""
+    group = list(proposed)
+    if len(group) > max_segs:
+        raise ValueError(f"deal_verify_rows: {len(group)} slots, a verify step takes {max_segs}")
+    if not any(ids for _, ids in group):
+        return []
+    take = [0] * len(group)
+    spare = max_rows - len(group)
+    while spare > 0:
+        dealt = False
+        for i, (_, ids) in enumerate(group):
+            if spare > 0 and take[i] < len(ids):
+                take[i] += 1
+                spare -= 1
+                dealt = True
+        if not dealt:
+            break
+    return [(slot, list(ids[:take[i]])) for i, (slot, ids) in enumerate(group)]
+
+
 def prefill_chunks(n: int, chunk: Optional[int]) -> List[tuple]:
     """(offset, length) pieces in which a prompt of n ids is prefilled: the whole prompt when
     chunk is None, else pieces of `chunk` ids with a shorter last one.  The first piece starts
@@ -144,7 +188,25 @@ class ContinuousBatcher:
     def __init__(self, engine: Engine, slots: int = 8, max_ctx: Optional[int] = None, page_tokens: int = 128,
                  n_pages: int = 0, sampling: Sampling = GREEDY, keep_logits: bool = False,
                  prefill_chunk: Optional[int] = None, keep_logprobs: bool = False, prefix_cache_pages: int = 0,
-                 ragged_prefill: bool = False):
+                 ragged_prefill: bool = False, drafter=None, draft_tokens: int = 4):
+        # drafter: speculative decoding for the whole batch.  An object with
+        # propose(history, k) (NgramDrafter) shared by all requests, or — for drafters that keep
+        # state — a factory called once per request.  Each step every emitting slot proposes up
+        # to draft_tokens ids (draft_cap) and ONE Batch.verify_batch call (deal_verify_rows)
+        # replaces the decode step; a step in which no slot proposes anything is the plain decode
+        # step.  None: exactly the calls made without it.  Greedy streams are token for token
+        # those of plain decode steps from the same logits.  On a use_graph engine a step is
+        # captured per table (which slots, how many drafts each): a table the bounded cache has
+        # not seen pays a capture first ("first call": 0.5 - 0.9 ms on
+        # Qwen2-7B; the hit rate of a real request mix has not been measured).
+        self.drafter = drafter
+        self.draft_tokens = int(draft_tokens)
+        if drafter is not None and not 0 <= self.draft_tokens <= VERIFY_MAX_ROWS - 1:
+            raise ValueError(f"draft_tokens must be in [0, {VERIFY_MAX_ROWS - 1}]")
+        self._drafters: Dict[int, object] = {}   # per request, when `drafter` is a factory
+        # verify_calls, drafted (ids handed to verify_batch), accepted (drafts the model agreed
+        # with), emitted (every token the batcher emitted, on any path)
+        self.stats: Dict[str, int] = dict(verify_calls=0, drafted=0, accepted=0, emitted=0)
         # ragged_prefill: wherever several prefill / append calls would follow each other with
         # nothing in between (an admitted group, a flush of whole prompts, the chunks advanced in
         # one step), ONE Batch.prefill_ragged call over the group instead — one pass over the
@@ -202,6 +264,7 @@ class ContinuousBatcher:
 
     def _finish(self, r: Request) -> None:
         r.done = True
+        self._drafters.pop(r.rid, None)
         if r.sampling is not None:
             self.batch.set_sampling(r.slot, None)
         self.batch.release(r.slot)
@@ -219,12 +282,23 @@ class ContinuousBatcher:
         return self.batch.logprobs([toks.get(i, -1) for i in range(len(self.slots))])
 
     def _emit(self, r: Request, tok: int, out: list, logits=None, lps=None) -> None:
+        row = lp = None
+        if self.keep_logits:
+            row = (self.batch.logits() if logits is None else logits)[r.slot]
+        if self.keep_logprobs:
+            lp = (self._logprobs({r.slot: tok}) if lps is None else lps)[r.slot]
+        self._emit_row(r, tok, out, row, lp)
+
+    def _emit_row(self, r: Request, tok: int, out: list, row, lp) -> None:
+        """The token with its logits row / log-probability (None where not kept); a stop id or
+        the token budget ends the request at this token."""
         r.tokens.append(tok)
         if self.keep_logits:
-            r.logits.append((self.batch.logits() if logits is None else logits)[r.slot].copy())
+            r.logits.append(row.copy())
         if self.keep_logprobs:
-            r.logprobs.append(float((self._logprobs({r.slot: tok}) if lps is None else lps)[r.slot]))
+            r.logprobs.append(float(lp))
         out.append((r.rid, tok))
+        self.stats["emitted"] += 1
         if len(r.tokens) >= r.max_new_tokens or tok in r.stop_ids:
             self._finish(r)
 
@@ -435,14 +509,67 @@ class ContinuousBatcher:
                     self._save(r)
                 self._emit(r, tok, out)
 
+    def _propose(self, r: Request) -> List[int]:
+        """The request's capped proposal for this step (ids the model lacks cut it short)."""
+        pos = len(r.prompt) + len(r.tokens) - 1   # the pending token's position
+        k = draft_cap(self.draft_tokens, r.max_new_tokens, len(r.tokens), pos, self.max_ctx)
+        if k <= 0:
+            return []
+        d = self.drafter
+        if isinstance(d, type) or not hasattr(d, "propose"):   # a factory (a class is one): one drafter per request
+            d = self._drafters.get(r.rid)
+            if d is None:
+                d = self._drafters[r.rid] = self.drafter()
+        vocab = self.batch.e.spec.vocab
+        ids: List[int] = []
+        for t in list(d.propose(r.prompt + r.tokens, k))[:k]:
+            if not 0 <= int(t) < vocab:
+                break
+            ids.append(int(t))
+        return ids
+
+    def _verify_step(self, out: list) -> bool:
+        """The step's tokens through Batch.verify_batch when some slot has a draft (False: none
+        has, the caller runs the plain decode step).  Slots in chunked prefill are not in the
+        table and do not advance.  Tokens are emitted in slot order, each slot's in order; a
+        request that ends inside its accepted tokens is released there, so nothing is rewound."""
+        emit = [r for r in self.slots if r is not None and not r.done and not r.chunks]
+        table = deal_verify_rows([(r.slot, self._propose(r)) for r in emit])
+        if not table:
+            return False
+        got = self.batch.verify_batch(table, self.sampling)
+        self.stats["verify_calls"] += 1
+        self.stats["drafted"] += sum(len(d) for _, d in table)
+        self.stats["accepted"] += sum(len(ids) - 1 for ids in got)
+        lg = self.batch.verify_logits() if self.keep_logits else None
+        lps = None
+        if self.keep_logprobs:   # row0[z] + i holds segment z's token i; the other rows are skipped
+            want: List[int] = []
+            for (_, d), ids in zip(table, got):
+                want += list(ids) + [-1] * (len(d) + 1 - len(ids))
+            lps = self.batch.verify_logprobs(want)
+        row0 = 0
+        for (slot, d), ids in zip(table, got):
+            r = self.slots[slot]
+            for i, tok in enumerate(ids):
+                self._emit_row(r, int(tok), out, None if lg is None else lg[row0 + i],
+                               None if lps is None else lps[row0 + i])
+                if r.done:
+                    break
+            row0 += len(d) + 1
+        return True
+
     def step(self) -> List[tuple]:
-        """Admit what fits, then one decode step for every slot; returns the (request id,
-        token) pairs produced, in slot order."""
+        """Admit what fits, then one decode step for every slot (with a drafter: one verify step
+        over the emitting slots when any of them has a draft); returns the (request id, token)
+        pairs produced, in slot order."""
         out: List[tuple] = []
         before = {r.rid for r in self.slots if r is not None}
         self._admit(out)
         self._advance_chunks(out, {r.rid for r in self.slots if r is not None} - before)
         if any(s is not None for s in self.slots):
+            if self.drafter is not None and self._verify_step(out):
+                return out
             live = list(self.slots)
             ids = self.batch.decode_step(self.sampling)
             lg = self.batch.logits() if self.keep_logits else None

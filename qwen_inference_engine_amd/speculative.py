@@ -13,6 +13,10 @@ every token so far (prompt and generated, the last one being the pending current
   history's longest recent suffix.  Pure Python, no model.
 * ``ModelDrafter``: greedy steps of a second, smaller ``Engine`` / ``Batch`` kept in step
   with the target's accepted history.
+
+``SpeculativeDecoder`` drives one sequence.  For many requests at once hand a drafter to
+``ContinuousBatcher(drafter=...)``: it verifies every slot's drafts in one ``Batch.verify_batch``
+pass per step; a ``ModelDrafter`` shared across slots is not supported there.
 """
 from __future__ import annotations
 
