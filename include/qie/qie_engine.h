@@ -117,7 +117,17 @@ typedef struct qie_engine_opts {
                                 block-scaled fp8 MFMA (QIE_LINEAR_ACT_FP8) — activations
                                 quantised per row to e4m3 before each projection, a
                                 different model from the bf16-activation one (numerics flag) */
-    int32_t reserved[5];
+    int32_t weight_fp4;      /* 1: the seven layer projections quantised to MXFP4 after loading
+                                (qie_ops.h: e2m1 codes, 32-element blocks, e8m0 scales).  Every
+                                M <= 16 launch of a projection (decode, verify, short prefills
+                                and appends) reads the codes, every larger one their exact bf16
+                                dequantisation, which the engine keeps beside the codes: memory
+                                GROWS by ~0.27x the bf16 projections.  lm_head, embeddings, norms
+                                and biases stay bf16; with weight_fp8 the lm_head alone is fp8.
+                                -22 from qie_engine_create with tensor parallelism, prefill_fp8,
+                                or a hidden / q dim / ffn the MXFP4 kernel does not take; the
+                                persistent decode mode refuses such an engine                  */
+    int32_t reserved[4];
 } qie_engine_opts;
 
 int qie_engine_create(const qie_model_spec* spec, const qie_engine_opts* opts, qie_engine** out);

@@ -95,7 +95,8 @@ typedef struct qie_linear_args {
     int32_t numerics;       /* for the fused norm                                       */
     const void* norm_w;     /* optional fused RMSNorm of x (weight [K]); GEMV path only */
     float norm_eps;
-    int32_t flags;          /* QIE_LINEAR_FP8: w[i] are fp8 weights (see below); else 0  */
+    int32_t flags;          /* QIE_LINEAR_FP8 / QIE_LINEAR_FP4: w[i] are fp8 / MXFP4 weights
+                               (see below); else 0                                      */
     uint64_t* argmax_keys;  /* optional [M] selection keys, atomically max-merged
                                (fused greedy arg-max, logit_decode.cu:15-33); caller
                                zeroes them before the launch                            */
@@ -440,6 +441,57 @@ int qie_fp8_tile16(const void* w_fp8, int64_t rows, int64_t cols, void* out, voi
 int qie_debug_fp8_decode(float* out_dev);
 /* Test probe: out_dev[i] = the bf16 bits the fp8 MFMA GEMV decodes e4m3 code i to (i < 256). */
 int qie_debug_fp8_decode_bf16(uint16_t* out_dev);
+
+/* ---------------------------------------------------------- MXFP4 weights
+ * A linear weight [rows, cols] (cols % 32 == 0) in MXFP4 (OCP microscaling: e2m1 codes in
+ * 32-element blocks along a row, one e8m0 scale per block), plain layout:
+ *   rows * cols / 2 code bytes: byte b of a row holds column 2b in its low nibble and column
+ *     2b + 1 in its high nibble; a code is a sign bit (8) + the index of its magnitude in
+ *     {0, 0.5, 1, 1.5, 2, 3, 4, 6};
+ *   rows * cols / 32 e8m0 bytes follow: byte (row, j) = e stands for 2^(e - 127), the scale of
+ *     columns [32 j, 32 j + 32) of that row.
+ * qie_fp4_weight_bytes = rows * cols / 2 + rows * cols / 32.
+ * Quantiser (qie_quantize_fp4 on device, qie_quantize_fp4_host; bit-identical), per block:
+ *   s = the smallest power of two with max|w| / s <= 6, clamped to [2^-125, 2^125], 1 for an
+ *   all-zero block; code = w / s rounded to the nearest grid value, ties to the even code index
+ *   (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4); a magnitude that rounds
+ *   to 0 gets code 0 (no negative zero).  The lower clamp makes every non-zero dequantised value a
+ *   normal bf16.  The upper clamp makes finite input give finite output: 6 * 2^125 = 1.5 * 2^127 is
+ *   the largest code x scale that is a finite bf16, so a block whose maximum lies above it (the
+ *   top 0.4 octave of bf16, up to the largest finite value) keeps s = 2^125 and its elements
+ *   beyond 6 s take code 6 -- the one case in which the quantiser saturates (at s = 2^126 the
+ *   nearest code of such a maximum would be 4 x 2^126 = inf).  Everywhere else nothing saturates.
+ * Every code x 2^k is exactly a bf16, so qie_dequantize_fp4 (bf16 [rows, cols] out) is exact and
+ * an fp4 engine computes the products of the bf16 model whose weights are those values.
+ *
+ * qie_linear reads such weights with args.flags QIE_LINEAR_FP4, through ONE kernel
+ * (k_decode_fp4.hip): 1 <= M <= 16 rows, K % 128 == 0, N <= 32,768, segments of whole 16-column
+ * tiles; K <= 8,192 with every epilogue and a fused norm, longer K (up to 32,768) by split-K:
+ * one segment, no norm, no SWIGLU.  Anything else — M > 16, another K, a combination with
+ * QIE_LINEAR_FP8 / _FP8_T16 / _ACT_FP8 — returns -22: there is no other fp4 kernel to fall back
+ * to.  A split-K launch needs a per-stream workspace that cannot be allocated during a graph
+ * capture: the first such launch of a stream (or qie_batch_create of an fp4 engine) makes it.
+ * Numerics: products of the bf16 activations and the exactly dequantised bf16 weights, summed
+ * in fp32 in one fixed order (per wave over its K slice, 128-column unit by unit, four 32-product
+ * MFMA steps per unit; then the slices in wave order, split parts in part order); no float
+ * atomics; two runs are bit-identical and row m does not depend on M.
+ *
+ * 16-row tiled layout (QIE_LINEAR_FP4 | QIE_LINEAR_FP4_T16; qie_fp4_tile16; rows % 16 == 0,
+ * cols % 128 == 0): the codes of rows [16t, 16t + 16) x columns [128j, 128j + 128) form the
+ * 1-KiB block t * (cols / 128) + j; bytes [16 l, 16 l + 16) of a block (l = 0..63) are row
+ * 16t + l % 16, columns 128j + 32 (l / 16) + [0, 32): one whole MX block per lane per 16-B load.
+ * The scales follow all code blocks, tiled the same way: 64 bytes per (t, j), byte l = the scale
+ * of that lane's MX block — one contiguous 64-B read per wave load.  Same total size. */
+#define QIE_LINEAR_FP4 64
+#define QIE_LINEAR_FP4_T16 128
+int64_t qie_fp4_weight_bytes(int64_t rows, int64_t cols);
+int qie_quantize_fp4(const void* w_bf16, int64_t rows, int64_t cols, void* out, void* stream);
+int qie_quantize_fp4_host(const void* w_bf16, int64_t rows, int64_t cols, void* out);
+int qie_dequantize_fp4(const void* w_fp4, int64_t rows, int64_t cols, void* out_bf16, void* stream);
+int qie_fp4_tile16(const void* w_fp4, int64_t rows, int64_t cols, void* out, void* stream);
+/* Test probe: out_dev[16 i + c] = the bf16 bits the fp4 kernel's conversion gives code c
+ * (c < 16) under the e8m0 exponent exps[i] (host, 1 <= n_exps <= 16).  Synchronises. */
+int qie_debug_fp4_decode_bf16(const uint8_t* exps, int32_t n_exps, uint16_t* out_dev);
 
 /* Tensor-parallel shard of the same synthetic tensor: dev[i][j] = element
  * (row0 + i) * full_cols + col0 + j of the full tensor, rows x cols, row-major. */

@@ -26,6 +26,8 @@ QIE_LINEAR_TILE128 = 4
 QIE_LINEAR_STREAMK = 8
 QIE_LINEAR_FP8_T16 = 16
 QIE_LINEAR_ACT_FP8 = 32
+QIE_LINEAR_FP4 = 64
+QIE_LINEAR_FP4_T16 = 128
 QIE_ATTN_PREROPED = 0x100   # qie_attention_decode numerics flag: q / new k arrive rotated
 QIE_VERIFY_MAX_ROWS = 16    # qie_verify: the current token + at most 15 drafts
 QIE_SCORE_UNFUSED = 1       # qie_score flag: the <= 16-row head launches + qie_logprob_rows
@@ -115,7 +117,7 @@ class EngineOptsC(C.Structure):
     _fields_ = [("device", C.c_int32), ("max_ctx", C.c_int32), ("use_graph", C.c_int32),
                 ("tp_rank", C.c_int32), ("tp_size", C.c_int32), ("tp_comm", C.c_void_p),
                 ("weight_fp8", C.c_int32), ("comm_always", C.c_int32), ("prefill_fp8", C.c_int32),
-                ("reserved", C.c_int32 * 5)]
+                ("weight_fp4", C.c_int32), ("reserved", C.c_int32 * 4)]
 
 
 # (name, restype, argtypes) — every symbol the public headers declare.
@@ -192,6 +194,12 @@ SIGNATURES = [
     ("qie_fp8_tile16", C.c_int, [_P, _I64, _I64, _P, _P]),
     ("qie_debug_fp8_decode", C.c_int, [_P]),
     ("qie_debug_fp8_decode_bf16", C.c_int, [_P]),
+    ("qie_fp4_weight_bytes", C.c_int64, [_I64, _I64]),
+    ("qie_quantize_fp4", C.c_int, [_P, _I64, _I64, _P, _P]),
+    ("qie_quantize_fp4_host", C.c_int, [_P, _I64, _I64, _P]),
+    ("qie_dequantize_fp4", C.c_int, [_P, _I64, _I64, _P, _P]),
+    ("qie_fp4_tile16", C.c_int, [_P, _I64, _I64, _P, _P]),
+    ("qie_debug_fp4_decode_bf16", C.c_int, [_P, _I32, _P]),
     # qie_engine.h
     ("qie_comm_unique_id", C.c_int, [_P]),
     ("qie_comm_create_rccl", C.c_int, [_P, _I32, _I32, _I32, C.POINTER(_P)]),

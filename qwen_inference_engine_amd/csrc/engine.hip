@@ -33,7 +33,9 @@
 namespace qie {
 bool dec8_applies(const qie_linear_args* a);
 int dec8_reserve(hipStream_t st);
-bool persist_supported(const qie_model_spec& s, int B, int tp, bool fp8, bool paged, int ncu, const char** why);
+bool dec4_applies(const qie_linear_args* a);
+int dec4_reserve(hipStream_t st);
+bool persist_supported(const qie_model_spec& s, int B, int tp, bool fp8, bool fp4, bool paged, int ncu, const char** why);
 size_t persist_attn_table_bytes(int n_layers);
 int persist_attn_table(const qie_model_spec& s, const qie_layer_weights* h_layers, const void* qkv_scratch,
                        const int32_t* pos, const float* rope_cos, const float* rope_sin, const qie_kv_cache* cache,
@@ -104,6 +106,15 @@ struct qie_engine {
     // bandwidth-bound GEMVs the fp8 codes; both compute the one dequantised model
     std::vector<qie_layer_weights> layers_pf;
     void* fp8_arena = nullptr;
+    // MXFP4 projections (opts.weight_fp4): the seven layer projections as e2m1 codes + e8m0 block
+    // scales in fp4_arena (e->layers points there), read by every M <= 16 launch; layers_pf holds
+    // their exact dequantisation for the M > 16 GEMMs — in place in the engine's own arena, or in
+    // pf_arena where the bf16 weights are the caller's (never written).  The head stays bf16, or
+    // is fp8 on its own (fp8 = true) with weight_fp8.
+    bool fp4 = false;
+    bool fp4_t16 = false;        // ... in the 16-row tiled layout (qie_fp4_tile16)
+    void* fp4_arena = nullptr;
+    void* pf_arena = nullptr;
     float* rope_cos = nullptr;
     float* rope_sin = nullptr;
     int rope_rows = 0;
@@ -368,7 +379,8 @@ static int check_align(const void* p, const char* what, int layer) {
 // they may be rewritten with their dequantisation for prefill; caller-owned weights
 // (qie_engine_set_weights) are never written — their prefill takes the fp8 GEMM path.
 static bool dec8_takes_tiled_projections(const qie_engine* e);   // (beside the projection builders)
-static int quantize_weights_fp8(qie_engine* e, bool own_arena) {
+// head_only (weight_fp4 + weight_fp8): the lm_head alone; the projections are MXFP4's.
+static int quantize_weights_fp8(qie_engine* e, bool own_arena, bool head_only = false) {
     QIE_REQUIRE(e->sh.tp == 1, "fp8 weights with tensor parallelism are not supported yet");
     const qie_model_spec& s = e->spec;
     const int64_t H = s.hidden, QD = (int64_t)s.n_heads * s.head_dim, KD = (int64_t)s.n_kv_heads * s.head_dim;
@@ -377,6 +389,7 @@ static int quantize_weights_fp8(qie_engine* e, bool own_arena) {
     struct Slot { const void** p; int64_t rows, cols; };
     std::vector<Slot> ts;
     for (auto& L : e->layers) {
+        if (head_only) break;
         ts.push_back({&L.wq, QD, H});
         ts.push_back({&L.wk, KD, H});
         ts.push_back({&L.wv, KD, H});
@@ -392,8 +405,8 @@ static int quantize_weights_fp8(qie_engine* e, bool own_arena) {
     e->fp8_arena = nullptr;
     QIE_HIP(hipMalloc(&e->fp8_arena, total));
     char* dst = (char*)e->fp8_arena;
-    e->layers_pf.clear();
-    if (own_arena) e->layers_pf = e->layers;   // bf16 arena pointers, rewritten below with the dequantised values
+    if (!head_only) e->layers_pf.clear();
+    if (own_arena && !head_only) e->layers_pf = e->layers;   // bf16 arena pointers, rewritten below with the dequantised values
     for (auto& t : ts) {
         const void* src = *t.p;
         QIE_TRY(qie_quantize_fp8(src, t.rows, t.cols, dst, e->stream));
@@ -441,11 +454,91 @@ static int quantize_weights_fp8(qie_engine* e, bool own_arena) {
             if (!rc && hipStreamSynchronize(e->stream) != hipSuccess) rc = fail(-5, "fp8 tiling: synchronize failed");
             hipFree(tmp);
             if (rc) return rc;
-            e->fp8_t16 = true;
+            e->fp8_t16 = !head_only;
             e->fp8_t16_head = head;
         }
     }
     return 0;
+}
+
+// MXFP4 projections (opts.weight_fp4), beside the fp8 form above: the seven projections of every
+// layer are quantised on device into fp4_arena (qie_ops.h: e2m1 codes in 32-element blocks + e8m0
+// scales), tiled (qie_fp4_tile16) where every segment is whole 16-row tiles, and the layer
+// pointers switched to it.  Their exact dequantisation, which the M > 16 GEMMs read (layers_pf),
+// replaces the bf16 values in the engine's own arena; caller-owned weights are never written: the
+// dequantised copies go to a private allocation (pf_arena).  Embeddings, norms, biases and the
+// lm_head stay as they are; with weight_fp8 the lm_head alone is then quantised to fp8.
+static bool fp4_takes_projections(const qie_engine* e, int flags);   // (beside the projection builders)
+static int quantize_weights_fp4(qie_engine* e, bool own_arena) {
+    QIE_REQUIRE(e->sh.tp == 1, "fp4 weights with tensor parallelism are not supported");
+    const qie_model_spec& s = e->spec;
+    const int64_t H = s.hidden, QD = (int64_t)s.n_heads * s.head_dim, KD = (int64_t)s.n_kv_heads * s.head_dim;
+    const int64_t I = s.ffn;
+    QIE_REQUIRE(fp4_takes_projections(e, QIE_LINEAR_FP4),
+                "fp4 weights: the MXFP4 kernel does not take this model's projections (hidden %lld, q dim %lld, ffn %lld)",
+                (long long)H, (long long)QD, (long long)I);
+    struct Slot { const void** p; int64_t rows, cols; };
+    std::vector<Slot> ts;
+    for (auto& L : e->layers) {
+        ts.push_back({&L.wq, QD, H});
+        ts.push_back({&L.wk, KD, H});
+        ts.push_back({&L.wv, KD, H});
+        ts.push_back({&L.wo, H, QD});
+        ts.push_back({&L.w_gate, I, H});
+        ts.push_back({&L.w_up, I, H});
+        ts.push_back({&L.w_down, H, I});
+    }
+    auto a256 = [](int64_t n) { return (size_t)((n + 255) / 256 * 256); };
+    size_t total = 0, total_pf = 0, big = 0;
+    for (auto& t : ts) {
+        total += a256(qie_fp4_weight_bytes(t.rows, t.cols));
+        total_pf += a256(t.rows * t.cols * 2);
+        big = std::max(big, (size_t)qie_fp4_weight_bytes(t.rows, t.cols));
+    }
+    if (e->fp4_arena) hipFree(e->fp4_arena);
+    if (e->pf_arena) hipFree(e->pf_arena);
+    e->fp4_arena = e->pf_arena = nullptr;
+    QIE_HIP(hipMalloc(&e->fp4_arena, total));
+    if (!own_arena) QIE_HIP(hipMalloc(&e->pf_arena, total_pf));
+    const bool tile = fp4_takes_projections(e, QIE_LINEAR_FP4 | QIE_LINEAR_FP4_T16);
+    void* tmp = nullptr;
+    if (tile) QIE_TRY(dmalloc(&tmp, big));
+    e->layers_pf = e->layers;   // the bf16 pointers; the projections' are replaced below where the copy is private
+    std::vector<const void*> pf_ptr(ts.size());
+    char* dst = (char*)e->fp4_arena;
+    char* pf = (char*)e->pf_arena;
+    int rc = 0;
+    for (size_t i = 0; i < ts.size() && !rc; i++) {
+        const Slot& t = ts[i];
+        const void* src = *t.p;
+        void* plain = tile ? tmp : (void*)dst;
+        rc = qie_quantize_fp4(src, t.rows, t.cols, plain, e->stream);
+        void* deq = own_arena ? const_cast<void*>(src) : (void*)pf;
+        if (!rc) rc = qie_dequantize_fp4(plain, t.rows, t.cols, deq, e->stream);
+        if (!rc && tile) rc = qie_fp4_tile16(tmp, t.rows, t.cols, dst, e->stream);
+        pf_ptr[i] = deq;
+        *t.p = dst;
+        dst += a256(qie_fp4_weight_bytes(t.rows, t.cols));
+        if (!own_arena) pf += a256(t.rows * t.cols * 2);
+    }
+    if (!rc && hipStreamSynchronize(e->stream) != hipSuccess) rc = fail(-5, "fp4 quantisation: synchronize failed");
+    if (tmp) hipFree(tmp);
+    if (rc) return rc;
+    for (size_t l = 0; l < e->layers_pf.size(); l++) {
+        qie_layer_weights& L = e->layers_pf[l];
+        const void** slots[7] = {&L.wq, &L.wk, &L.wv, &L.wo, &L.w_gate, &L.w_up, &L.w_down};
+        for (int j = 0; j < 7; j++) *slots[j] = pf_ptr[l * 7 + j];
+    }
+    e->w.layers = e->layers.data();
+    e->fp4 = true;
+    e->fp4_t16 = tile;
+    e->fp8 = e->fp8_t16 = e->fp8_t16_head = false;
+    return e->opts.weight_fp8 ? quantize_weights_fp8(e, own_arena, true) : 0;
+}
+// after the weights are bound: the quantised forms the options ask for
+static int quantize_weights(qie_engine* e, bool own_arena) {
+    if (e->opts.weight_fp4) return quantize_weights_fp4(e, own_arena);
+    return e->opts.weight_fp8 ? quantize_weights_fp8(e, own_arena) : 0;
 }
 
 // Resolve role pointers from the reference index (short_name, layer) ->
@@ -488,7 +581,7 @@ static int bind_from_index(qie_engine* e) {
     e->w.n_layers = s.n_layers;
     e->w.layers = e->layers.data();
     e->have_weights = true;
-    return e->opts.weight_fp8 ? quantize_weights_fp8(e, true) : 0;
+    return quantize_weights(e, true);
 }
 
 // ------------------------------------------------------------- enqueue helpers
@@ -501,7 +594,10 @@ static qie_linear_args lin_args(int flags) {
 // every weight linear of the engine: fp8 weights when the engine quantised them
 static int lin_flags(const qie_engine* e) { return e->fp8 ? QIE_LINEAR_FP8 : 0; }
 // the layer projections (QKV, O, gate/up, down): + the tiled-layout flag where they are tiled
-static int proj_flags(const qie_engine* e) { return lin_flags(e) | (e->fp8_t16 ? QIE_LINEAR_FP8_T16 : 0); }
+static int proj_flags(const qie_engine* e) {
+    if (e->fp4) return QIE_LINEAR_FP4 | (e->fp4_t16 ? QIE_LINEAR_FP4_T16 : 0);
+    return lin_flags(e) | (e->fp8_t16 ? QIE_LINEAR_FP8_T16 : 0);
+}
 
 // The exchange steps go through the communicator under tensor parallelism, and at world 1
 // when the engine was asked to (opts.comm_always: the captured-collective path on one GPU).
@@ -566,6 +662,7 @@ static int row_parallel(qie_batch* b, qie_linear_args& a, uint16_t* x, float* pa
 static bool prenorm_applies(const qie_linear_args& a) {
     static const int on = dev_env("QIE_PRENORM", 1);
     if (!on || a.M < 2 || a.M > 16 || !a.norm_w) return false;
+    if (a.flags & QIE_LINEAR_FP4) return false;   // the MXFP4 kernel fuses the norm at every M it takes
     return !dec8_applies(&a) || dev_env("QIE_DEC8_PRENORM", 0) != 0;   // the fp8 batched-decode kernel fuses the norm
 }
 // ... and the action: the projection reads the normed rows xn instead of norming x itself
@@ -588,6 +685,7 @@ static int prenorm(qie_batch* b, qie_linear_args& a, uint16_t* xn) {
 // trip (QIE_ATTN_PREROPED)
 static bool rope_in_projection(const qie_batch* b) {
     const qie_model_spec& s = b->e->spec;
+    if (b->e->fp4) return false;   // the MXFP4 kernel has no RoPE epilogue: the attention launch rotates
     return b->B == 1 && !s.qk_norm && s.numerics == QIE_NUMERICS_REF && dev_env("QIE_ROPE_IN_PROJ", 0) != 0;
 }
 
@@ -661,6 +759,26 @@ static bool dec8_takes_tiled_projections(const qie_engine* e) {
         if (!dec8_applies(&a)) return false;
     return true;
 }
+
+// quantize_weights_fp4 / qie_engine_create: whether the MXFP4 kernel takes all four projection
+// launches of a layer under `flags` (plain or tiled); the plan does not depend on M <= 16 or on
+// the pointers, so a spec is enough
+static bool fp4_takes_spec(const qie_model_spec& s, int flags) {
+    qie_engine probe;
+    probe.spec = s;
+    probe.sh.nq = s.n_heads, probe.sh.nkv = s.n_kv_heads, probe.sh.ffn = s.ffn;
+    const LayerRows r{1};
+    qie_layer_weights L{};
+    qie_linear_args o = o_args(&probe, L, flags, r), down = down_args(&probe, L, flags, r);
+    o.epilogue = down.epilogue = QIE_EPI_RESIDUAL;
+    const qie_linear_args all[] = {qkv_args(&probe, L, flags, r), o, gate_up_args(&probe, L, flags, r), down};
+    for (qie_linear_args a : all) {
+        if (a.epilogue == QIE_EPI_STORE || a.epilogue == QIE_EPI_SWIGLU) a.norm_w = &probe;   // (planned as fused; not read)
+        if (!dec4_applies(&a)) return false;
+    }
+    return true;
+}
+static bool fp4_takes_projections(const qie_engine* e, int flags) { return fp4_takes_spec(e->spec, flags); }
 
 // How a built projection gets its input, applied before the launch:
 //   Decode  prenorm()'s rule (2..16 rows: norm once into the rows' xn; else the fused norm)
@@ -1020,6 +1138,16 @@ int qie_engine_create(const qie_model_spec* spec, const qie_engine_opts* opts, q
     // prefill_fp8 is a numerics choice (every projection input quantised to e4m3): refuse it
     // where the engine could not honour it, instead of silently running bf16 activations
     // against a caller (and an oracle) that expects the fp8-activation model
+    if (opts && opts->weight_fp4) {
+        QIE_REQUIRE(tp == 1, "qie_engine_create: weight_fp4 with tensor parallelism is not supported (a tp_comm of "
+                             "%d ranks was given)", tp);
+        QIE_REQUIRE(!opts->prefill_fp8, "qie_engine_create: weight_fp4 does not combine with prefill_fp8 (block-scaled "
+                                        "fp8 activations need fp8 projection weights)");
+        QIE_REQUIRE(fp4_takes_spec(s, QIE_LINEAR_FP4),
+                    "qie_engine_create: weight_fp4: the MXFP4 kernel does not take this model's projections: hidden "
+                    "(%d), q dim (%d) and ffn (%d) must be multiples of 128 (hidden at most 8192), q and kv widths "
+                    "multiples of 16", s.hidden, s.n_heads * s.head_dim, s.ffn);
+    }
     if (opts && opts->prefill_fp8) {
         const int64_t qd = (int64_t)probe.nq * s.head_dim, ffl = s.ffn / tp;
         QIE_REQUIRE(opts->weight_fp8, "qie_engine_create: prefill_fp8 needs weight_fp8 (fp8 weights are the "
@@ -1314,7 +1442,7 @@ int qie_engine_set_weights(qie_engine* e, const qie_model_weights* w) {
     e->w = *w;
     e->w.layers = e->layers.data();
     e->have_weights = true;
-    return e->opts.weight_fp8 ? quantize_weights_fp8(e, false) : 0;
+    return quantize_weights(e, false);
 }
 
 int qie_engine_weights(const qie_engine* e, qie_model_weights* out, const qie_layer_weights** layers) {
@@ -1343,6 +1471,8 @@ void qie_engine_destroy(qie_engine* e) {
     if (e->stream) hipStreamSynchronize(e->stream);
     if (e->arena) hipFree(e->arena);
     if (e->fp8_arena) hipFree(e->fp8_arena);
+    if (e->fp4_arena) hipFree(e->fp4_arena);
+    if (e->pf_arena) hipFree(e->pf_arena);
     if (e->rope_cos) hipFree(e->rope_cos);
     if (e->rope_sin) hipFree(e->rope_sin);
     if (e->index) qie_index_destroy(e->index);
@@ -1743,6 +1873,7 @@ static int batch_create(qie_engine* e, int32_t batch, int32_t max_ctx, int32_t p
         QIE_TRY(flush_table(b));
         // the fp8 batched-decode split-K workspace of this stream, before any graph capture
         if (e->fp8 && (batch >= 2 || e->fp8_t16)) QIE_TRY(dec8_reserve(e->stream));
+        if (e->fp4) QIE_TRY(dec4_reserve(e->stream));   // (the MXFP4 kernel has no other kernel to decline to)
         return 0;
     };
     if (const int rc = make()) {
@@ -1857,10 +1988,11 @@ static int enqueue_prompt_layers(qie_batch* b, const LayerRows& r, const qie_kv_
     // Otherwise bf16 rows; on an fp8 engine at >= 256 rows the GEMMs run on the dequantised bf16
     // copy (layers_pf), and with tiled fp8 projections (readable by the batched-decode kernel
     // only) every prefill of more than 16 rows does
-    const bool pf16 = e->fp8 && !e->layers_pf.empty() && (n >= 256 || (e->fp8_t16 && n > 16));
+    // (fp4 projections: codes up to 16 rows, the dequantised copy beyond — the MXFP4 kernel is their only reader)
+    const bool pf16 = e->fp4 ? n > 16 : e->fp8 && !e->layers_pf.empty() && (n >= 256 || (e->fp8_t16 && n > 16));
     LayerPath path{e->layers.data(), proj_flags(e), prefill_mx(e) ? InputForm::Fp8 : InputForm::Normed};
     if (pf16 && path.in == InputForm::Normed)
-        path = LayerPath{e->layers_pf.data(), path.flags & ~(QIE_LINEAR_FP8 | QIE_LINEAR_FP8_T16), InputForm::Normed};
+        path = LayerPath{e->layers_pf.data(), 0, InputForm::Normed};
     for (int l = 0; l < s.n_layers; l++) QIE_TRY(enqueue_layer_rows(b, l, r, path, cache, attend, b->pf_ws.p));
     return 0;
 }
@@ -2242,6 +2374,7 @@ static int ensure_verify_bufs(qie_batch* b) {
     if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
     int rc = he == hipSuccess ? 0 : fail((int)he, "qie_verify: buffer init: %s", hipGetErrorString(he));
     if (!rc && e->fp8) rc = dec8_reserve(e->stream);
+    if (!rc && e->fp4) rc = dec4_reserve(e->stream);
     if (rc) {
         hipFree(v.mem);
         return rc;
@@ -2545,7 +2678,7 @@ int qie_batch_set_decode_mode(qie_batch* b, int32_t mode) {
     qie_engine* e = b->e;
     if (mode == 1) {
         const char* why = "";
-        QIE_REQUIRE(persist_supported(e->spec, b->B, e->sh.tp, e->fp8, b->d_table != nullptr, device_cu_count(), &why),
+        QIE_REQUIRE(persist_supported(e->spec, b->B, e->sh.tp, e->fp8, e->fp4, b->d_table != nullptr, device_cu_count(), &why),
                     "qie_batch_set_decode_mode: the persistent decode step does not cover this batch (%s)", why);
         if (!b->pk_mem || !b->d_layers || !b->d_attp) {
             // all three or none: a failed allocation leaves the batch in mode 0 with nothing held
@@ -2723,12 +2856,14 @@ int qie_batch_time_kernel(qie_batch* b, int32_t which, int32_t iters, double* av
     QIE_TRY(scratch_mem.grow((size_t)B * std::max<int64_t>(std::max(I, V), QD + 2 * KD) * 2 + B * 8 + 64));
     uint16_t* scratch = (uint16_t*)scratch_mem.p;
     const double wb = e->fp8 ? 1.0 : 2.0;   // weight bytes per element (fp8 row scales: negligible)
+    // the layer projections' (fp4: a code nibble + one e8m0 byte per 32 elements)
+    const double pb = e->fp4 ? 0.5 + 1.0 / 32 : wb;
     double by = 0;
     switch (which) {
-        case 0: by = 2.0 * I * H * wb + B * H * 2 + H * 2 + B * I * 2; break;
-        case 1: by = (double)H * I * wb + B * I * 2 + B * H * 2; break;
-        case 2: by = (double)(QD + 2 * KD) * H * wb + B * H * 2 + B * (QD + 2 * KD) * 2; break;
-        case 3: by = (double)H * QD * wb + B * QD * 2 + B * H * 2; break;
+        case 0: by = 2.0 * I * H * pb + B * H * 2 + H * 2 + B * I * 2; break;
+        case 1: by = (double)H * I * pb + B * I * 2 + B * H * 2; break;
+        case 2: by = (double)(QD + 2 * KD) * H * pb + B * H * 2 + B * (QD + 2 * KD) * 2; break;
+        case 3: by = (double)H * QD * pb + B * QD * 2 + B * H * 2; break;
         case 4: by = (double)V * H * wb + B * H * 2 + B * (double)V * 2; break;
         default: {
             std::vector<int32_t> pos(B);

@@ -1158,6 +1158,13 @@ static int launch_skinny(const GemvParams& p, const LinearPlan& pl, hipStream_t 
 
 int gemm(const qie_linear_args* a, hipStream_t st);
 int dec8_linear(const qie_linear_args* a, const LinearPlan& pl, hipStream_t st, bool* done);
+int dec4_linear(const qie_linear_args* a, const LinearPlan& pl, hipStream_t st);
+
+// true when the MXFP4 kernel takes this projection (the engine then skips its separate norm)
+bool dec4_applies(const qie_linear_args* a) {
+    int ku, ks, parts;
+    return dec4_plan(*a, &ku, &ks, &parts) == PlanError::None;
+}
 
 // true when the fp8 batched-decode kernel takes this projection (the engine then skips its
 // separate norm)
@@ -1184,6 +1191,24 @@ static int gemv(const qie_linear_args* a, const LinearExtras& ex, hipStream_t st
     const Knobs k = dev_knobs();
     const int cus = device_cu_count();
     LinearPlan pl = plan_linear(*a, ex, cus, k);
+    if (pl.family == LinearFamily::Dec4) {   // MXFP4 weights: one kernel or a refusal
+        switch (pl.error) {
+            case PlanError::None: return dec4_linear(a, pl, st);
+            case PlanError::Fp4Flags:
+                return fail(-22, "qie_linear: fp4 weights: flags %d combine QIE_LINEAR_FP4 with fp8 weights / activations "
+                                 "(or name the tiled layout without QIE_LINEAR_FP4)", a->flags);
+            case PlanError::Fp4Rows:
+                return fail(-22, "qie_linear: fp4 weights are read at 1 <= M <= 16 rows only (M=%lld): larger M runs on "
+                                 "the dequantised bf16 weights", (long long)a->M);
+            case PlanError::Fp4K:
+                return fail(-22, "qie_linear: fp4 weights need K %% 128 == 0 (K=%lld)", (long long)a->K);
+            default:
+                return fail(-22, "qie_linear: fp4 weights: the MXFP4 kernel does not take M=%lld K=%lld N=%lld epilogue %d "
+                                 "(N <= 32768, segments of whole 16-column tiles, K <= 8192 or split-K without norm / "
+                                 "SWIGLU / segments up to K 32768)", (long long)a->M, (long long)a->K, (long long)a->N,
+                            a->epilogue);
+        }
+    }
     if (pl.family == LinearFamily::Dec8) {
         bool done = false;
         const int rc = dec8_linear(a, pl, st, &done);
@@ -1202,6 +1227,7 @@ static int gemv(const qie_linear_args* a, const LinearExtras& ex, hipStream_t st
             return fail(-22, "qie_linear: fp8 weights need K %% 16 == 0 (K=%lld)", (long long)a->K);
         case PlanError::NormRouted:
             return fail(-22, "qie_linear: internal: fused norm routed to a variant without one");
+        default: return fail(-22, "qie_linear: internal: plan error %d", (int)pl.error);
     }
     if (pl.family == LinearFamily::Gemm) return gemm(a, st);
     GemvParams p;
@@ -1273,6 +1299,14 @@ int linear(const qie_linear_args* a, const LinearExtras& ex, hipStream_t st) {
                      ex.rope.pos && ex.rope.cs && ex.rope.sn),
                 "qie_linear: fused RoPE: M = 1 STORE projections only");
     if (ex.push_taken) *ex.push_taken = false;
+    // MXFP4 weights have one reader: the planner takes the launch or names the refusal, at any M
+    if (a->flags & (QIE_LINEAR_FP4 | QIE_LINEAR_FP4_T16)) {
+        // (a peer push in the extras is left untaken, as the fp8 kernels leave it: *push_taken stays
+        // false and the caller runs its exchange; a fused RoPE would be dropped silently, so it is
+        // refused -- the engine does not ask for one on fp4 weights, rope_in_projection)
+        QIE_REQUIRE(!(ex.rope.pos || ex.rope.rows), "qie_linear: fp4 weights take no fused RoPE");
+        return gemv(a, ex, st);
+    }
     if (a->flags & QIE_LINEAR_ACT_FP8) return gemm(a, st);   // fp8 activations: the block-scaled MFMA GEMM at every M
     QIE_REQUIRE(!(a->flags & QIE_LINEAR_FP8_T16) ||
                     ((a->flags & QIE_LINEAR_FP8) && a->M >= 1 && a->M <= 16 && a->K % 64 == 0 &&

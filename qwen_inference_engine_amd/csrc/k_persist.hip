@@ -655,7 +655,7 @@ size_t persist_lds_bytes(int H, int I, int QD, int KD, int G, int hd) {
 // Which models / batches the persistent step covers (the launch path serves the rest):
 // batch 1, bf16 weights, one device, head_dim 128, a contiguous KV cache, and per-CU output
 // ranges that fit the kernel's LDS staging.
-bool persist_supported(const qie_model_spec& s, int B, int tp, bool fp8, bool paged, int ncu, const char** why) {
+bool persist_supported(const qie_model_spec& s, int B, int tp, bool fp8, bool fp4, bool paged, int ncu, const char** why) {
     const int QD = s.n_heads * s.head_dim, KD = s.n_kv_heads * s.head_dim;
     const int G = s.n_heads / s.n_kv_heads;
     auto no = [&](const char* w) {
@@ -665,6 +665,7 @@ bool persist_supported(const qie_model_spec& s, int B, int tp, bool fp8, bool pa
     if (B != 1) return no("batch != 1");
     if (tp != 1) return no("tensor parallel");
     if (fp8) return no("fp8 weights");
+    if (fp4) return no("fp4 weights");
     if (paged) return no("paged KV cache");
     if (s.head_dim != 128 && s.head_dim != 64) return no("head_dim not 64 or 128");
     if (s.hidden % 16 || s.ffn % 16 || QD % 16 || KD % 16) return no("widths not multiples of 16");

@@ -68,8 +68,8 @@ struct LinearExtras {
 };
 
 // ------------------------------------------------------------------ the plan
-enum class LinearFamily { Dec8, Skinny, Gemm, Gemv };
-enum class PlanError { None, TiledShape, NormLds, Fp8K16, NormRouted };
+enum class LinearFamily { Dec8, Skinny, Gemm, Gemv, Dec4 };
+enum class PlanError { None, TiledShape, NormLds, Fp8K16, NormRouted, Fp4Flags, Fp4Rows, Fp4K, Fp4Shape };
 
 constexpr int kGemvBalancedThreads = 576;   // block size bound of the one-block-per-CU GEMV (9 waves)
 constexpr size_t kGemvLdsCap = 96 * 1024;
@@ -96,6 +96,7 @@ struct LinearPlan {
     bool t16 = false;        // skinny kernel on 16-row tiled fp8 weights
     bool push = false;       // GemvParams::push taken from the extras
     int dec8_ku = 0, dec8_ks = 0, dec8_parts = 0;   // Dec8: K slice shape; parts >= 2: split-K
+    int dec4_ku = 0, dec4_ks = 0, dec4_parts = 0;   // Dec4: the same of the MXFP4 kernel (128-column units)
     bool needs_occupancy() const {
         return family == LinearFamily::Skinny ? skinny_bpc <= 0
                                               : family == LinearFamily::Gemv && block_waves == 0 && bpc <= 0;
@@ -177,6 +178,52 @@ inline bool dec8_plan(const qie_linear_args& a, const Knobs& k, int* ku, int* ks
     return true;
 }
 
+// ------------------------------------------------------------------ MXFP4 batched decode
+// The MXFP4 kernel (k_decode_fp4.hip) is the only reader of fp4 weights: what it does not take is
+// refused (a PlanError, -22 from qie_linear), never routed to another kernel.  Units are 128
+// columns (one 16-B load per lane = one 32-element MX block = four MFMA operands).  K slice
+// shapes: KU units per wave (2, 4 or 8: 16 KU VGPRs of A fragments), KS = ceil(units / KU)
+// waves; the last wave's slice may be ragged (its units past K are zero rows and loads out of
+// the buffer range).  KU is the smallest of 2 / 4 / 8 with KS <= 4 / 8 / 8, so every K up to 64
+// units (8,192) is taken unsplit, fused norm included: 896 = 2 x 4 (7 units), 3,584 = 4 x 7,
+// 5,120 = 8 x 5, 8,192 = 8 x 8.  Longer K: split-K over parts of 8 waves x 2 units (2,048
+// columns; 18,944 = 10 parts, 17,408 = 9, 29,568 = 15), single-segment epilogues without a norm.
+constexpr int kDec4MaxUnits = 64, kDec4SplitKu = 2, kDec4SplitKs = 8;
+inline PlanError dec4_plan(const qie_linear_args& a, int* ku, int* ks, int* parts) {
+    const bool t16 = (a.flags & QIE_LINEAR_FP4_T16) != 0;
+    if (!(a.flags & QIE_LINEAR_FP4) || (a.flags & (QIE_LINEAR_FP8 | QIE_LINEAR_FP8_T16 | QIE_LINEAR_ACT_FP8)))
+        return PlanError::Fp4Flags;
+    if (a.M < 1 || a.M > 16) return PlanError::Fp4Rows;
+    if (a.K <= 0 || a.K % 128 != 0) return PlanError::Fp4K;
+    if (a.N <= 0 || a.N > 32768 || a.ldx % 8 != 0 || a.K >= (1 << 20)) return PlanError::Fp4Shape;
+    const bool sw = a.epilogue == QIE_EPI_SWIGLU;
+    // column tiles must not straddle segments: a segment that another follows is whole tiles (the
+    // last one may end in a ragged tile: its rows are clamped); tiled weights: whole tiles everywhere
+    if (!sw && ((a.seg_rows[0] % 16 != 0 && (a.seg_rows[1] > 0 || a.seg_rows[2] > 0)) ||
+                ((a.seg_rows[0] + a.seg_rows[1]) % 16 != 0 && a.seg_rows[2] > 0)))
+        return PlanError::Fp4Shape;
+    if (t16 && (sw ? a.N % 16 != 0 : (a.seg_rows[0] % 16 != 0 || a.seg_rows[1] % 16 != 0 || a.seg_rows[2] % 16 != 0)))
+        return PlanError::Fp4Shape;
+    // every segment's codes + scales must fit a 32-bit buffer range
+    for (int s = 0; s < 3; s++)
+        if ((int64_t)(sw ? a.N : a.seg_rows[s]) * (a.K / 2 + a.K / 32) >= (int64_t)1 << 31) return PlanError::Fp4Shape;
+    const int64_t units = a.K / 128;
+    *parts = 1;
+    if (units <= kDec4MaxUnits) {
+        *ku = units <= 8 ? 2 : (units <= 32 ? 4 : 8);
+        *ks = (int)((units + *ku - 1) / *ku);
+        return PlanError::None;
+    }
+    if (a.norm_w || sw || a.seg_rows[1] > 0 || a.N > (int64_t)kDec8MaxTiles * 16) return PlanError::Fp4Shape;
+    const int64_t per = kDec4SplitKu * kDec4SplitKs;
+    const int64_t np = (units + per - 1) / per;
+    if (np > kDec8MaxParts) return PlanError::Fp4Shape;
+    *ku = kDec4SplitKu;
+    *ks = kDec4SplitKs;
+    *parts = (int)np;
+    return PlanError::None;
+}
+
 // ------------------------------------------------------------------ GEMV pieces
 inline bool K_fits(int64_t K, int xch) { return K <= 2048 * (int64_t)xch && K % 8 == 0; }
 
@@ -227,6 +274,14 @@ inline LinearPlan plan_linear(const qie_linear_args& a, const LinearExtras& ex, 
     const bool fp8w = (a.flags & QIE_LINEAR_FP8) != 0;
     const bool has_norm = a.norm_w != nullptr;
     const int NB = a.epilogue == QIE_EPI_SWIGLU ? 2 : 1;
+    // MXFP4 weights: k_decode_fp4.hip or an error (at any M: qie_linear sends every fp4 launch here)
+    if (a.flags & (QIE_LINEAR_FP4 | QIE_LINEAR_FP4_T16)) {
+        pl.error = dec4_plan(a, &pl.dec4_ku, &pl.dec4_ks, &pl.dec4_parts);
+        pl.family = LinearFamily::Dec4;
+        pl.wt = 2;
+        pl.n_tasks = (a.N + 15) / 16;
+        return pl;
+    }
     // fp8 weights, 2..16 rows, K a whole number of per-wave slices (or split-K): k_decode_fp8.hip
     if (allow_dec8 && dec8_plan(a, k, &pl.dec8_ku, &pl.dec8_ks, &pl.dec8_parts)) {
         pl.family = LinearFamily::Dec8;

@@ -54,7 +54,8 @@ inline std::string format_gemm_plan(const GemmPlan& g, int epi) {
 // "grid=?".
 inline std::string format_linear_plan(const qie_linear_args& a, const Knobs& k, const GemmKnobs& gk, int cus,
                                       int resident_blocks, bool allow_split = true) {
-    if ((a.flags & QIE_LINEAR_ACT_FP8) || a.M > 16) return format_gemm_plan(plan_gemm(a, gk, cus, allow_split), a.epilogue);
+    const bool fp4 = (a.flags & (QIE_LINEAR_FP4 | QIE_LINEAR_FP4_T16)) != 0;   // plan_linear's, at every M
+    if (!fp4 && ((a.flags & QIE_LINEAR_ACT_FP8) || a.M > 16)) return format_gemm_plan(plan_gemm(a, gk, cus, allow_split), a.epilogue);
     const LinearPlan pl = plan_linear(a, LinearExtras{}, cus, k);
     std::string s;
     if (pl.error != PlanError::None) {
@@ -64,6 +65,10 @@ inline std::string format_linear_plan(const qie_linear_args& a, const Knobs& k, 
     switch (pl.family) {
         case LinearFamily::Dec8:
             plan_appendf(s, "dec8 KU=%d KS=%d parts=%d", pl.dec8_ku, pl.dec8_ks, pl.dec8_parts);
+            return s;
+        case LinearFamily::Dec4:
+            plan_appendf(s, "dec4 KU=%d KS=%d parts=%d t16=%d", pl.dec4_ku, pl.dec4_ks, pl.dec4_parts,
+                         (a.flags & QIE_LINEAR_FP4_T16) ? 1 : 0);
             return s;
         case LinearFamily::Gemm: return format_gemm_plan(plan_gemm(a, gk, cus, allow_split), a.epilogue);
         case LinearFamily::Skinny:

@@ -179,7 +179,7 @@ class Comm:
 class Engine:
     def __init__(self, spec: ModelSpec, device: int = 0, max_ctx: int = 4096, use_graph: bool = True,
                  comm: Optional[Comm] = None, weight_fp8: bool = False, comm_always: bool = False,
-                 prefill_fp8: bool = False):
+                 prefill_fp8: bool = False, weight_fp4: bool = False):
         self.lib = _lib.load()
         self.spec = spec
         self._spec_c = spec.to_c()
@@ -192,6 +192,10 @@ class Engine:
         # numerics flag: prefill projections on the block-scaled fp8 MFMA (activations quantised
         # per row to e4m3; needs weight_fp8) — the oracle's Model(prefill_act_fp8=True)
         opts.prefill_fp8 = int(prefill_fp8)
+        # the seven layer projections in MXFP4 (e2m1 codes, 32-element blocks, e8m0 scales) for
+        # every M <= 16 launch; with weight_fp8 the lm_head alone is fp8.  The model computed is
+        # HostWeights.fp4_dequantized(head_fp8=weight_fp8)
+        opts.weight_fp4 = int(weight_fp4)
         self.comm = comm
         self._fp8 = weight_fp8
         h = C.c_void_p()

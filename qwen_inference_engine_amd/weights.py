@@ -191,6 +191,59 @@ def dequantize_fp8(codes: np.ndarray, scales: np.ndarray) -> np.ndarray:
     return (b >> 16).astype(np.uint16)
 
 
+# ------------------------------------------------------------------ MXFP4 weights
+# The written-down rule of include/qie/qie_ops.h in numpy, independent of libqie's quantisers
+# (tests compare them bit for bit).
+E2M1_GRID = np.array([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0], np.float64)
+
+
+def quantize_mxfp4(w: np.ndarray):
+    """bf16 bits [rows, cols] (cols % 32 == 0) -> (codes uint8 [rows, cols] in 0..15: sign bit 8 +
+    index into E2M1_GRID; exps uint8 [rows, cols / 32]: e8m0 block exponents).  Per block of 32:
+    s = the smallest power of two with max|w| / s <= 6, clamped to [2^-125, 2^125], 1 for an
+    all-zero block; code = w / s rounded to the nearest grid value, ties to the even index; a
+    magnitude that rounds to 0 gets code 0.  (At the upper clamp -- block maxima above 6 * 2^125 --
+    w / s can exceed 6 and takes code 6: finite in, finite out.)"""
+    w = np.ascontiguousarray(w, np.uint16)
+    rows, cols = w.shape
+    assert cols % 32 == 0
+    v = (w.astype(np.uint32) << 16).view(np.float32).astype(np.float64).reshape(rows, cols // 32, 32)
+    amax = np.abs(v).max(axis=2)
+    _, e = np.frexp(amax)                       # amax = f * 2^e, f in [0.5, 1)
+    k = e.astype(np.int64) - 3                  # 6 * 2^(e - 3) = 0.75 * 2^e: the first candidate
+    k = np.where(6.0 * np.exp2(k.astype(np.float64)) < amax, k + 1, k)
+    k = np.minimum(np.maximum(k, -125), 125)
+    k = np.where(amax > 0, k, 0)
+    q = np.abs(v) / np.exp2(k.astype(np.float64))[:, :, None]   # exact: a power of two
+    mid = (E2M1_GRID[1:] + E2M1_GRID[:-1]) / 2                  # 0.25 0.75 1.25 1.75 2.5 3.5 5
+    idx = np.zeros(q.shape, np.int64)
+    for i, m in enumerate(mid):                 # above midpoint i -> at least index i + 1;
+        up = (q >= m) if i % 2 else (q > m)     # a tie goes to the even index
+        idx = np.where(up, i + 1, idx)
+    codes = np.where((v < 0) & (idx > 0), idx | 8, idx).astype(np.uint8).reshape(rows, cols)
+    return codes, (k + 127).astype(np.uint8)
+
+
+def dequantize_mxfp4(codes: np.ndarray, exps: np.ndarray) -> np.ndarray:
+    """codes x block scale as bf16 bits (exact: one mantissa bit x 2^k)."""
+    rows, cols = codes.shape
+    mag = E2M1_GRID[codes & 7].astype(np.float32)
+    val = np.where(codes & 8, -mag, mag).astype(np.float32).reshape(rows, cols // 32, 32)
+    with np.errstate(over="ignore"):
+        v = (val * np.exp2(exps.astype(np.float32) - 127.0).astype(np.float32)[:, :, None]).astype(np.float32)
+    b = np.ascontiguousarray(v.reshape(rows, cols)).view(np.uint32)
+    assert not (b & 0xFFFF).any(), "dequantised fp4 value not exactly representable in bf16"
+    return (b >> 16).astype(np.uint16)
+
+
+def pack_mxfp4(codes: np.ndarray, exps: np.ndarray) -> np.ndarray:
+    """The plain device layout (qie_ops.h): rows * cols / 2 code bytes (column 2b in the low
+    nibble of byte b), then the rows * cols / 32 e8m0 bytes."""
+    c = np.ascontiguousarray(codes, np.uint8)
+    packed = (c[:, 0::2] | (c[:, 1::2] << 4)).astype(np.uint8)
+    return np.concatenate([packed.reshape(-1), np.ascontiguousarray(exps, np.uint8).reshape(-1)])
+
+
 # ------------------------------------------------------------------ synthetic values
 @dataclasses.dataclass(frozen=True)
 class SynthParams:
@@ -297,6 +350,25 @@ class HostWeights:
                 t[name] = dequantize_fp8(*quantize_fp8(t[name]))
         t["lm_head.weight"] = dequantize_fp8(*quantize_fp8(self.lm_head))
         return HostWeights(spec.replace(tie_embeddings=False), t)
+
+    def fp4_dequantized(self, head_fp8: bool = False) -> "HostWeights":
+        """The model the fp4 engine computes (``qie_engine_opts.weight_fp4``): the seven layer
+        projections replaced by their MXFP4 dequantisation (exactly representable in bf16).  The
+        head, the embedding and their tie stay as they are; with ``head_fp8`` (the engine's
+        weight_fp4 + weight_fp8) the head becomes its own fp8-dequantised copy and the returned
+        spec is untied."""
+        t = dict(self.tensors)
+        spec = self.spec
+        for l in range(spec.n_layers):
+            for short in ("self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight",
+                          "self_attn.o_proj.weight", "mlp.gate_proj.weight", "mlp.up_proj.weight",
+                          "mlp.down_proj.weight"):
+                name = f"model.layers.{l}.{short}"
+                t[name] = dequantize_mxfp4(*quantize_mxfp4(t[name]))
+        if head_fp8:
+            t["lm_head.weight"] = dequantize_fp8(*quantize_fp8(self.lm_head))
+            spec = spec.replace(tie_embeddings=False)
+        return HostWeights(spec, t)
 
     def write_weights_bin(self, bin_path: str, meta_path: str) -> List[Tensor]:
         """Write the reference flat layout: tensors in parsed_tensors order, no gaps."""
