@@ -424,7 +424,10 @@ int qie_dequantize_fp8(const void* w_fp8, int64_t rows, int64_t cols, void* out_
  * e4m3 codes [M, K] with row stride ldx BYTES and x_exps their per-row e8m0 exponents, row m
  * standing for 2^(x_exps[m] - 127) * e4m3(code) (qie_quantize_rows_fp8).  The weights must be
  * fp8 (QIE_LINEAR_FP8, plain or QIE_LINEAR_FP8_T16 tiled); their power-of-two row scales are
- * the MFMA's other e8m0 operand.  K % 128 == 0, ldx % 16 == 0, no fused norm / arg-max, any
+ * the MFMA's other e8m0 operand: the kernel takes ONLY the exponent field of each fp32 row scale
+ * (bits >> 23), so the scales must be positive normal powers of two -- a mantissa or a sign is
+ * ignored, not applied (qie_quantize_fp8 writes nothing else; a prefill_fp8 engine checks the
+ * scales it makes).  K % 128 == 0, ldx % 16 == 0, no fused norm / arg-max, any
  * M (the batched-decode row limit of the tiled layout does not apply).  Replaces the
  * reference's matrix_mul (matrix_mul.cu:165-288) for a model whose prefill activations are
  * quantised; the oracle runs the same model (or_set_act_fp8). */

@@ -418,6 +418,20 @@ static int quantize_weights_fp8(qie_engine* e, bool own_arena, bool head_only = 
         dst += (qie_fp8_weight_bytes(t.rows, t.cols) + 255) / 256 * 256;
     }
     QIE_HIP(hipStreamSynchronize(e->stream));
+    // prefill_fp8: the block-scaled GEMM takes only the exponent field of a weight row scale
+    // (qie_ops.h QIE_LINEAR_ACT_FP8), so every projection's scales must be positive normal
+    // powers of two; checked once here, where they are made
+    if (e->opts.prefill_fp8) {
+        std::vector<uint32_t> sc;
+        for (auto& t : ts) {
+            if (t.p == &e->w.lm_head) continue;
+            sc.resize((size_t)t.rows);
+            QIE_HIP(hipMemcpy(sc.data(), (const char*)*t.p + t.rows * t.cols, (size_t)t.rows * 4, hipMemcpyDeviceToHost));
+            for (const uint32_t b : sc)
+                QIE_REQUIRE((b & 0x807fffffu) == 0 && (b >> 23) != 0 && (b >> 23) != 255,
+                            "prefill_fp8: an fp8 weight row scale (bits 0x%08x) is not a normal power of two", b);
+        }
+    }
     e->w.layers = e->layers.data();
     e->fp8 = true;
     e->fp8_t16 = e->fp8_t16_head = false;

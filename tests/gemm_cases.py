@@ -6,7 +6,8 @@ shape, the plan that shape gets on 256 CUs with the shipped knobs, worded as too
 prints it up to the grid, and what the GPU test feeds it.  tests/test_gemm_cases_cpu.py checks
 the declarations against plan_dump, that no reachable form lacks a row, and that the exact
 families below reject every mutant of the reference; tests/test_gpu_gemm_variants.py runs every
-row in three input families.
+row in three input families.  The fp8-activation kernel (gemm8mx_kernel) has its own table under
+the same protocol: tests/mx_cases.py, tests/test_mx_cases_cpu.py, tests/test_gpu_mx_variants.py.
 
 Plain data and numpy helpers: no test, no fixture.
 
@@ -167,7 +168,7 @@ _FORM = re.compile(r"(gemm8sk_kernel<\w+>) dp_rounds=(\d+) chunk=(\d+)|(gemm8_ke
 def form_key(text):
     """What the coverage rule counts of a plan line: (instantiation, splitk) for gemm8_kernel,
     (instantiation, dp_rounds > 0, chunk > 1) for stream-K, the instantiation otherwise; None for
-    plans out of scope (gemm8mx_kernel, the M <= 16 kernels)."""
+    other plans (gemm8mx_kernel: mx_cases.form_key; the M <= 16 kernels: linear_cases)."""
     m = _FORM.match(text)
     if not m:
         return None
@@ -258,12 +259,19 @@ def live(c, y):
 
 def perm(c):
     """F2: the column of K that holds weight row n's needle, for every n."""
-    K, cols, bk = c.K, n_cols(c), k_tile(c)
+    K, bk = c.K, k_tile(c)
     want = [0, K - 1]
     for t in cut_tiles(c):
         want += [64 * t - 1, 64 * t]
+    return place_needles(c, n_cols(c), want, [k for e in range(bk, K, bk) for k in (e - 1, e)])
+
+
+def place_needles(c, cols, want, edges):
+    """`cols` needle positions in [0, K): every k of `want`, the k of `edges` (an even choice of
+    them where the columns do not reach), the rest spread over all of K; in a random order."""
+    K = c.K
     want = list(dict.fromkeys(want))
-    edges = [k for e in range(bk, K, bk) for k in (e - 1, e) if k not in want]
+    edges = [k for k in dict.fromkeys(edges) if k not in want]
     if len(edges) > cols - len(want):   # fewer columns than edges: an even choice over all of K
         edges = [edges[i] for i in np.unique(np.linspace(0, len(edges) - 1, cols - len(want)).astype(np.int64))]
     want += edges
@@ -361,10 +369,16 @@ def model(c, inp, mut=None):
       clamped_row_stored  row M (a re-read of row M-1) stored below the last row;
       column_n_written    column N (a re-read of weight row N-1) stored beside the last column."""
     assert mut is None or mut in MUTANTS, mut
-    M, K, N, bk = c.M, c.K, n_cols(c), k_tile(c)
+    bk, cuts = k_tile(c), cut_tiles(c)
+    return model_of(c, inp, bf(inp.x).copy(), bf(np.concatenate(inp.ws)).copy(), bk, cuts[0] * 64 // bk if cuts else None, mut)
+
+
+def model_of(c, inp, x, W, bk, cut, mut):
+    """model() on the float32 values x [M, K] and W [rows, K] (changed in place) of a kernel
+    whose k-tile is bk elements and whose second part begins at k-tile `cut` (None: unsplit);
+    a `mut` that is none of MUTANTS changes nothing here."""
+    M, K, N = c.M, c.K, n_cols(c)
     nk = -(-K // bk)
-    x = bf(inp.x).copy()
-    W = bf(np.concatenate(inp.ws)).copy()
     bs = [b.copy() for b in inp.bs]
     seg0 = c.segs[0] if len(c.segs) > 1 else None   # the first column of segment 1
 
@@ -375,8 +389,7 @@ def model(c, inp, mut=None):
     elif mut == "ktile_twice":
         x[:, tile(nk // 2)] *= 2
     elif mut == "part_off_by_one":
-        cuts = cut_tiles(c)
-        x[:, tile(cuts[0] * 64 // bk if cuts else nk - 1)] = 0
+        x[:, tile(cut if cut is not None else nk - 1)] = 0
     elif mut == "weight_row_shift" and seg0:
         W[seg0] = W[seg0 - 1]
     elif mut == "neighbour_bias" and seg0 and bs:

@@ -14,7 +14,8 @@
     K - 1, both sides of every part / range cut and of every k-tile edge the columns can reach;
 (d) every mutant of the reference is rejected by at least one F1 or F2 case under the GPU
     test's own acceptance function, and the unmutated model is accepted by every case.
-Out of scope: fp8 activations (gemm8mx_kernel: tests/test_gpu_fp8_mx.py) and the forms only
+fp8 activations (gemm8mx_kernel) have the same protocol in tests/mx_cases.py,
+tests/test_mx_cases_cpu.py and tests/test_gpu_mx_variants.py.  Out of scope: the forms only
 development knobs reach (QIE_GEMM8 = 1 / 3, QIE_GEMM_BIG, QIE_GEMM8_SK_GRID / _SK_MINK: compiled
 out of the shipped library)."""
 import os

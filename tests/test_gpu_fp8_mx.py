@@ -10,6 +10,9 @@ matrix_mul.cu:165-288) — against the oracle's fp8-activation mode (or_set_act_
 * the engine (Qwen2-7B widths, 2 layers, fp8 weights, prefill_fp8) teacher-forced against the
   oracle with the same activation quantisation in its prefill (tests/parity.py's bar, whose
   second evaluation is then oracle order 8: order 2 + the MFMA accumulation model).
+Every (epilogue, weight layout, split-K) form of the kernel is run on inputs with one right answer,
+bit for bit, by tests/test_gpu_mx_variants.py (table: tests/mx_cases.py, kept complete and sharp
+by tests/test_mx_cases_cpu.py); this file holds the random-data bounds it borrows (MX_ACC_REL).
 """
 import ctypes as C
 
