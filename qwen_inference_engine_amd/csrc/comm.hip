@@ -194,7 +194,7 @@ struct LocalComm : qie_comm {
 //     hang, no silently wrong residual); the communicator is then poisoned (every later
 //     exchange returns at once) and the engine fails its next synchronising call
 //     (qie_decode / qie_decode_step / prefill with ids / logits); qie_comm_peer_error()
-//     reads the word directly.  Every rank's
+//     reads the word's copy in pinned host memory (after the rank's stream synchronised).  Every rank's
 //     collective must be able to run while another waits: one process per GPU, or (ranks of
 //     one process on one device) at most 2 ranks — a process gets 4 hardware queues, and two
 //     ranks' streams sharing one queue would serialise a waiting kernel before its peer.
@@ -210,6 +210,7 @@ struct PeerArgs {
     char* buf[kPeerMaxWorld];   // every rank's exchange buffer (this rank's own included)
     int world, rank;
     unsigned* ctl;              // this rank's [0] generation, [1] ticket, [2] error
+    unsigned* err_host;         // the error word's copy in pinned host memory (qie_comm_peer_error)
 };
 
 enum { kPeerSumF32 = 0, kPeerSumResid = 1, kPeerMaxU64 = 2, kPeerGather = 3, kPeerGatherB = 4 };
@@ -261,6 +262,7 @@ __global__ __launch_bounds__(256) void peer_kernel(PeerArgs A, const void* src, 
             __builtin_amdgcn_s_sleep(2);
             if (__builtin_amdgcn_s_memrealtime() - t0 > 1000000000ull) {   // ~10 s at 100 MHz
                 __hip_atomic_store(A.ctl + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(A.err_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
                 err_s = 1;
                 break;
             }
@@ -395,6 +397,7 @@ __global__ __launch_bounds__(256) void peer_tag_kernel(PeerArgs A, const float* 
     }
     if (late) {
         __hip_atomic_store(A.ctl + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(A.err_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         err_s = 1;
     }
     __syncthreads();
@@ -413,6 +416,10 @@ __global__ __launch_bounds__(256) void peer_tag_kernel(PeerArgs A, const float* 
 struct PeerComm : qie_comm {
     char* own = nullptr;          // this rank's exchange buffer (uncached)
     unsigned* ctl = nullptr;      // generation, ticket, error
+    // the error word again, in pinned host memory: a kernel that gives up stores it there too, so
+    // qie_comm_peer_error reads it without a HIP call (a blocking copy on the null stream between
+    // two collective calls is one more host wait that a peer thread's exchange can sit behind)
+    unsigned* err_host = nullptr;
     char* peer[kPeerMaxWorld] = {};
     bool opened[kPeerMaxWorld] = {};   // IPC-mapped (closed on destroy)
     float* tmp = nullptr;
@@ -422,6 +429,7 @@ struct PeerComm : qie_comm {
             if (opened[r] && peer[r]) hipIpcCloseMemHandle(peer[r]);
         if (own_alloc && own) peer_pool_put(own);
         if (ctl) hipFree(ctl);
+        if (err_host) hipHostFree(err_host);
         if (tmp) hipFree(tmp);
     }
     bool own_alloc = true;
@@ -431,6 +439,7 @@ struct PeerComm : qie_comm {
         a.world = world;
         a.rank = rank;
         a.ctl = ctl;
+        a.err_host = err_host;
         return a;
     }
     template <int OP>
@@ -511,6 +520,8 @@ struct PeerComm : qie_comm {
         return 0;
     }
     bool graph_capturable() const override { return true; }
+    bool in_process = false;   // the peers are host threads of this process (qie_comm_create_peer_local)
+    bool peers_wait_on_device() const override { return in_process && world > 1; }
     const unsigned* error_word() const override { return ctl + 2; }
     int error_state(void* stream) const override {   // stream-ordered (never the null stream)
         unsigned v = 0;
@@ -530,6 +541,8 @@ static int peer_alloc(PeerComm* c) {
     QIE_HIP(hipMemset(c->own + kPeerTagOff, 0, tag_bytes));   // tag 0: no generation's
     QIE_HIP(hipMalloc((void**)&c->ctl, 64));
     QIE_HIP(hipMemset(c->ctl, 0, 64));
+    QIE_HIP(hipHostMalloc((void**)&c->err_host, 64, hipHostMallocDefault));
+    *c->err_host = 0;
     QIE_HIP(hipDeviceSynchronize());   // zeroed before any stream's exchange kernel can run
     return 0;
 }
@@ -646,6 +659,7 @@ int qie_comm_create_peer_local(int32_t world, qie_comm** out) {
         auto* c = new PeerComm();
         c->world = world;
         c->rank = r;
+        c->in_process = true;
         const int rc = peer_alloc(c);
         if (rc) {
             delete c;
@@ -663,9 +677,8 @@ int qie_comm_create_peer_local(int32_t world, qie_comm** out) {
 int qie_comm_peer_error(const qie_comm* comm, int32_t* err) {
     auto* c = dynamic_cast<const PeerComm*>(comm);
     QIE_REQUIRE(c && err, "qie_comm_peer_error: not a peer communicator");
-    unsigned v[3] = {0, 0, 0};
-    QIE_HIP(hipMemcpy(v, c->ctl, sizeof(v), hipMemcpyDeviceToHost));
-    *err = (int32_t)v[2];
+    // after the rank's stream synchronised (the kernel's store has landed): no HIP call
+    *err = (int32_t)__atomic_load_n(c->err_host, __ATOMIC_ACQUIRE);
     return 0;
 }
 

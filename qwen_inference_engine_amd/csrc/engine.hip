@@ -140,9 +140,14 @@ struct DevBlock {
         bytes = 0;
     }
     // at least n bytes (never null afterwards); freed before it is made anew, so the peak does
-    // not double and a failure leaves nothing dangling
-    int grow(size_t n) {
+    // not double and a failure leaves nothing dangling.  `keep` (outgrown(), below): the old
+    // block goes there instead of to hipFree, and stays allocated beside the new one
+    int grow(size_t n, std::vector<void*>* keep = nullptr) {
         if (p && n <= bytes) return 0;
+        if (p && keep) {
+            keep->push_back(p);
+            p = nullptr;
+        }
         release();
         QIE_TRY(dmalloc(&p, n));
         bytes = n;
@@ -174,6 +179,8 @@ struct qie_batch {
     PrefillRows pf;              // prompt rows, grown to the largest prefill so far
     DevBlock pf_ws;              // its attention workspace: depends on n and on the form (short prompts split;
                                  //   an append's partials grow with its rows), not monotone in n
+    std::vector<void*> retired;  // blocks outgrown while in-process peer ranks may be running (outgrown()):
+                                 //   freed by qie_batch_destroy
     // paged KV (qie_batch_create_paged): pool pages of page_tokens tokens; the host block table,
     // the free list, the pages held per slot and the count per page live in `pool`
     // (page_pool.hpp), the device table [B + 1][max_pages] mirrors its table.  Row B belongs to
@@ -1083,15 +1090,46 @@ static void free_rows(Rows& r) {
     r = Rows{};
 }
 
+// Where a block that a call outgrows goes instead of to hipFree (null: nowhere, free it).  hipFree
+// waits for every stream of the device.  Ranks that are threads of one process on the in-process
+// peer backend (qie_comm::peers_wait_on_device) leave a call a few microseconds apart, and the
+// first one's next exchange kernel may already be waiting on the device for this rank's: a
+// hipFree between the two calls then returns only when that kernel's bounded wait gives up, and
+// the communicator is poisoned (a 17-row prefill, no attention workspace, then a 6-row one with
+// split partials: tests/test_gpu_tp.py test_peer_batch2_forms_equal_local).  Such a batch keeps
+// the blocks it outgrows until qie_batch_destroy: by then this rank has launched all its steps,
+// so no peer's exchange waits for a launch of this rank any more, and the free only waits for
+// kernels that can finish.  The cost: every block the batch ever outgrew stays allocated, and
+// each growth is to exactly n rows, so prompts of slowly rising length keep memory quadratic in
+// the longest.  The in-process peer backend is the suite's (two ranks, tiny models, a few calls);
+// ranks in processes of their own take the other branch.
+// What this covers is the growth inside prefill and scoring calls only.  Other host calls that
+// wait for the whole device are left as they are, and a caller with in-process peer ranks makes
+// them only where no collective call follows before every rank has made them too: the split-K
+// workspace's growth (k_gemm.hip g8_workspace; 256 rows and more), qie_batch_set_decode_mode,
+// qie_batch_pk_trace, PeerComm::allgather's chunk buffer (shards beyond 2 MiB), and the plain
+// helpers qie_free / qie_synchronize / qie_memcpy_d2h.
+static std::vector<void*>* outgrown(qie_batch* b) {
+    return use_comm(b->e) && b->e->comm->peers_wait_on_device() ? &b->retired : nullptr;
+}
+template <class Rows>
+static void drop_rows(qie_batch* b, Rows& r) {
+    std::vector<void*>* keep = outgrown(b);
+    if (!keep) return free_rows(r);
+    if (r.mem) keep->push_back(r.mem);
+    r = Rows{};
+}
+
 // The growable blocks: the old block is freed (and nulled) BEFORE the new one is made, so the
 // peak does not double and a failed allocation leaves rows == 0 and nothing dangling.  Not zeroed.
+// (outgrown() non-null: the old block is kept instead, and the peak does grow.)
 static int ensure_prefill_scratch(qie_batch* b, int64_t n, bool extend) {
     if (n > b->pf.rows) {
-        free_rows(b->pf);
+        drop_rows(b, b->pf);
         const RowDims d = row_dims(b->e, n);
         QIE_TRY(alloc_rows(b->pf, n, [&](Carver& c, PrefillRows& r) { carve_prefill(c, r, d, prefill_mx(b->e)); }));
     }
-    return b->pf_ws.grow((size_t)prefill_attn_ws_bytes(b, n, extend));
+    return b->pf_ws.grow((size_t)prefill_attn_ws_bytes(b, n, extend), outgrown(b));
 }
 
 // The persistent step's error word (a bounded hand-off wait that gave up): the step's outputs
@@ -1924,6 +1962,7 @@ void qie_batch_destroy(qie_batch* b) {
     for (void* p : {(void*)b->kc, (void*)b->vc, (void*)b->d_table, b->pk_mem, (void*)b->d_layers, b->d_attp,
                     (void*)b->pk_ts, (void*)b->d_slots, b->rows_ws, (void*)b->vb_aux})
         if (p) hipFree(p);
+    for (void* p : b->retired) hipFree(p);
     // (the DevBlock workspaces free themselves)
     for (qie_kv_prefix* p : b->prefixes) delete p;   // handles still open: their pages go with the pool
     delete b;
@@ -1947,10 +1986,10 @@ static int ensure_verify_bufs(qie_batch* b);
 
 static int ensure_score_scratch(qie_batch* b, int64_t n, bool fused) {
     if (n > b->sc.rows) {
-        free_rows(b->sc);
+        drop_rows(b, b->sc);
         QIE_TRY(alloc_rows(b->sc, n, [&](Carver& c, ScoreRows& r) { carve_score(c, r, n); }));
     }
-    return fused ? b->sc_ws.grow((size_t)qie_score_rows_workspace_bytes(n, b->e->spec.vocab)) : 0;
+    return fused ? b->sc_ws.grow((size_t)qie_score_rows_workspace_bytes(n, b->e->spec.vocab), outgrown(b)) : 0;
 }
 
 // The scoring head over the n rows of b->pf.x a prefill of slot `seq` has just run (after its own

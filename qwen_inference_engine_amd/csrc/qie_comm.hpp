@@ -25,6 +25,14 @@ struct qie_comm {
     // recv = [world][bytes], rank r's send at offset r * bytes
     virtual int allgather(const void* send, void* recv, int64_t bytes, hipStream_t st) = 0;
     virtual bool graph_capturable() const = 0;
+    // true where a rank's exchange kernel waits ON THE DEVICE for a peer that is a host thread
+    // of the same process (peer backend, qie_comm_create_peer_local).  A host call that waits
+    // for every stream of the device — hipFree does — made by one rank between two steps can
+    // then never return while a peer's exchange already waits for this rank's next launch (it
+    // returns when the bounded wait gives up).  The engine then keeps the blocks a prefill or
+    // scoring call outgrows instead of freeing them (engine.hip outgrown(), which also lists
+    // the device-wide host calls that are left to the caller's ordering).
+    virtual bool peers_wait_on_device() const { return false; }
     // x (bf16 [n]) = bf16(x + bf16(all-reduced sum of part)): the row-parallel exchange; the
     // peer backend does it in one kernel, the others all-reduce `part` in place and add
     virtual int allreduce_residual_bf16(const float* part, uint16_t* x, int64_t n, hipStream_t st);
