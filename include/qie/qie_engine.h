@@ -126,7 +126,15 @@ typedef struct qie_engine_opts {
                                 and biases stay bf16; with weight_fp8 the lm_head alone is fp8.
                                 -22 from qie_engine_create with tensor parallelism, prefill_fp8,
                                 or a hidden / q dim / ffn the MXFP4 kernel does not take; the
-                                persistent decode mode refuses such an engine                  */
+                                persistent decode mode refuses such an engine.
+                                2: the same codes and NO dequantised copy: every prompt pass of
+                                more than 16 rows (prefill, batch, append, ragged, score) reads
+                                the codes through the MXFP4 GEMM (QIE_LINEAR_FP4_GEMM), so the
+                                projections take 0.53 B per weight.  An engine that owns its
+                                weights (synthetic, weights.bin) then moves the tensors it still
+                                reads into a compact arena and frees the load arena (the peak
+                                during load is unchanged).  Same refusals as 1; any other value
+                                returns -22                                                   */
     int32_t reserved[4];
 } qie_engine_opts;
 
@@ -441,6 +449,10 @@ int qie_batch_reserve(qie_batch* b, int32_t seq, int32_t n_tokens);
 /* The engine's weight arena (load_all_weights_to_gpu_chunked's d_base_out /
  * total_bytes_out, iengine.cu:117) and its RoPE tables (fp32 [rows][head_dim/2]). */
 int qie_engine_arena(const qie_engine* e, void** base, int64_t* bytes);
+/* Device bytes the engine itself holds for weights: its own arena (none with caller-owned
+ * weights) + the MXFP4 codes + the dequantised copy (weight_fp4 = 1 on caller-owned weights)
+ * + the fp8 arena. */
+int qie_engine_weight_bytes(const qie_engine* e, int64_t* bytes);
 int qie_engine_rope_tables(const qie_engine* e, const float** rope_cos, const float** rope_sin,
                            int32_t* rows);
 /* Time `iters` launches of one of the decode step's kernels with hipEvents on

@@ -487,6 +487,16 @@ int qie_debug_fp8_decode_bf16(uint16_t* out_dev);
  * of that lane's MX block — one contiguous 64-B read per wave load.  Same total size. */
 #define QIE_LINEAR_FP4 64
 #define QIE_LINEAR_FP4_T16 128
+/* QIE_LINEAR_FP4 | QIE_LINEAR_FP4_GEMM (with or without _FP4_T16): M > 16 rows run the MXFP4 prefill
+ * GEMM (k_gemm_fp4.hip), which reads the same codes and scales in either layout: K % 128 == 0, every
+ * epilogue, up to three segments (a segment that another follows, and every tiled segment, whole
+ * 16-row tiles), no fused norm / arg-max, M_pad x ldx x 2 < 2^32 bytes, each segment under 2^31
+ * bytes.  M <= 16 goes to the kernel above exactly as without the flag.  The flag without
+ * QIE_LINEAR_FP4, or with an fp8 flag, returns -22.  Numerics: the same products, fp32 sums per
+ * output in k order (128-column units, four 32-product MFMA steps each; split-K parts in part
+ * order); no float atomics, two runs bit-identical, row m independent of M.  No bf16 weight is
+ * written anywhere: an engine can keep the codes alone (qie_engine_opts.weight_fp4 = 2). */
+#define QIE_LINEAR_FP4_GEMM 256
 int64_t qie_fp4_weight_bytes(int64_t rows, int64_t cols);
 int qie_quantize_fp4(const void* w_bf16, int64_t rows, int64_t cols, void* out, void* stream);
 int qie_quantize_fp4_host(const void* w_bf16, int64_t rows, int64_t cols, void* out);

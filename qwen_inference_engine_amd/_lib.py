@@ -28,6 +28,7 @@ QIE_LINEAR_FP8_T16 = 16
 QIE_LINEAR_ACT_FP8 = 32
 QIE_LINEAR_FP4 = 64
 QIE_LINEAR_FP4_T16 = 128
+QIE_LINEAR_FP4_GEMM = 256   # with QIE_LINEAR_FP4: M > 16 rows run the MXFP4 prefill GEMM
 QIE_ATTN_PREROPED = 0x100   # qie_attention_decode numerics flag: q / new k arrive rotated
 QIE_VERIFY_MAX_ROWS = 16    # qie_verify: the current token + at most 15 drafts
 QIE_SCORE_UNFUSED = 1       # qie_score flag: the <= 16-row head launches + qie_logprob_rows
@@ -269,6 +270,7 @@ SIGNATURES = [
     ("qie_batch_kv_cache", C.c_int, [_P, _I32, C.POINTER(KvCacheC)]),
     ("qie_batch_reserve", C.c_int, [_P, _I32, _I32]),
     ("qie_engine_arena", C.c_int, [_P, C.POINTER(_P), _PI64]),
+    ("qie_engine_weight_bytes", C.c_int, [_P, _PI64]),
     ("qie_engine_rope_tables", C.c_int, [_P, C.POINTER(_P), C.POINTER(_P), _PI32]),
     ("qie_batch_time_kernel", C.c_int, [_P, _I32, _I32, _PD, _PD]),
     ("qie_batch_debug_step", C.c_int, [_P, _P, _PI32, _P]),

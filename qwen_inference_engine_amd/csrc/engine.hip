@@ -115,6 +115,10 @@ struct qie_engine {
     bool fp4_t16 = false;        // ... in the 16-row tiled layout (qie_fp4_tile16)
     void* fp4_arena = nullptr;
     void* pf_arena = nullptr;
+    // opts.weight_fp4 == 2: codes only.  layers_pf stays empty, pf_arena is never allocated, and every
+    // prompt pass of more than 16 rows reads the codes through the MXFP4 GEMM (QIE_LINEAR_FP4_GEMM)
+    bool fp4_codes_only = false;
+    size_t fp4_bytes = 0, pf_bytes = 0, fp8_bytes = 0;   // of fp4_arena, pf_arena, fp8_arena (qie_engine_weight_bytes)
     float* rope_cos = nullptr;
     float* rope_sin = nullptr;
     int rope_rows = 0;
@@ -411,6 +415,7 @@ static int quantize_weights_fp8(qie_engine* e, bool own_arena, bool head_only = 
     if (e->fp8_arena) hipFree(e->fp8_arena);
     e->fp8_arena = nullptr;
     QIE_HIP(hipMalloc(&e->fp8_arena, total));
+    e->fp8_bytes = total;
     char* dst = (char*)e->fp8_arena;
     if (!head_only) e->layers_pf.clear();
     if (own_arena && !head_only) e->layers_pf = e->layers;   // bf16 arena pointers, rewritten below with the dequantised values
@@ -490,6 +495,53 @@ static int quantize_weights_fp8(qie_engine* e, bool own_arena, bool head_only = 
 // dequantised copies go to a private allocation (pf_arena).  Embeddings, norms, biases and the
 // lm_head stay as they are; with weight_fp8 the lm_head alone is then quantised to fp8.
 static bool fp4_takes_projections(const qie_engine* e, int flags);   // (beside the projection builders)
+// Codes-only engine with its own arena: what is still read of it (embeddings, lm_head, norms, biases)
+// moves into a compact allocation and the pointers are rebound.  The caller frees *load_arena once the
+// fp8 head is made: an untied head that weight_fp8 replaces is quantised from there and not kept in bf16.
+// The index goes too: its offsets are the load arena's.
+static int compact_own_arena(qie_engine* e, void** load_arena) {
+    const qie_model_spec& s = e->spec;
+    const int64_t H = s.hidden, QD = (int64_t)s.n_heads * s.head_dim, KD = (int64_t)s.n_kv_heads * s.head_dim;
+    struct Slot { const void** p; int64_t bytes; };
+    std::vector<Slot> ts;
+    ts.push_back({&e->w.embed, (int64_t)s.vocab * H * 2});
+    const bool tied = e->w.lm_head == e->w.embed;
+    if (!tied && !e->opts.weight_fp8) ts.push_back({&e->w.lm_head, (int64_t)s.vocab * H * 2});
+    ts.push_back({&e->w.final_norm, H * 2});
+    for (auto& L : e->layers) {
+        ts.push_back({&L.attn_norm, H * 2});
+        ts.push_back({&L.ffn_norm, H * 2});
+        ts.push_back({&L.bq, QD * 2});
+        ts.push_back({&L.bk, KD * 2});
+        ts.push_back({&L.bv, KD * 2});
+        ts.push_back({&L.q_norm, (int64_t)s.head_dim * 2});
+        ts.push_back({&L.k_norm, (int64_t)s.head_dim * 2});
+    }
+    auto a256 = [](int64_t n) { return (size_t)((n + 255) / 256 * 256); };
+    size_t total = 0;
+    for (auto& t : ts)
+        if (*t.p) total += a256(t.bytes);
+    void* compact = nullptr;
+    QIE_HIP(hipMalloc(&compact, total));
+    char* dst = (char*)compact;
+    for (auto& t : ts) {
+        if (!*t.p) continue;
+        if (hipMemcpyAsync(dst, *t.p, (size_t)t.bytes, hipMemcpyDeviceToDevice, e->stream) != hipSuccess) {
+            hipFree(compact);
+            return fail(-5, "fp4 codes-only: copy into the compact arena failed");
+        }
+        *t.p = dst;
+        dst += a256(t.bytes);
+    }
+    if (tied) e->w.lm_head = e->w.embed;
+    if (hipStreamSynchronize(e->stream) != hipSuccess) return fail(-5, "fp4 codes-only: synchronize failed");
+    *load_arena = e->arena;
+    e->arena = compact;
+    e->arena_bytes = total;
+    if (e->index) qie_index_destroy(e->index);
+    e->index = nullptr;
+    return 0;
+}
 static int quantize_weights_fp4(qie_engine* e, bool own_arena) {
     QIE_REQUIRE(e->sh.tp == 1, "fp4 weights with tensor parallelism are not supported");
     const qie_model_spec& s = e->spec;
@@ -519,8 +571,14 @@ static int quantize_weights_fp4(qie_engine* e, bool own_arena) {
     if (e->fp4_arena) hipFree(e->fp4_arena);
     if (e->pf_arena) hipFree(e->pf_arena);
     e->fp4_arena = e->pf_arena = nullptr;
+    const bool codes_only = e->opts.weight_fp4 == 2;
+    e->fp4_bytes = e->pf_bytes = 0;
     QIE_HIP(hipMalloc(&e->fp4_arena, total));
-    if (!own_arena) QIE_HIP(hipMalloc(&e->pf_arena, total_pf));
+    e->fp4_bytes = total;
+    if (!own_arena && !codes_only) {
+        QIE_HIP(hipMalloc(&e->pf_arena, total_pf));
+        e->pf_bytes = total_pf;
+    }
     const bool tile = fp4_takes_projections(e, QIE_LINEAR_FP4 | QIE_LINEAR_FP4_T16);
     void* tmp = nullptr;
     if (tile) QIE_TRY(dmalloc(&tmp, big));
@@ -535,9 +593,9 @@ static int quantize_weights_fp4(qie_engine* e, bool own_arena) {
         void* plain = tile ? tmp : (void*)dst;
         rc = qie_quantize_fp4(src, t.rows, t.cols, plain, e->stream);
         void* deq = own_arena ? const_cast<void*>(src) : (void*)pf;
-        if (!rc) rc = qie_dequantize_fp4(plain, t.rows, t.cols, deq, e->stream);
+        if (!rc && !codes_only) rc = qie_dequantize_fp4(plain, t.rows, t.cols, deq, e->stream);
         if (!rc && tile) rc = qie_fp4_tile16(tmp, t.rows, t.cols, dst, e->stream);
-        pf_ptr[i] = deq;
+        pf_ptr[i] = codes_only ? nullptr : deq;
         *t.p = dst;
         dst += a256(qie_fp4_weight_bytes(t.rows, t.cols));
         if (!own_arena) pf += a256(t.rows * t.cols * 2);
@@ -550,11 +608,17 @@ static int quantize_weights_fp4(qie_engine* e, bool own_arena) {
         const void** slots[7] = {&L.wq, &L.wk, &L.wv, &L.wo, &L.w_gate, &L.w_up, &L.w_down};
         for (int j = 0; j < 7; j++) *slots[j] = pf_ptr[l * 7 + j];
     }
+    if (codes_only) e->layers_pf.clear();
     e->w.layers = e->layers.data();
     e->fp4 = true;
     e->fp4_t16 = tile;
+    e->fp4_codes_only = codes_only;
     e->fp8 = e->fp8_t16 = e->fp8_t16_head = false;
-    return e->opts.weight_fp8 ? quantize_weights_fp8(e, own_arena, true) : 0;
+    void* load_arena = nullptr;
+    if (codes_only && own_arena) QIE_TRY(compact_own_arena(e, &load_arena));   // (before the head is quantised or tiled)
+    rc = e->opts.weight_fp8 ? quantize_weights_fp8(e, own_arena, true) : 0;
+    if (load_arena) hipFree(load_arena);
+    return rc;
 }
 // after the weights are bound: the quantised forms the options ask for
 static int quantize_weights(qie_engine* e, bool own_arena) {
@@ -1191,6 +1255,8 @@ int qie_engine_create(const qie_model_spec* spec, const qie_engine_opts* opts, q
     // where the engine could not honour it, instead of silently running bf16 activations
     // against a caller (and an oracle) that expects the fp8-activation model
     if (opts && opts->weight_fp4) {
+        QIE_REQUIRE(opts->weight_fp4 == 1 || opts->weight_fp4 == 2,
+                    "qie_engine_create: weight_fp4 is 0, 1 (codes + dequantised copy) or 2 (codes only), not %d", opts->weight_fp4);
         QIE_REQUIRE(tp == 1, "qie_engine_create: weight_fp4 with tensor parallelism is not supported (a tp_comm of "
                              "%d ranks was given)", tp);
         QIE_REQUIRE(!opts->prefill_fp8, "qie_engine_create: weight_fp4 does not combine with prefill_fp8 (block-scaled "
@@ -2044,7 +2110,9 @@ static int enqueue_prompt_layers(qie_batch* b, const LayerRows& r, const qie_kv_
     // (fp4 projections: codes up to 16 rows, the dequantised copy beyond — the MXFP4 kernel is their only reader)
     const bool pf16 = e->fp4 ? n > 16 : e->fp8 && !e->layers_pf.empty() && (n >= 256 || (e->fp8_t16 && n > 16));
     LayerPath path{e->layers.data(), proj_flags(e), prefill_mx(e) ? InputForm::Fp8 : InputForm::Normed};
-    if (pf16 && path.in == InputForm::Normed)
+    if (pf16 && e->fp4_codes_only)   // no copy exists: the MXFP4 GEMM reads the codes
+        path = LayerPath{e->layers.data(), proj_flags(e) | QIE_LINEAR_FP4_GEMM, InputForm::Normed};
+    else if (pf16 && path.in == InputForm::Normed)
         path = LayerPath{e->layers_pf.data(), 0, InputForm::Normed};
     for (int l = 0; l < s.n_layers; l++) QIE_TRY(enqueue_layer_rows(b, l, r, path, cache, attend, b->pf_ws.p));
     return 0;
@@ -2812,6 +2880,13 @@ int qie_engine_arena(const qie_engine* e, void** base, int64_t* bytes) {
     QIE_REQUIRE(e && e->have_weights, "qie_engine_arena: engine has no weights");
     if (base) *base = e->arena;
     if (bytes) *bytes = (int64_t)e->arena_bytes;
+    return 0;
+}
+
+int qie_engine_weight_bytes(const qie_engine* e, int64_t* bytes) {
+    QIE_REQUIRE(e && bytes && e->have_weights, "qie_engine_weight_bytes: engine has no weights");
+    *bytes = (int64_t)((e->arena ? e->arena_bytes : 0) + (e->fp4_arena ? e->fp4_bytes : 0) + (e->pf_arena ? e->pf_bytes : 0) +
+                       (e->fp8_arena ? e->fp8_bytes : 0));
     return 0;
 }
 

@@ -34,6 +34,8 @@ enum class GemmFamily {
     Gemm8StreamK,  // gemm8sk_kernel<EPI>
     Mx,            // gemm8mx_kernel<EPI, false>: fp8 activations, plain fp8 weights
     MxT16,         // gemm8mx_kernel<EPI, true>: 16-row tiled fp8 weights
+    Fp4,           // gemm4_kernel<EPI, false> (k_gemm_fp4.hip): MXFP4 weights, plain layout
+    Fp4T16,        // gemm4_kernel<EPI, true>: 16-row tiled MXFP4 weights
 };
 
 struct GemmPlan {
@@ -51,6 +53,7 @@ struct GemmPlan {
 };
 
 constexpr int kGemmTileLds = 2 * (256 + 256) * 64 * 2;   // gemm8 family: two 64-KB k-tile buffers
+constexpr int kGemm4Lds = 2 * 256 * 128 * 2;             // gemm4: two 64-KB buffers of 256 rows x one 128-column unit
 
 // parts per tile: the fewest rounds of (tile, part) items over the CUs, in units of a tile
 // (112 tiles: 2 parts = one round of half tiles; 144 tiles: 3 parts, two rounds of thirds),
@@ -104,6 +107,19 @@ inline GemmPlan plan_gemm(const qie_linear_args& a, const GemmKnobs& k, int cus_
         }
         return tiled((a.flags & QIE_LINEAR_FP8_T16) ? GemmFamily::MxT16 : GemmFamily::Mx, t256, t256 * pl.splitk,
                      kGemmTileLds);
+    }
+
+    // QIE_LINEAR_FP4_GEMM (qie_ops.h; M > 16 on MXFP4 weights): one 256x256 kernel on 128-column units.
+    // Split-K by the ACT_FP8 rule above (tiles that do not fill half the chip, parts of >= 8 units).
+    // The rule is carried over from ACT_FP8, split against unsplit NOT A/B-measured for this kernel.  Under it,
+    // 2,048 rows, tiled codes vs the bf16 plan of the same shape (profiles/weight_fp4_prefill.json): O (112
+    // tiles, 2 parts) 89.2 vs 71.5 us, down (112, 2 parts) 256.1 vs 251.3, QKV (144, unsplit) 88.6 vs 74.2
+    if (a.flags & QIE_LINEAR_FP4_GEMM) {
+        if (allow_split && 2 * t256 <= cus) {
+            const int s = split_parts(t256, cus, (int)(a.K / 128), 8, k.mx_splitk_max);
+            if (s > 1) split(s);
+        }
+        return tiled((a.flags & QIE_LINEAR_FP4_T16) ? GemmFamily::Fp4T16 : GemmFamily::Fp4, t256, t256 * pl.splitk, kGemm4Lds);
     }
 
     if (!(a.flags & QIE_LINEAR_FP8) && a.K % 32 == 0 && a.ldx % 8 == 0) {

@@ -4,7 +4,8 @@
 // reference computes one 16x16 WMMA tile per warp with scalar 2-byte loads into
 // per-warp smem and no pipelining.  Here (gfx950):
 //   C[M, N] = A[M, K] . W[N, K]^T   (both operands K-contiguous, "NT")
-// Five kernels, chosen by plan_gemm() (gemm_plan.hpp); gemm() at the end of the file validates,
+// Five kernels here (a sixth, gemm4_kernel on MXFP4 weights, in k_gemm_fp4.hip), chosen by
+// plan_gemm() (gemm_plan.hpp); gemm() at the end of the file validates,
 // plans, gets the split-K workspace and launches the plan's instantiation:
 //   gemm_kernel      generic 128x128 tile, any K % 8 == 0, bf16 or fp8 weights (below)
 //   gemm_big_kernel  256x256 / 256x128 tile, LDS-DMA into a ring of four 32-deep k-tiles
@@ -27,6 +28,7 @@
 #include "gemm_plan.hpp"
 #include "gemm8_tile.hpp"
 #include "linear_epilogue.hpp"
+#include "gemm_epilogue.hpp"
 #include "../../include/qie/qie_ops.h"
 
 #include <map>
@@ -89,71 +91,6 @@ __device__ __forceinline__ uint4 fp8x8_to_bf16(uint2 q, float sc) {
     fp8x4_to_f32(q.y, f + 4);
     return make_uint4(pack2(f[0] * sc, f[1] * sc), pack2(f[2] * sc, f[3] * sc), pack2(f[4] * sc, f[5] * sc),
                       pack2(f[6] * sc, f[7] * sc));
-}
-
-// ---------------- epilogue of every GEMM kernel.  A wave holds NI x NJ accumulator fragments
-// (16x16 each; C/D map: col = lane & 15 = fr, row = 4 * (lane >> 4) + r = 4 fq + r) of the rows
-// from m0 (tile) + wrow (wave) and the weight rows (tile columns) from col0.  SWIGLU: fragment
-// jj is the gate and jj + NJ / 2 the up row of output column swcol0 + 16 jj + fr; STORE adds the
-// bias of the column's segment (b0 / b1 / b2, each may be null).
-struct EpiOut {
-    uint16_t* C;
-    int64_t ldc, M, N, n0, n01;
-};
-template <class P>
-__device__ __forceinline__ EpiOut epi_out(const P& p) {
-    return EpiOut{p.C, p.ldc, p.M, p.N, p.n0, p.n01};
-}
-
-template <int EPI, int NI, int NJ>
-__device__ __forceinline__ void gemm_epilogue(const f32x4 (&acc)[NI][NJ], const EpiOut& o, int64_t m0, int wrow, int64_t col0,
-                                              int64_t swcol0, int fr, int fq, const uint16_t* b0, const uint16_t* b1,
-                                              const uint16_t* b2) {
-#pragma clang fp contract(off)
-    if constexpr (EPI == QIE_EPI_SWIGLU) {
-#pragma unroll
-        for (int i = 0; i < NI; i++) {
-#pragma unroll
-            for (int jj = 0; jj < NJ / 2; jj++) {
-                const int64_t col = swcol0 + 16 * jj + fr;
-                if (col >= o.N) continue;
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int64_t row = m0 + wrow + i * 16 + fq * 4 + r;
-                    if (row >= o.M) continue;
-                    o.C[row * o.ldc + col] = swiglu_bf16(acc[i][jj][r], acc[i][jj + NJ / 2][r]);
-                }
-            }
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < NJ; j++) {
-            const int64_t col = col0 + j * 16 + fr;
-            if (col >= o.N) continue;
-            float bias = 0.f;
-            if constexpr (EPI == QIE_EPI_STORE) {
-                const uint16_t* b = col < o.n0 ? b0 : (col < o.n01 ? b1 : b2);
-                if (b) bias = bf2f(b[col < o.n0 ? col : (col < o.n01 ? col - o.n0 : col - o.n01)]);
-            }
-#pragma unroll
-            for (int i = 0; i < NI; i++) {
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int64_t row = m0 + wrow + i * 16 + fq * 4 + r;
-                    if (row >= o.M) continue;
-                    if constexpr (EPI == QIE_EPI_F32) {
-                        reinterpret_cast<float*>(o.C)[row * o.ldc + col] = acc[i][j][r];
-                        continue;
-                    }
-                    uint16_t* dst = o.C + row * o.ldc + col;
-                    if constexpr (EPI == QIE_EPI_RESIDUAL)
-                        *dst = f2bf(bf2f(*dst) + rbf(acc[i][j][r]));
-                    else
-                        *dst = f2bf(acc[i][j][r] + bias);
-                }
-            }
-        }
-    }
 }
 
 template <int EPI, int WT>
@@ -843,10 +780,17 @@ static int check_mx(const qie_linear_args* a) {
     return 0;
 }
 
+// k_gemm_fp4.hip: QIE_LINEAR_FP4_GEMM's argument check and launch
+int gemm4_check(const qie_linear_args* a);
+int gemm4_launch(const qie_linear_args* a, const GemmPlan& pl, const G8Split& ws, hipStream_t st);
+
 // validate, fill the kernels' argument blocks, plan, get the workspace, launch the plan
 int gemm(const qie_linear_args* a, hipStream_t st) {
     const bool act8 = (a->flags & QIE_LINEAR_ACT_FP8) != 0;
-    if (act8) {
+    const bool fp4 = (a->flags & QIE_LINEAR_FP4_GEMM) != 0;
+    if (fp4) {
+        QIE_TRY(gemm4_check(a));
+    } else if (act8) {
         QIE_TRY(check_mx(a));
     } else {
         QIE_REQUIRE(a->norm_w == nullptr, "qie_linear: fused RMSNorm is GEMV-only (M <= 8)");
@@ -887,6 +831,7 @@ int gemm(const qie_linear_args* a, hipStream_t st) {
     // no workspace (it would have to grow during a graph capture): what plan_gemm chooses without
     if (pl.slabs > 0 && g8_workspace(st, pl.slabs, pl.tickets, &ws) != 0) pl = plan_gemm(*a, k, cus, false);
     ws.splitk = pl.splitk;
+    if (fp4) return gemm4_launch(a, pl, ws, st);
     const G8Stream sk{pl.dp_rounds, pl.tiles, pl.chunk, ws.slab, ws.cnt};
     static const int mx_dbg = dev_env("QIE_MX_DBG", 0);
     return dispatch_epi(a->epilogue, [&](auto E) {
@@ -900,6 +845,7 @@ int gemm(const qie_linear_args* a, hipStream_t st) {
             case GemmFamily::Gemm8StreamK: return launch_plan(gemm8sk_kernel<EPI>, pl, st, p, pl.n_mt, sk);
             case GemmFamily::Mx: return launch_plan(gemm8mx_kernel<EPI, false>, pl, st, m, pl.n_mt, ws, mx_dbg);
             case GemmFamily::MxT16: return launch_plan(gemm8mx_kernel<EPI, true>, pl, st, m, pl.n_mt, ws, mx_dbg);
+            default: break;   // (Fp4 / Fp4T16 left above)
         }
         return fail(-22, "qie_linear: internal: unplanned GEMM family");
     });

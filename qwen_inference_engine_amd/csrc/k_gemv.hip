@@ -1299,7 +1299,17 @@ int linear(const qie_linear_args* a, const LinearExtras& ex, hipStream_t st) {
                      ex.rope.pos && ex.rope.cs && ex.rope.sn),
                 "qie_linear: fused RoPE: M = 1 STORE projections only");
     if (ex.push_taken) *ex.push_taken = false;
-    // MXFP4 weights have one reader: the planner takes the launch or names the refusal, at any M
+    // QIE_LINEAR_FP4_GEMM: M > 16 on fp4 weights runs gemm4_kernel (k_gemm_fp4.hip); M <= 16 as without it
+    if (a->flags & QIE_LINEAR_FP4_GEMM) {
+        QIE_REQUIRE(a->flags & QIE_LINEAR_FP4, "qie_linear: QIE_LINEAR_FP4_GEMM needs QIE_LINEAR_FP4 weights (flags %d)", a->flags);
+        QIE_REQUIRE(!(a->flags & (QIE_LINEAR_FP8 | QIE_LINEAR_FP8_T16 | QIE_LINEAR_ACT_FP8)),
+                    "qie_linear: fp4 weights: flags %d combine QIE_LINEAR_FP4_GEMM with fp8 weights / activations", a->flags);
+        if (a->M > 16) {
+            QIE_REQUIRE(!(ex.rope.pos || ex.rope.rows), "qie_linear: fp4 weights take no fused RoPE");
+            return gemm(a, st);
+        }
+    }
+    // MXFP4 weights at M <= 16 have one reader: the planner takes the launch or names the refusal
     if (a->flags & (QIE_LINEAR_FP4 | QIE_LINEAR_FP4_T16)) {
         // (a peer push in the extras is left untaken, as the fp8 kernels leave it: *push_taken stays
         // false and the caller runs its exchange; a fused RoPE would be dropped silently, so it is

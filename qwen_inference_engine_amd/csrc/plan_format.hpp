@@ -41,6 +41,8 @@ inline std::string format_gemm_plan(const GemmPlan& g, int epi) {
             break;
         case GemmFamily::Mx: plan_appendf(s, "gemm8mx_kernel<%s,0> splitk=%d", e, g.splitk); break;
         case GemmFamily::MxT16: plan_appendf(s, "gemm8mx_kernel<%s,1> splitk=%d", e, g.splitk); break;
+        case GemmFamily::Fp4: plan_appendf(s, "gemm4_kernel<%s,0> splitk=%d", e, g.splitk); break;
+        case GemmFamily::Fp4T16: plan_appendf(s, "gemm4_kernel<%s,1> splitk=%d", e, g.splitk); break;
     }
     plan_appendf(s, " n_mt=%d tiles=%d slabs=%d tickets=%d grid=%u", g.n_mt, g.tiles, g.slabs, g.tickets, g.grid_x);
     if (g.grid_y != 1) plan_appendf(s, "x%u", g.grid_y);
@@ -54,7 +56,9 @@ inline std::string format_gemm_plan(const GemmPlan& g, int epi) {
 // "grid=?".
 inline std::string format_linear_plan(const qie_linear_args& a, const Knobs& k, const GemmKnobs& gk, int cus,
                                       int resident_blocks, bool allow_split = true) {
-    const bool fp4 = (a.flags & (QIE_LINEAR_FP4 | QIE_LINEAR_FP4_T16)) != 0;   // plan_linear's, at every M
+    // fp4 weights: plan_linear's at every M, but for M > 16 under QIE_LINEAR_FP4_GEMM (qie_linear's routing)
+    const bool g4 = (a.flags & QIE_LINEAR_FP4) && (a.flags & QIE_LINEAR_FP4_GEMM) && a.M > 16;
+    const bool fp4 = (a.flags & (QIE_LINEAR_FP4 | QIE_LINEAR_FP4_T16)) != 0 && !g4;
     if (!fp4 && ((a.flags & QIE_LINEAR_ACT_FP8) || a.M > 16)) return format_gemm_plan(plan_gemm(a, gk, cus, allow_split), a.epilogue);
     const LinearPlan pl = plan_linear(a, LinearExtras{}, cus, k);
     std::string s;

@@ -194,7 +194,8 @@ class Engine:
         opts.prefill_fp8 = int(prefill_fp8)
         # the seven layer projections in MXFP4 (e2m1 codes, 32-element blocks, e8m0 scales) for
         # every M <= 16 launch; with weight_fp8 the lm_head alone is fp8.  The model computed is
-        # HostWeights.fp4_dequantized(head_fp8=weight_fp8)
+        # HostWeights.fp4_dequantized(head_fp8=weight_fp8).  True / 1 keeps the dequantised bf16 copy
+        # for passes of more than 16 rows; 2 keeps the codes alone (those passes run the MXFP4 GEMM)
         opts.weight_fp4 = int(weight_fp4)
         self.comm = comm
         self._fp8 = weight_fp8
@@ -211,6 +212,13 @@ class Engine:
         if p.head_boost_every > 0 and p.head_boost_log2 != 0:
             self.boost_head(p.head_boost_every, p.head_boost_log2)
         return self
+
+    def weight_bytes(self) -> int:
+        """Device bytes the engine itself holds for weights (qie_engine_weight_bytes): its own arena,
+        the MXFP4 codes, the dequantised copy and the fp8 arena; none of the caller's tensors."""
+        n = C.c_int64()
+        _lib.check(self.lib.qie_engine_weight_bytes(self.h, C.byref(n)), "qie_engine_weight_bytes")
+        return int(n.value)
 
     def boost_head(self, every: int, log2f: int) -> None:
         """lm_head rows r % every == 0 times 2^log2f, in place on device (SynthParams'
