@@ -135,7 +135,17 @@ typedef struct qie_engine_opts {
                                 reads into a compact arena and frees the load arena (the peak
                                 during load is unchanged).  Same refusals as 1; any other value
                                 returns -22                                                   */
-    int32_t reserved[4];
+    int32_t kv_fp8;          /* 1: every batch holds an fp8 KV cache (qie_ops.h "fp8 KV cache": e4m3 K/V rows
+                                with per-row exponents, contiguous or paged, pages counted as before) and
+                                one bf16 staging cache of one layer; decode runs qie_attention_decode_fp8,
+                                the prompt passes (prefill, prefill_batch, append, score) quantise their
+                                rows and attend over the dequantised values.  -22 from qie_engine_create
+                                with tensor parallelism, prefill_fp8, a head_dim other than 64 / 128 or
+                                any other value; such a batch returns -22 from qie_prefill_ragged,
+                                qie_verify(_batch), qie_batch_fork, qie_batch_prefix_save / _load,
+                                qie_batch_set_decode_mode(1), qie_batch_debug_step, qie_batch_time_kernel
+                                5 / 6 and qie_batch_kv_cache (was reserved[0]: the size is unchanged) */
+    int32_t reserved[3];
 } qie_engine_opts;
 
 int qie_engine_create(const qie_model_spec* spec, const qie_engine_opts* opts, qie_engine** out);
@@ -442,6 +452,11 @@ int qie_batch_dims(const qie_batch* b, int32_t* batch, int32_t* max_ctx);
  * sequence index 0): contiguous -> that slot's region; paged -> the pool with the
  * slot's block-table row.  Valid until the batch is destroyed. */
 int qie_batch_kv_cache(const qie_batch* b, int32_t seq, qie_kv_cache* out);
+/* An fp8-KV batch (qie_engine_opts.kv_fp8): its raw fp8 descriptor for sequences seq.. (-22 on a bf16
+ * batch; qie_batch_kv_cache returns -22 on an fp8 one).  qie_batch_kv_bytes, any batch: the device bytes
+ * of its K/V pools, plus on an fp8 batch the exponent arrays and the staging cache. */
+int qie_batch_kv_cache_fp8(const qie_batch* b, int32_t seq, qie_kv_cache_fp8* out);
+int qie_batch_kv_bytes(const qie_batch* b, int64_t* bytes);
 /* Operator tier: make slot `seq` a live sequence holding the KV pages for positions
  * [0, n_tokens) (paged: taken from the pool, all-or-nothing; contiguous: a bounds
  * check).  allocate_page_buffers (iengine.cu:90-100) in the reference's terms. */

@@ -506,6 +506,68 @@ int qie_fp4_tile16(const void* w_fp4, int64_t rows, int64_t cols, void* out, voi
  * (c < 16) under the e8m0 exponent exps[i] (host, 1 <= n_exps <= 16).  Synchronises. */
 int qie_debug_fp4_decode_bf16(const uint8_t* exps, int32_t n_exps, uint16_t* out_dev);
 
+/* ----------------------------------------------------------- fp8 KV cache
+ * A KV cache whose K and V rows are OCP e4m3 codes with one power-of-two scale per row.  A row is
+ * the head_dim elements of one (layer, kv head, token); it stands for 2^(e - 127) * e4m3(code).
+ * qie_kv_cache itself is unchanged; the fp8 form wraps it:
+ *   c.k / c.v point at the CODES, one byte per element, in qie_kv_cache's layout (contiguous or
+ *     paged); every count, stride and index of qie_kv_cache keeps its meaning, in elements, which
+ *     here are bytes (seq_stride % 16 == 0, 16-byte aligned);
+ *   k_exps / v_exps hold the e8m0 bytes [L][nkv][run], run = max_ctx per sequence (contiguous) or
+ *     page_tokens per page (paged); sequence s / page p at + s * exp_stride (bytes).
+ * So the exponents of a 128-key attention step are 128 contiguous bytes, and its codes at
+ * head_dim 128 are 16 KiB contiguous.
+ * Quantiser: exactly qie_quantize_rows_fp8's (e4m3_row_scale: the smallest power of two s >= 2^-126
+ * with amax / s <= 448, 1 for an all-zero row; x / s rounded to nearest even).  A row's codes and
+ * exponent equal, bit for bit, what that op gives for the same bf16 row.
+ * Every dequantised value is a bf16: a code has at most 4 significant bits and the scale is a power
+ * of two, and a bf16 input is a multiple of 2^-133, which rounding to the coarser e4m3 grid keeps.
+ * An fp8-KV attention therefore computes the bf16 model whose K/V rows are those values.
+ * Non-finite input is not supported: as in qie_quantize_rows_fp8, a NaN element is ignored by the
+ * amax and becomes a NaN code (0x7f), and an infinite element makes the row's scale infinite. */
+typedef struct qie_kv_cache_fp8 {
+    qie_kv_cache c;        /* k / v point at e4m3 CODES, one byte per element; every count, stride and
+                              index of qie_kv_cache keeps its meaning, in elements (= bytes)            */
+    void* k_exps;          /* e8m0 bytes [L][nkv][run] per sequence (contiguous: run = max_ctx) or per  */
+    void* v_exps;          /*   page (paged: run = page_tokens), page p / sequence s at + p*exp_stride  */
+    int64_t exp_stride;
+} qie_kv_cache_fp8;
+
+/* qie_qkv_post / qie_qkv_post_ragged (segs != NULL: the ragged form, rows_per_seq ignored) writing
+ * an fp8 cache: q and the K / V rows before quantisation are those ops' bit for bit; each K and V
+ * row is then quantised (above) and its codes and exponent stored.  head_dim 64 or 128.  With
+ * `stage` (may be NULL) the DEQUANTISED bf16 row also goes to the same (sequence, kv head, position)
+ * of `stage`, a contiguous bf16 cache of at least one layer with the same n_kv_heads and head_dim,
+ * always at its layer 0 — the prompt attention then reads the values decode will read. */
+int qie_qkv_post_fp8(const void* qkv, int64_t M, const int32_t* pos, int32_t rows_per_seq,
+                     const qie_row_segs* segs, const void* q_norm, const void* k_norm,
+                     const float* rope_cos, const float* rope_sin, int32_t n_heads,
+                     const qie_kv_cache_fp8* cache, const qie_kv_cache* stage, int32_t layer, float eps,
+                     int32_t numerics, void* q_out, void* stream);
+/* qie_attention_decode's contract on an fp8 cache (fused qk-norm + RoPE or QIE_ATTN_PREROPED, the
+ * new row appended QUANTISED, attention over [0, pos[m]], in-launch split combine; head_dim 64 and
+ * 128, contiguous and paged; ws as qie_attention_decode_workspace_bytes).  The codes become bf16 in
+ * registers (v_cvt_scalef32_pk_bf16_fp8, the row scale as its operand), the new token's row enters
+ * the attention dequantised, and everything after that is the bf16 kernel's arithmetic in its sum
+ * orders: the result is qie_attention_decode's on the bf16 cache holding the dequantised rows. */
+int qie_attention_decode_fp8(const void* qkv, int64_t B, const int32_t* pos, const void* q_norm,
+                             const void* k_norm, const float* rope_cos, const float* rope_sin,
+                             int32_t n_heads, const qie_kv_cache_fp8* cache, int32_t layer, float eps,
+                             int32_t numerics, void* out, void* ws, void* stream);
+/* The K and V rows [pos0, pos0 + n_rows) of every kv head of layer `layer` of sequence src_seq,
+ * expanded exactly to bf16 at the same positions of layer dst_layer of sequence dst_seq of `dst`
+ * (a contiguous bf16 cache with the same n_kv_heads and head_dim), one launch; a paged source is
+ * walked through its block table.  n_rows == 0 returns 0 without a launch. */
+int qie_kv_dequantize_fp8(const qie_kv_cache_fp8* src, int32_t src_seq, int32_t layer, int32_t pos0,
+                          int32_t n_rows, const qie_kv_cache* dst, int32_t dst_seq, int32_t dst_layer,
+                          void* stream);
+/* qie_kv_copy's contract for two fp8 caches: codes and exponents of positions [pos0, pos0 + n_rows),
+ * every layer and kv head, one launch.  As in qie_kv_copy, "the same sequence of the same cache" is
+ * judged by the K code base (contiguous) or the K base and block-table row (paged) alone: descriptors
+ * that share V or exponent arrays under different K bases are the caller's to keep apart. */
+int qie_kv_copy_fp8(const qie_kv_cache_fp8* src, int32_t src_seq, const qie_kv_cache_fp8* dst,
+                    int32_t dst_seq, int32_t pos0, int32_t n_rows, void* stream);
+
 /* Tensor-parallel shard of the same synthetic tensor: dev[i][j] = element
  * (row0 + i) * full_cols + col0 + j of the full tensor, rows x cols, row-major. */
 int qie_synthetic_fill_slice(void* dev, int64_t rows, int64_t cols, int64_t full_cols, int64_t row0,

@@ -98,6 +98,11 @@ class KvCacheC(C.Structure):
                 ("max_pages", C.c_int32)]
 
 
+class KvCacheFp8C(C.Structure):
+    """qie_kv_cache_fp8: e4m3 codes in `c`'s layout + per-row e8m0 exponent bytes."""
+    _fields_ = [("c", KvCacheC), ("k_exps", C.c_void_p), ("v_exps", C.c_void_p), ("exp_stride", C.c_int64)]
+
+
 QIE_RAGGED_MAX_SEGS = 8
 
 
@@ -118,7 +123,7 @@ class EngineOptsC(C.Structure):
     _fields_ = [("device", C.c_int32), ("max_ctx", C.c_int32), ("use_graph", C.c_int32),
                 ("tp_rank", C.c_int32), ("tp_size", C.c_int32), ("tp_comm", C.c_void_p),
                 ("weight_fp8", C.c_int32), ("comm_always", C.c_int32), ("prefill_fp8", C.c_int32),
-                ("weight_fp4", C.c_int32), ("reserved", C.c_int32 * 4)]
+                ("weight_fp4", C.c_int32), ("kv_fp8", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 # (name, restype, argtypes) — every symbol the public headers declare.
@@ -167,6 +172,13 @@ SIGNATURES = [
     ("qie_rope", C.c_int, [_P, _I64, _I64, _I32, _I32, _P, _I32, _P, _P, _I32, _P]),
     ("qie_kv_write", C.c_int, [_P, _P, _I64, _I64, _I32, C.POINTER(KvCacheC), _I32, _I32, _P]),
     ("qie_kv_copy", C.c_int, [C.POINTER(KvCacheC), _I32, C.POINTER(KvCacheC), _I32, _I32, _I32, _P]),
+    ("qie_qkv_post_fp8", C.c_int, [_P, _I64, _P, _I32, C.POINTER(RowSegsC), _P, _P, _P, _P, _I32,
+                                   C.POINTER(KvCacheFp8C), C.POINTER(KvCacheC), _I32, _F, _I32, _P, _P]),
+    ("qie_attention_decode_fp8", C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _I32, C.POINTER(KvCacheFp8C), _I32, _F,
+                                           _I32, _P, _P, _P]),
+    ("qie_kv_dequantize_fp8", C.c_int, [C.POINTER(KvCacheFp8C), _I32, _I32, _I32, _I32, C.POINTER(KvCacheC), _I32,
+                                        _I32, _P]),
+    ("qie_kv_copy_fp8", C.c_int, [C.POINTER(KvCacheFp8C), _I32, C.POINTER(KvCacheFp8C), _I32, _I32, _I32, _P]),
     ("qie_silu", C.c_int, [_P, _I64, _P]),
     ("qie_mul", C.c_int, [_P, _P, _P, _I64, _P]),
     ("qie_memcpy_d2d", C.c_int, [_P, _P, _I64, _P]),
@@ -268,6 +280,8 @@ SIGNATURES = [
     ("qie_batch_decode_mode", C.c_int, [_P]),
     ("qie_batch_pk_trace", C.c_int, [_P, _I32, _P, C.c_int64]),
     ("qie_batch_kv_cache", C.c_int, [_P, _I32, C.POINTER(KvCacheC)]),
+    ("qie_batch_kv_cache_fp8", C.c_int, [_P, _I32, C.POINTER(KvCacheFp8C)]),
+    ("qie_batch_kv_bytes", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("qie_batch_reserve", C.c_int, [_P, _I32, _I32]),
     ("qie_engine_arena", C.c_int, [_P, C.POINTER(_P), _PI64]),
     ("qie_engine_weight_bytes", C.c_int, [_P, _PI64]),

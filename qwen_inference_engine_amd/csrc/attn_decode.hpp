@@ -4,6 +4,7 @@
 // roles.  Replaces selfattention (layers/src/self_attension.cu:10-149) for one query row.
 #pragma once
 #include "qie_common.hpp"
+#include "kv_fp8.hpp"
 #include "../../include/qie/qie_ops.h"
 
 namespace qie {
@@ -208,19 +209,37 @@ __device__ __forceinline__ DecPro dec_pro_issue(const DecodeAttnParams& a, const
 
 // qk-norm + RoPE of the q heads and the new k, then q -> LDS (bf16), new k/v -> cache
 // and LDS.  Branch-free (only the stores are predicated), stores predicated, loads unconditional).
-template <int HD, bool PR>
+// KV8 (fp8 KV cache, kv_fp8.hpp): the new k / v row is quantised by the LPT lanes that hold it
+// (every lane runs the DPP amax), its codes and exponent byte (at ke / ve + eoff) go to the cache,
+// and kv_new takes the DEQUANTISED row: this step attends over what every later step will read.
+template <int HD, bool KV8>
+__device__ __forceinline__ void dec_put_new(const DecPro& d, const uint4& packed, int dl, int64_t poff, uint16_t* kb,
+                                            uint16_t* vb, uint16_t (*kv_new)[HD], const Kv8Exps* ex, int64_t eoff,
+                                            const Kv8Row& r8) {
+    if constexpr (KV8) {
+        *reinterpret_cast<uint2*>(reinterpret_cast<uint8_t*>(d.is_k ? kb : vb) + poff + dl * 8) = r8.codes;
+        if (dl == 0) (d.is_k ? ex->ke : ex->ve)[eoff] = (uint8_t)r8.e;
+        *reinterpret_cast<uint4*>(&kv_new[d.is_k ? 0 : 1][dl * 8]) = r8.deq;
+    } else {
+        *reinterpret_cast<uint4*>((d.is_k ? kb : vb) + poff + dl * 8) = packed;
+        *reinterpret_cast<uint4*>(&kv_new[d.is_k ? 0 : 1][dl * 8]) = packed;
+    }
+}
+
+template <int HD, bool PR, bool KV8 = false>
 __device__ __forceinline__ void dec_pro_finish(const DecodeAttnParams& a, DecPro& d, int dl, int grp, int64_t poff,
                                                uint16_t* kb, uint16_t* vb, uint16_t (*q_s)[HD],
-                                               uint16_t (*kv_new)[HD]) {
+                                               uint16_t (*kv_new)[HD], const Kv8Exps* ex = nullptr, int64_t eoff = 0) {
 #pragma clang fp contract(off)
     constexpr int LPT = HD / 8;
+    Kv8Row r8;
     if constexpr (PR) {   // q / new k already rotated: move them
         pin4(d.raw);
+        if constexpr (KV8) r8 = kv8_quantize_row<LPT>(d.raw);
         if (d.is_q) {
             *reinterpret_cast<uint4*>(&q_s[grp][dl * 8]) = d.raw;
         } else if (d.pro) {
-            *reinterpret_cast<uint4*>((d.is_k ? kb : vb) + poff + dl * 8) = d.raw;
-            *reinterpret_cast<uint4*>(&kv_new[d.is_k ? 0 : 1][dl * 8]) = d.raw;
+            dec_put_new<HD, KV8>(d, d.raw, dl, poff, kb, vb, kv_new, ex, eoff, r8);
         }
         return;
     }
@@ -271,12 +290,11 @@ __device__ __forceinline__ void dec_pro_finish(const DecodeAttnParams& a, DecPro
 #pragma unroll
     for (int j = 0; j < 8; j++) x[j] = d.is_v ? x[j] : y[j];
     const uint4 packed = make_uint4(pack2(x[0], x[1]), pack2(x[2], x[3]), pack2(x[4], x[5]), pack2(x[6], x[7]));
+    if constexpr (KV8) r8 = kv8_quantize_row<LPT>(packed);
     if (d.is_q) {
         *reinterpret_cast<uint4*>(&q_s[grp][dl * 8]) = packed;
     } else if (d.pro) {
-        uint16_t* dst = (d.is_k ? kb : vb) + poff + dl * 8;
-        *reinterpret_cast<uint4*>(dst) = packed;
-        *reinterpret_cast<uint4*>(&kv_new[d.is_k ? 0 : 1][dl * 8]) = packed;
+        dec_put_new<HD, KV8>(d, packed, dl, poff, kb, vb, kv_new, ex, eoff, r8);
     }
 }
 
@@ -294,9 +312,34 @@ struct AttnNoHook {
     __device__ void out4(int64_t, unsigned long long) {}
 };
 
-template <int HD, bool PG, int NWA, bool PR, int KS, class X = AttnNoHook>
+//
+// KV8 (the fp8 KV cache, qie_ops.h / kv_fp8.hpp; ex = its exponent arrays): a.kc / a.vc hold e4m3
+// codes, one byte per element.  A step's loads keep the bf16 form's (key, d) assignment at half the
+// bytes — 8 B per lane per K k-step and per V chunk — plus the step's KS exponent bytes of K and of
+// V, KS / 64 bytes per lane, once per wave.  At the top of the step the exponents pass through a
+// per-wave LDS slot to the lanes that hold each key's codes, and the codes become the SAME kf / vr
+// registers the bf16 form loads (v_cvt_scalef32_pk_bf16_fp8, the key's scale as its operand): the
+// new-row selects, the MFMAs, the V slot, the softmax and the combine below are the bf16 form's.
+// Steps stay at 128 keys.  A/B against 256-key steps (QIE_DEC_KS = 256 in the development build, both
+// forms alternating in one process, tools/kv_fp8_bench.py --step-ab; us per launch, 128 -> 256 keys):
+//   hd 128 (28 q / 4 kv heads; 256 VGPRs + 72 AGPRs against 194 + 12, one wave per SIMD, 87 KiB LDS)
+//     ctx 2k  B 1 10.00 -> 13.17   B 8  15.78 ->  14.59
+//     ctx 8k  B 1 16.66 -> 14.81   B 8  34.99 ->  37.31
+//     ctx 32k B 1 35.88 -> 37.98   B 8 111.27 -> 119.90
+//   hd 64 (14 q / 2 kv heads; 190 VGPRs against 172)
+//     ctx 2k  B 1  8.26 ->  9.39   B 8  11.66 ->  10.50
+//     ctx 8k  B 1 13.04 -> 10.92   B 8  23.08 ->  22.47
+//     ctx 32k B 1 23.83 -> 22.08   B 8  66.61 ->  65.89
+// (spreads under 0.1 us).  At hd 128 the longer step loses 6 - 8 % where the cache is largest and 32 %
+// at ctx 2k, B 1, and wins 8 - 11 % at two points: not the lever.  At hd 64 it wins 1 - 16 % from ctx
+// 8k on and loses 14 % at ctx 2k, B 1; it also needs pages of a multiple of 256 tokens, and the step
+// length is fixed when the graph is captured, so the 128-key step stays there too.
+// The fp8 form as it is against the bf16 form (profiles/kv_fp8.json, Qwen2-7B heads): 0.95 - 1.09 x its
+// time per launch at ctx 2k - 32k, B 1 / 8 — half the bytes, not faster: as many load instructions per
+// step, plus the conversions.
+template <int HD, bool PG, int NWA, bool PR, int KS, class X = AttnNoHook, bool KV8 = false>
 __device__ __forceinline__ bool attn_decode_mfma2_body(const DecodeAttnParams& a, const int bx, const int by,
-                                                       X* hook = nullptr) {
+                                                       X* hook = nullptr, const Kv8Exps* ex = nullptr) {
 #pragma clang fp contract(off)
     constexpr int LPT = HD / 8;          // prologue: lanes per head row
     constexpr int KSTEPS = HD / 32;      // MFMA k-steps over d for S
@@ -313,6 +356,8 @@ __device__ __forceinline__ bool attn_decode_mfma2_body(const DecodeAttnParams& a
     __shared__ __attribute__((aligned(16))) uint16_t v_s[NWA][KS * DW];
     __shared__ __attribute__((aligned(16))) float s_s[16][KS + 4];
     __shared__ int last_flag;
+    constexpr int EPL = KS / 64;         // KV8: exponent bytes per lane per step (K and V each)
+    __shared__ uint8_t e_s[KV8 ? NWA : 1][2][KV8 ? KS : 1];
 
     const int64_t m = by;
     const int g = bx / a.nsplit_max, s = bx % a.nsplit_max;
@@ -323,13 +368,43 @@ __device__ __forceinline__ bool attn_decode_mfma2_body(const DecodeAttnParams& a
     const int QKVD = (a.nq + 2 * a.nkv) * HD;
     const uint16_t* row = a.qkv + m * (int64_t)QKVD;
     const int64_t head_off = kv_run_off(a.km, (int64_t)a.layer * a.nkv + g, HD);
-    uint16_t* kb = a.kc + head_off;
-    uint16_t* vb = a.vc + head_off;
+    // (KV8: offsets are in elements = bytes, so the bases advance by head_off bytes)
+    uint16_t* kb = KV8 ? reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(a.kc) + head_off) : a.kc + head_off;
+    uint16_t* vb = KV8 ? reinterpret_cast<uint16_t*>(reinterpret_cast<uint8_t*>(a.vc) + head_off) : a.vc + head_off;
     uint4 kf[TPW][KSTEPS], vr[VCH];
+    uint2 kf8[KV8 ? TPW : 1][KV8 ? KSTEPS : 1], vr8[KV8 ? VCH : 1];
+    uint8_t ke8[EPL], ve8[EPL];
+    const int64_t ehead = KV8 ? kv_run_off(ex->em, (int64_t)a.layer * a.nkv + g, 1) : 0;
     // step loads of keys [kb0, kb0 + 128), rows past `last` re-read row `last`
     auto load_step_at = [&](int kb0, int last) {
         // a 128-key step never straddles a page (chunks and pages are multiples of 128)
         const int64_t so = kv_tok<PG>(a.km, m, kb0, HD);
+        if constexpr (KV8) {
+            const uint8_t* k8 = reinterpret_cast<const uint8_t*>(kb) + so;
+            const uint8_t* v8 = reinterpret_cast<const uint8_t*>(vb) + so;
+#pragma unroll
+            for (int t = 0; t < TPW; t++) {
+                const int key = min(kb0 + 16 * TPW * wave + 16 * t + fr, last);
+#pragma unroll
+                for (int ks = 0; ks < KSTEPS; ks++)
+                    kf8[t][ks] = *reinterpret_cast<const uint2*>(k8 + (int64_t)(key - kb0) * HD + 32 * ks + 8 * gq);
+            }
+#pragma unroll
+            for (int i = 0; i < VCH; i++) {
+                const int c = lane + 64 * i;
+                const int key = min(kb0 + c / CPW, last);
+                vr8[i] = *reinterpret_cast<const uint2*>(v8 + (int64_t)(key - kb0) * HD + wave * DW + (c % CPW) * 8);
+            }
+            // the step's exponent bytes (same clamp as the rows: always inside the run)
+            const int64_t eo = ehead + kv_tok<PG>(ex->em, m, kb0, 1);
+#pragma unroll
+            for (int j = 0; j < EPL; j++) {
+                const int key = min(kb0 + lane + 64 * j, last);
+                ke8[j] = ex->ke[eo + (key - kb0)];
+                ve8[j] = ex->ve[eo + (key - kb0)];
+            }
+            return;
+        }
 #pragma unroll
         for (int t = 0; t < TPW; t++) {
             const int key = min(kb0 + 16 * TPW * wave + 16 * t + fr, last);
@@ -399,18 +474,20 @@ __device__ __forceinline__ bool attn_decode_mfma2_body(const DecodeAttnParams& a
     // KS s: one-step splits, and split 0 of every context (the one-split contexts of <= 2
     // steps, Qwen2-0.5B's ctx 129-256, re-issued the same loads behind the position: +1.2 us)
     if (!(SPEC && spec) || t0 != KS * s) load_step(0);
-    if (SPEC && spec) {
+    if (!KV8 && SPEC && spec) {
         // rows past the context hold whatever the cache has there: their scores are masked
         // to -inf (P = 0), and their V rows are zeroed so that 0 * V stays 0 for any bits
+        // (KV8: zeroed after the conversion, in the step — the stale exponent may be anything too)
 #pragma unroll
         for (int i = 0; i < VCH; i++)
             if (t0 + (lane + 64 * i) / CPW >= t1) vr[i] = make_uint4(0, 0, 0, 0);
     }
-    dec_pro_finish<HD, PR>(a, pr, dl, grp, kv_tok<PG>(a.km, m, p, HD), kb, vb, q_s, kv_new);
+    dec_pro_finish<HD, PR, KV8>(a, pr, dl, grp, kv_tok<PG>(a.km, m, p, HD), kb, vb, q_s, kv_new, ex,
+                                KV8 ? ehead + kv_tok<PG>(ex->em, m, p, 1) : 0);
     for (int idx = tid; idx < (16 - G) * CPR; idx += NT)   // padded q rows
         *reinterpret_cast<uint4*>(&q_s[G + idx / CPR][(idx % CPR) * 8]) = make_uint4(0, 0, 0, 0);
     __syncthreads();
-    if (QIE_DBG(a.dbg & 8)) {
+    if (!KV8 && QIE_DBG(a.dbg & 8)) {
         if (tid == 0) a.out[m] = (uint16_t)(kf[0][0].x + vr[VCH - 1].y + kf[TPW - 1][KSTEPS - 1].z);
         return false;
     }
@@ -449,6 +526,33 @@ __device__ __forceinline__ bool attn_decode_mfma2_body(const DecodeAttnParams& a
         // kernel from 216 to 298 registers.)
         const bool hasp = p >= kb0 && p < kb0 + KS;
         const bool full = kb0 + KS <= t1;
+        if constexpr (KV8) {
+            // exponents -> this wave's LDS slot -> the lanes holding each key's codes (wave-local:
+            // no block barrier), then codes x scale -> the bf16 registers of the bf16 form
+#pragma unroll
+            for (int j = 0; j < EPL; j++) {
+                e_s[wave][0][lane + 64 * j] = ke8[j];
+                e_s[wave][1][lane + 64 * j] = ve8[j];
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+            for (int t = 0; t < TPW; t++) {
+                const float sc = kv8_scale(e_s[wave][0][16 * TPW * wave + 16 * t + fr]);
+#pragma unroll
+                for (int ks = 0; ks < KSTEPS; ks++) kf[t][ks] = fp8x8_to_bf16x8(kf8[t][ks], sc);
+            }
+#pragma unroll
+            for (int i = 0; i < VCH; i++) {
+                const int r = (lane + 64 * i) / CPW;
+                vr[i] = fp8x8_to_bf16x8(vr8[i], kv8_scale(e_s[wave][1][r]));
+                // rows past the context (the last step of the last split): P = 0 there, and the
+                // stale codes / exponent may decode to anything — 0 so that 0 * V stays 0
+                if (!full && kb0 + r >= t1) vr[i] = make_uint4(0, 0, 0, 0);
+            }
+            __builtin_amdgcn_wave_barrier();   // slot read before the next step's write
+        }
         if (hasp) {
 #pragma unroll
             for (int t = 0; t < TPW; t++) {

@@ -178,6 +178,16 @@ struct qie_batch {
     uint16_t* vc = nullptr;
     int64_t seq_stride = 0;
     int run_pad = 0;             // contiguous: run = max_ctx + run_pad tokens (dev A/B)
+    // opts.kv_fp8: kc / vc hold e4m3 codes (seq_stride in elements = bytes), ke / ve
+    // the per-row exponent bytes [L][nkv][run] per sequence / page, and sk / sv one contiguous
+    // one-layer bf16 staging cache of B sequences that the prompt passes attend over
+    bool kv8 = false;
+    uint8_t* ke = nullptr;
+    uint8_t* ve = nullptr;
+    int64_t exp_stride = 0;
+    uint16_t* sk = nullptr;
+    uint16_t* sv = nullptr;
+    int64_t stage_stride = 0;
     DecodeRows dec;              // the B slots, made by batch_create
     std::vector<int32_t> h_pos;
     PrefillRows pf;              // prompt rows, grown to the largest prefill so far
@@ -356,12 +366,38 @@ static qie_kv_cache batch_cache(const qie_batch* b, int seq0) {
         c.block_table = b->d_table + (int64_t)seq0 * b->max_pages;
         c.page_tokens = b->page_tokens;
         c.max_pages = b->max_pages;
-    } else {
-        c.k = b->kc + (int64_t)seq0 * b->seq_stride;
-        c.v = b->vc + (int64_t)seq0 * b->seq_stride;
+    } else {   // (kv8: one byte per element)
+        const int64_t off = (int64_t)seq0 * b->seq_stride * (b->kv8 ? 1 : 2);
+        c.k = (char*)b->kc + off;
+        c.v = (char*)b->vc + off;
     }
     return c;
 }
+// ... of an fp8-KV batch, and its staging cache (one layer, contiguous) for the same sequences
+static qie_kv_cache_fp8 batch_cache8(const qie_batch* b, int seq0) {
+    qie_kv_cache_fp8 c{};
+    c.c = batch_cache(b, seq0);
+    const int64_t off = b->d_table ? 0 : (int64_t)seq0 * b->exp_stride;
+    c.k_exps = b->ke + off;
+    c.v_exps = b->ve + off;
+    c.exp_stride = b->exp_stride;
+    return c;
+}
+static qie_kv_cache batch_stage(const qie_batch* b, int seq0) {
+    qie_kv_cache c{};
+    c.n_layers = 1;
+    c.n_kv_heads = b->e->sh.nkv;
+    c.head_dim = b->e->spec.head_dim;
+    c.max_ctx = b->max_ctx + b->run_pad;
+    c.seq_stride = b->stage_stride;
+    c.k = b->sk + (int64_t)seq0 * b->stage_stride;
+    c.v = b->sv + (int64_t)seq0 * b->stage_stride;
+    return c;
+}
+// the calls an fp8-KV batch does not serve: refused before anything is launched
+#define QIE_NO_KV8(b, who)                                                                                    \
+    QIE_REQUIRE(!(b)->kv8, "%s: not available on an fp8-KV batch (kv_fp8: this call reads or shares bf16 K/V " \
+                           "rows; only prefill, append, score and decode run on the fp8 cache)", who)
 
 static int build_rope(qie_engine* e) {
     const int hd = e->spec.head_dim, half = hd / 2, rows = e->opts.max_ctx;
@@ -916,6 +952,15 @@ static int attend_decode(qie_batch* b, int l, void* out) {
     const qie_layer_weights& L = e->layers[l];
     const qie_kv_cache cache = batch_cache(b, 0);
     set_decode_rope_cur(b->dec.rope_cur);
+    if (b->kv8) {
+        const qie_kv_cache_fp8 c8 = batch_cache8(b, 0);
+        const int rc = qie_attention_decode_fp8(b->dec.qkv, b->B, b->dec.pos, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin,
+                                                e->sh.nq, &c8, l, s.rms_eps,
+                                                s.numerics | (rope_in_projection(b) ? QIE_ATTN_PREROPED : 0), out,
+                                                b->dec.dec_ws, e->stream);
+        set_decode_rope_cur(nullptr);
+        return rc;
+    }
     const int rc = qie_attention_decode(b->dec.qkv, b->B, b->dec.pos, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, e->sh.nq,
                                         &cache, l, s.rms_eps,
                                         s.numerics | (rope_in_projection(b) ? QIE_ATTN_PREROPED : 0), out, b->dec.dec_ws,
@@ -952,7 +997,18 @@ static int enqueue_layer_rows(qie_batch* b, int l, const LayerRows& r, const Lay
     const qie_layer_weights& L = p.layers[l];
     hipStream_t st = e->stream;
     QIE_TRY(run_proj(b, qkv_args(e, L, p.flags, r), p.in, r));
-    if (r.segs) {
+    if (b->kv8) {
+        // fp8 KV (prefill_rows' forms only): the rows below pos0 expanded into the staging cache, the
+        // new rows quantised into the cache and staged dequantised, then the bf16 attention over the
+        // staging cache at its layer 0 — the prompt attends over the values decode will read
+        QIE_REQUIRE(!r.segs, "internal: ragged rows on an fp8-KV batch");
+        const qie_kv_cache_fp8 c8 = batch_cache8(b, r.seq0);
+        const qie_kv_cache stage = batch_stage(b, r.seq0);
+        if (r.pos0 >= 1) QIE_TRY(qie_kv_dequantize_fp8(&c8, 0, l, 0, r.pos0, &stage, 0, 0, st));
+        QIE_TRY(qie_qkv_post_fp8(r.qkv, r.M, r.pos, r.rows_per_seq, nullptr, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin,
+                                 e->sh.nq, &c8, &stage, l, s.rms_eps, s.numerics, r.q, st));
+        QIE_TRY(attend(r.q, r.M, r.pos, r.rows_per_seq, &stage, 0, e->sh.nq, r.att, attn_ws, st));
+    } else if (r.segs) {
         QIE_TRY(qie_qkv_post_ragged(r.qkv, r.M, r.pos, r.segs, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, e->sh.nq,
                                     &cache, l, s.rms_eps, s.numerics, r.q, st));
         QIE_TRY(qie_attention_ragged(r.q, r.pos, r.segs, &cache, l, e->sh.nq, r.att, attn_ws, st));
@@ -1254,6 +1310,15 @@ int qie_engine_create(const qie_model_spec* spec, const qie_engine_opts* opts, q
     // prefill_fp8 is a numerics choice (every projection input quantised to e4m3): refuse it
     // where the engine could not honour it, instead of silently running bf16 activations
     // against a caller (and an oracle) that expects the fp8-activation model
+    if (opts && opts->kv_fp8) {
+        QIE_REQUIRE(opts->kv_fp8 == 1, "qie_engine_create: kv_fp8 is 0 or 1 (fp8 KV cache), not %d", opts->kv_fp8);
+        QIE_REQUIRE(tp == 1, "qie_engine_create: kv_fp8 with tensor parallelism is not supported (a tp_comm of %d "
+                             "ranks was given)", tp);
+        QIE_REQUIRE(!opts->prefill_fp8, "qie_engine_create: kv_fp8 does not combine with prefill_fp8 (its prompt "
+                                        "passes have no fp8-KV reference to be checked against)");
+        QIE_REQUIRE(spec->head_dim == 64 || spec->head_dim == 128,
+                    "qie_engine_create: kv_fp8 needs head_dim 64 or 128 (got %d)", spec->head_dim);
+    }
     if (opts && opts->weight_fp4) {
         QIE_REQUIRE(opts->weight_fp4 == 1 || opts->weight_fp4 == 2,
                     "qie_engine_create: weight_fp4 is 0, 1 (codes + dequantised copy) or 2 (codes only), not %d", opts->weight_fp4);
@@ -1651,6 +1716,9 @@ static int commit_kv_writes(qie_batch* b, const KvWrites& w) {
         PagePool::CopyJob jobs[kMaxBatchSlots];
         const int n_jobs = b->pool.commit(w.r, jobs);
         b->table_dirty = true;
+        // (an fp8-KV batch shares no page: forks and prefix handles are refused; qie_kv_copy_fp8 is
+        // the copy their support will call here)
+        QIE_REQUIRE(!(b->kv8 && n_jobs), "internal: a shared page on an fp8-KV batch");
         const qie_kv_cache c = batch_cache(b, 0);
         for (int j = 0; j < n_jobs; j++) {
             b->pool.row(b->B)[jobs[j].index] = jobs[j].old_page;
@@ -1827,6 +1895,7 @@ int qie_batch_slot_sampling(const qie_batch* b, int32_t seq, qie_slot_sampling* 
 int qie_batch_fork(qie_batch* b, int32_t src, int32_t dst, int32_t n_tokens, int32_t step_offset) {
     QIE_REQUIRE(b && src >= 0 && src < b->B && dst >= 0 && dst < b->B && src != dst,
                 "qie_batch_fork: bad arguments (two different slots of the batch)");
+    QIE_NO_KV8(b, "qie_batch_fork");
     QIE_REQUIRE(!b->idle[src], "qie_batch_fork: slot %d holds no live sequence", src);
     const int p = b->h_pos[src], n = n_tokens;
     QIE_REQUIRE(n >= 1 && n <= p, "qie_batch_fork: n_tokens %d outside [1, %d] (the source's position)", n, p);
@@ -1875,6 +1944,7 @@ int qie_batch_page_refs(qie_batch* b, int32_t* host_refs, int32_t n) {
 
 int qie_batch_prefix_save(qie_batch* b, int32_t seq, int32_t n_tokens, qie_kv_prefix** out) {
     QIE_REQUIRE(b && out && seq >= 0 && seq < b->B, "qie_batch_prefix_save: bad arguments");
+    QIE_NO_KV8(b, "qie_batch_prefix_save");
     QIE_REQUIRE(b->d_table, "qie_batch_prefix_save: prefix handles need a paged batch");
     QIE_REQUIRE(!b->idle[seq], "qie_batch_prefix_save: slot %d holds no live sequence", seq);
     QIE_REQUIRE(n_tokens > 0 && n_tokens % b->page_tokens == 0 && n_tokens <= b->h_pos[seq],
@@ -1900,6 +1970,7 @@ int qie_batch_prefix_save(qie_batch* b, int32_t seq, int32_t n_tokens, qie_kv_pr
 int qie_batch_prefix_load(qie_batch* b, const qie_kv_prefix* p, int32_t dst, int32_t n_tokens, int32_t token) {
     QIE_REQUIRE(b && p && dst >= 0 && dst < b->B && token >= 0 && token < b->e->spec.vocab,
                 "qie_batch_prefix_load: bad arguments");
+    QIE_NO_KV8(b, "qie_batch_prefix_load");
     QIE_REQUIRE(b->d_table && p->owner == b, "qie_batch_prefix_load: the handle belongs to another batch");
     QIE_REQUIRE(n_tokens > 0 && n_tokens % b->page_tokens == 0 && n_tokens <= (int)p->ids.size() &&
                     n_tokens + 1 < b->max_ctx,
@@ -1973,9 +2044,23 @@ static int batch_create(qie_engine* e, int32_t batch, int32_t max_ctx, int32_t p
     // tags (-1: no position).  Never reallocated: the decode graph and the persistent step's
     // attention table hold pointers into it.
     auto make = [&]() -> int {
-        const size_t pool = (size_t)n_runs * b->seq_stride * 2;
+        b->kv8 = e->opts.kv_fp8 != 0;
+        const size_t pool = (size_t)n_runs * b->seq_stride * (b->kv8 ? 1 : 2);
         QIE_TRY(dmalloc((void**)&b->kc, pool));
         QIE_TRY(dmalloc((void**)&b->vc, pool));
+        if (b->kv8) {   // exponents (0 = never written) and the staging cache
+            b->exp_stride = b->seq_stride / hd;
+            b->stage_stride = (int64_t)sh.nkv * (max_ctx + b->run_pad) * hd;
+            const size_t eb = (size_t)n_runs * b->exp_stride, sb = (size_t)batch * b->stage_stride * 2;
+            QIE_TRY(dmalloc((void**)&b->ke, eb));
+            QIE_TRY(dmalloc((void**)&b->ve, eb));
+            QIE_TRY(dmalloc((void**)&b->sk, sb));
+            QIE_TRY(dmalloc((void**)&b->sv, sb));
+            QIE_HIP(hipMemsetAsync(b->ke, 0, eb, e->stream));
+            QIE_HIP(hipMemsetAsync(b->ve, 0, eb, e->stream));
+            QIE_HIP(hipMemsetAsync(b->sk, 0, sb, e->stream));
+            QIE_HIP(hipMemsetAsync(b->sv, 0, sb, e->stream));
+        }
         if (page_tokens > 0) QIE_TRY(dmalloc((void**)&b->d_table, b->pool.table.size() * 4));
         RowDims d = row_dims(e, batch);
         d.samp_ws_bytes = qie_sample_workspace_bytes(batch, s.vocab);
@@ -2025,7 +2110,7 @@ void qie_batch_destroy(qie_batch* b) {
     free_rows(b->pf);
     free_rows(b->v);
     free_rows(b->sc);
-    for (void* p : {(void*)b->kc, (void*)b->vc, (void*)b->d_table, b->pk_mem, (void*)b->d_layers, b->d_attp,
+    for (void* p : {(void*)b->kc, (void*)b->vc, (void*)b->ke, (void*)b->ve, (void*)b->sk, (void*)b->sv, (void*)b->d_table, b->pk_mem, (void*)b->d_layers, b->d_attp,
                     (void*)b->pk_ts, (void*)b->d_slots, b->rows_ws, (void*)b->vb_aux})
         if (p) hipFree(p);
     for (void* p : b->retired) hipFree(p);
@@ -2180,7 +2265,10 @@ static int prefill_rows(qie_batch* b, int seq0, int n_seqs, const int32_t* ids, 
     hipLaunchKernelGGL(iota_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b->pf.pos, (int)n, len, pos0);
     hipLaunchKernelGGL(copy_ids_kernel, dim3((len + 255) / 256, n_seqs), dim3(256), 0, st, b->pf.ids_in,
                        b->dec.hist + (int64_t)seq0 * b->max_ctx + pos0, len, (int64_t)b->max_ctx);
-    QIE_TRY(enqueue_prompt_layers(b, layer_rows(b->pf, n, len), batch_cache(b, seq0),
+    LayerRows rows = layer_rows(b->pf, n, len);
+    rows.seq0 = seq0;
+    rows.pos0 = pos0;
+    QIE_TRY(enqueue_prompt_layers(b, rows, batch_cache(b, seq0),
                                   append ? qie_attention_extend : qie_attention));
     // position of each last prompt token; finalize advances it to pos0 + len (the new token).
     for (int z = 0; z < n_seqs; z++)
@@ -2231,6 +2319,7 @@ int qie_prefill_ragged(qie_batch* b, const qie_prefill_seg* segs, int32_t n_segs
     const char* who = "qie_prefill_ragged";
     QIE_REQUIRE(b && segs && ids && n_segs >= 1 && n_segs <= b->B && n_segs <= QIE_RAGGED_MAX_SEGS,
                 "%s: bad arguments (1 .. min(B, %d) segments)", who, QIE_RAGGED_MAX_SEGS);
+    QIE_NO_KV8(b, who);
     qie_engine* e = b->e;
     const qie_model_spec& s = e->spec;
     QIE_REQUIRE(!e->opts.prefill_fp8,
@@ -2557,6 +2646,7 @@ int qie_verify(qie_batch* b, int32_t seq, const int32_t* draft, int32_t n_draft,
                int32_t* out_ids, int32_t* n_out) {
     QIE_REQUIRE(b && out_ids && n_out && seq >= 0 && seq < b->B && n_draft >= 0 && (n_draft == 0 || draft),
                 "qie_verify: bad arguments");
+    QIE_NO_KV8(b, "qie_verify");
     QIE_REQUIRE(n_draft + 1 <= QIE_VERIFY_MAX_ROWS, "qie_verify: %d drafts exceed the %d rows of a step (at most %d)",
                 n_draft, QIE_VERIFY_MAX_ROWS, QIE_VERIFY_MAX_ROWS - 1);
     qie_engine* e = b->e;
@@ -2710,6 +2800,7 @@ int qie_verify_batch(qie_batch* b, const qie_verify_seg* segs, int32_t n_segs, c
     const char* who = "qie_verify_batch";
     QIE_REQUIRE(b && segs && out_ids && n_out && n_segs >= 1 && n_segs <= b->B && n_segs <= QIE_RAGGED_MAX_SEGS,
                 "%s: bad arguments (1 .. min(B, %d) segments)", who, QIE_RAGGED_MAX_SEGS);
+    QIE_NO_KV8(b, who);
     qie_engine* e = b->e;
     const qie_model_spec& s = e->spec;
     QIE_REQUIRE(!(e->fp8 && e->opts.prefill_fp8),
@@ -2798,6 +2889,7 @@ int qie_batch_set_decode_mode(qie_batch* b, int32_t mode) {
     QIE_REQUIRE(b && (mode == 0 || mode == 1), "qie_batch_set_decode_mode: bad arguments (mode 0 or 1)");
     qie_engine* e = b->e;
     if (mode == 1) {
+        QIE_NO_KV8(b, "qie_batch_set_decode_mode(1)");
         const char* why = "";
         QIE_REQUIRE(persist_supported(e->spec, b->B, e->sh.tp, e->fp8, e->fp4, b->d_table != nullptr, device_cu_count(), &why),
                     "qie_batch_set_decode_mode: the persistent decode step does not cover this batch (%s)", why);
@@ -2872,7 +2964,23 @@ int qie_batch_dims(const qie_batch* b, int32_t* batch, int32_t* max_ctx) {
 
 int qie_batch_kv_cache(const qie_batch* b, int32_t seq, qie_kv_cache* out) {
     QIE_REQUIRE(b && out && seq >= 0 && seq < b->B, "qie_batch_kv_cache: bad arguments");
+    QIE_REQUIRE(!b->kv8, "qie_batch_kv_cache: an fp8-KV batch has no bf16 cache (use qie_batch_kv_cache_fp8)");
     *out = batch_cache(b, seq);
+    return 0;
+}
+
+int qie_batch_kv_cache_fp8(const qie_batch* b, int32_t seq, qie_kv_cache_fp8* out) {
+    QIE_REQUIRE(b && out && seq >= 0 && seq < b->B, "qie_batch_kv_cache_fp8: bad arguments");
+    QIE_REQUIRE(b->kv8, "qie_batch_kv_cache_fp8: not an fp8-KV batch (qie_engine_opts.kv_fp8)");
+    *out = batch_cache8(b, seq);
+    return 0;
+}
+
+int qie_batch_kv_bytes(const qie_batch* b, int64_t* bytes) {
+    QIE_REQUIRE(b && bytes, "qie_batch_kv_bytes: bad arguments");
+    const int64_t runs = b->d_table ? b->n_pages : b->B;
+    *bytes = 2 * runs * b->seq_stride * (b->kv8 ? 1 : 2);                                   // K and V
+    if (b->kv8) *bytes += 2 * runs * b->exp_stride + 2 * (int64_t)b->B * b->stage_stride * 2;   // exponents, staging
     return 0;
 }
 
@@ -2974,6 +3082,7 @@ static int time_persistent(qie_batch* b, int iters, double* avg_us, double* byte
 int qie_batch_time_kernel(qie_batch* b, int32_t which, int32_t iters, double* avg_us, double* bytes) {
     QIE_REQUIRE(b && iters > 0 && avg_us && bytes && which >= 0 && which <= 6, "qie_batch_time_kernel: bad arguments");
     qie_engine* e = b->e;
+    if (which >= 5) QIE_NO_KV8(b, "qie_batch_time_kernel (which 5 / 6)");
     if (which == 6) return time_persistent(b, iters, avg_us, bytes);
     const qie_model_spec& s = e->spec;
     const TpShard& sh = e->sh;   // this rank's shard sizes
@@ -3034,6 +3143,7 @@ int qie_batch_time_kernel(qie_batch* b, int32_t which, int32_t iters, double* av
 
 int qie_batch_debug_step(qie_batch* b, const qie_sampling* smp, int32_t* next_ids, void* host_x) {
     QIE_REQUIRE(b && host_x, "qie_batch_debug_step: bad arguments");
+    QIE_NO_KV8(b, "qie_batch_debug_step");
     qie_engine* e = b->e;
     const int64_t n = (int64_t)b->B * e->spec.hidden, slots = 2 * (int64_t)e->spec.n_layers + 1;
     QIE_TRY(prepare_steps(b, 1, "qie_batch_debug_step"));

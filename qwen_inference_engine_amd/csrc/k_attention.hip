@@ -275,6 +275,11 @@ template <int HD, bool PG, int NWA, bool PR, int KS = kDecMStep>
 __global__ __launch_bounds__(64 * NWA) void attn_decode_mfma2_kernel(DecodeAttnParams a) {
     attn_decode_mfma2_body<HD, PG, NWA, PR, KS>(a, blockIdx.x, blockIdx.y);
 }
+// the same body on an fp8 KV cache (attn_decode.hpp, KV8)
+template <int HD, bool PG, bool PR, int KS = kDecMStep>
+__global__ __launch_bounds__(256) void attn_decode_kv8_kernel(DecodeAttnParams a, Kv8Exps ex) {
+    attn_decode_mfma2_body<HD, PG, 4, PR, KS, AttnNoHook, true>(a, blockIdx.x, blockIdx.y, nullptr, &ex);
+}
 
 
 // Diagnostics: lane l reads the 8 bytes at element 4*l of an LDS array holding
@@ -302,7 +307,8 @@ void set_decode_rope_cur(const float* rc) { g_rope_cur = rc; }
 
 static int fill_dec_params(DecodeAttnParams& a, const void* qkv, int64_t B, const int32_t* pos, const void* q_norm,
                            const void* k_norm, const float* rope_cos, const float* rope_sin, int32_t n_heads,
-                           const qie_kv_cache* cache, int32_t layer, float eps, int32_t numerics, void* out, void* ws) {
+                           const qie_kv_cache* cache, int32_t layer, float eps, int32_t numerics, void* out, void* ws,
+                           const char* who = "qie_attention_decode", bool kv8 = false) {
     a.qkv = (const uint16_t*)qkv;
     a.pos = pos;
     a.q_norm = (const uint16_t*)q_norm;
@@ -311,7 +317,7 @@ static int fill_dec_params(DecodeAttnParams& a, const void* qkv, int64_t B, cons
     a.sn = rope_sin;
     a.kc = (uint16_t*)cache->k;
     a.vc = (uint16_t*)cache->v;
-    QIE_TRY(kv_map_make(cache, &a.km, "qie_attention_decode"));
+    QIE_TRY(kv_map_make(cache, &a.km, who));
     a.layer = layer;
     a.nkv = cache->n_kv_heads;
     a.nq = n_heads;
@@ -330,20 +336,22 @@ static int fill_dec_params(DecodeAttnParams& a, const void* qkv, int64_t B, cons
     // block per kv head — measured equal, attention 7.94 vs 7.96 µs live, 1,446 vs 1,454 tok/s:
     // the second step's chain is not what the launch waits on).
     const int hd = cache->head_dim;
+    // The fp8 form (kv8): 128, or 256 at either head_dim (dev A/B, attn_decode.hpp: slower).
     const int ks_env = dev_env("QIE_DEC_KS", 0);
-    // (a step never straddles a page: 256-key steps need pages of >= 256 tokens)
-    const bool ks256_ok = hd == 64 && (cache->block_table == nullptr || cache->page_tokens >= 256);
+    // (a step never straddles a page: 256-key steps need pages of a multiple of 256 tokens)
+    const bool ks256_ok = (hd == 64 || kv8) && (cache->block_table == nullptr || cache->page_tokens % 256 == 0);
     int ks = kDecMStep;
-    if (ks_env == 128 || (ks_env == 256 && ks256_ok) || (ks_env == 64 && hd == 128 && !(numerics & QIE_ATTN_PREROPED)))
+    if (ks_env == 128 || (ks_env == 256 && ks256_ok) ||
+        (ks_env == 64 && hd == 128 && !kv8 && !(numerics & QIE_ATTN_PREROPED)))
         ks = ks_env;
     a.ks = ks;
     a.nsplit_max = std::min(a.splits_target, (cache->max_ctx + ks - 1) / ks);
-    QIE_REQUIRE(a.nsplit_max <= kDecMaxSplits, "qie_attention_decode: max_ctx %d too long", cache->max_ctx);
+    QIE_REQUIRE(a.nsplit_max <= kDecMaxSplits, "%s: max_ctx %d too long", who, cache->max_ctx);
     a.eps = eps;
     a.numerics = numerics & QIE_NUMERICS_MASK;
     a.pre_roped = (numerics & QIE_ATTN_PREROPED) != 0;
     QIE_REQUIRE(!a.pre_roped || (q_norm == nullptr && k_norm == nullptr && a.numerics == QIE_NUMERICS_REF),
-                "qie_attention_decode: QIE_ATTN_PREROPED needs REF numerics without qk-norm");
+                "%s: QIE_ATTN_PREROPED needs REF numerics without qk-norm", who);
     const int64_t cnt = ((B * a.nkv * 4 + 255) / 256) * 256;
     a.counters = (unsigned*)ws;
     a.part_o = (float*)((char*)ws + cnt);
@@ -501,6 +509,40 @@ int qie_attention_decode(const void* qkv, int64_t B, const int32_t* pos, const v
     QIE_REQUIRE(a.ks == 128 || (a.ks == 64 && cache->head_dim == 128 && !pr) || (a.ks == 256 && cache->head_dim == 64),
                 "qie_attention_decode: internal: no kernel for %d-key steps at hd %d", a.ks, cache->head_dim);
     hipLaunchKernelGGL(k2, grid, dim3(256), 0, (hipStream_t)stream, a);
+    QIE_LAUNCH_CHECK();
+    return 0;
+}
+
+int qie_attention_decode_fp8(const void* qkv, int64_t B, const int32_t* pos, const void* q_norm, const void* k_norm,
+                             const float* rope_cos, const float* rope_sin, int32_t n_heads,
+                             const qie_kv_cache_fp8* cache, int32_t layer, float eps, int32_t numerics, void* out,
+                             void* ws, void* stream) {
+    QIE_REQUIRE(qkv && pos && cache && cache->c.k && cache->c.v && rope_cos && rope_sin && out && ws && B > 0,
+                "qie_attention_decode_fp8: bad arguments");
+    const qie_kv_cache& c = cache->c;
+    QIE_REQUIRE(c.n_kv_heads > 0 && n_heads % c.n_kv_heads == 0 && n_heads / c.n_kv_heads <= kMaxGroup,
+                "qie_attention_decode_fp8: n_heads/n_kv_heads must be an integer <= %d", kMaxGroup);
+    QIE_REQUIRE(layer >= 0 && layer < c.n_layers, "qie_attention_decode_fp8: bad layer");
+    DecodeAttnParams a;
+    QIE_TRY(fill_dec_params(a, qkv, B, pos, q_norm, k_norm, rope_cos, rope_sin, n_heads, &c, layer, eps, numerics, out,
+                            ws, "qie_attention_decode_fp8", true));
+    Kv8Exps ex;
+    QIE_TRY(kv8_exps_make(cache, a.km, &ex, "qie_attention_decode_fp8"));   // head_dim 64 / 128
+    dim3 grid((unsigned)(a.nkv * a.nsplit_max), (unsigned)B);
+    const bool pg = a.km.table != nullptr, pr = a.pre_roped != 0;
+    auto k2 = c.head_dim == 128
+                  ? (pr ? (pg ? attn_decode_kv8_kernel<128, true, true> : attn_decode_kv8_kernel<128, false, true>)
+                        : (pg ? attn_decode_kv8_kernel<128, true, false> : attn_decode_kv8_kernel<128, false, false>))
+                  : (pr ? (pg ? attn_decode_kv8_kernel<64, true, true> : attn_decode_kv8_kernel<64, false, true>)
+                        : (pg ? attn_decode_kv8_kernel<64, true, false> : attn_decode_kv8_kernel<64, false, false>));
+    if (a.ks == 256)   // 256-key steps (dev A/B)
+        k2 = c.head_dim == 128
+                 ? (pr ? (pg ? attn_decode_kv8_kernel<128, true, true, 256> : attn_decode_kv8_kernel<128, false, true, 256>)
+                       : (pg ? attn_decode_kv8_kernel<128, true, false, 256> : attn_decode_kv8_kernel<128, false, false, 256>))
+                 : (pr ? (pg ? attn_decode_kv8_kernel<64, true, true, 256> : attn_decode_kv8_kernel<64, false, true, 256>)
+                       : (pg ? attn_decode_kv8_kernel<64, true, false, 256> : attn_decode_kv8_kernel<64, false, false, 256>));
+    QIE_REQUIRE(a.ks == 128 || a.ks == 256, "qie_attention_decode_fp8: internal: no kernel for %d-key steps", a.ks);
+    hipLaunchKernelGGL(k2, grid, dim3(256), 0, (hipStream_t)stream, a, ex);
     QIE_LAUNCH_CHECK();
     return 0;
 }

@@ -11,6 +11,7 @@
 //   kv_copy_layer_to_cache_{prefill,decode} layers/src/include_cuda.cu:165-279
 #include "qie_common.hpp"
 #include "launch_util.hpp"
+#include "qkv_post.hpp"
 #include "../../include/qie/qie_ops.h"
 
 #include <cmath>
@@ -176,47 +177,7 @@ __global__ __launch_bounds__(256) void rmsnorm_reg_kernel(const uint4* __restric
 }
 
 // ------------------------------------------- q/k post-projection + KV append
-// Block per row, one wave per head.  Each lane owns one RoPE pair:
-//   REF: (2*lane, 2*lane+1) interleaved (RoPE.cu:12-18)
-//   HF : (lane, lane + hd/2) rotate_half
-// qk-norm (Qwen3 only) is the per-head RMSNorm of qk_norm.cu:43-79.
-struct QkvPostArgs {
-    const uint16_t* qkv;
-    const int32_t* pos;
-    int rows_per_seq;
-    const uint16_t* q_norm;
-    const uint16_t* k_norm;
-    const float* cs;
-    const float* sn;
-    int nq, nkv, hd;
-    uint16_t* kc;
-    uint16_t* vc;
-    KvMap km;
-    int layer;
-    float eps;
-    int numerics;
-    uint16_t* q_out;
-};
-
-// Round 6: the wave's heads are taken in batches of kQkvBatch whose source pairs are all
-// loaded before the first store (the row-at-a-time form waited one memory round trip per head,
-// nine in a row per wave at Qwen2-7B widths); the arithmetic per element is unchanged.
-constexpr int kQkvBatch = 10;
-
-// The ragged form (qie_qkv_post_ragged): the row's sequence comes from a segment table held by
-// value in the arguments instead of m / rows_per_seq; nothing else differs.
-struct QkvPostRaggedArgs : QkvPostArgs {
-    qie_row_segs segs;
-};
-__device__ __forceinline__ int64_t qkv_row_seq(const QkvPostArgs& a, int64_t m) { return m / a.rows_per_seq; }
-__device__ __forceinline__ int64_t qkv_row_seq(const QkvPostRaggedArgs& a, int64_t m) {
-    int seq = a.segs.seq[0];   // constant indices only: the table stays in scalar registers
-#pragma unroll
-    for (int z = 1; z < QIE_RAGGED_MAX_SEGS; z++)
-        if (z < a.segs.n && m >= a.segs.row0[z]) seq = a.segs.seq[z];
-    return seq;
-}
-
+// (arguments and the per-pair arithmetic: qkv_post.hpp, shared with the fp8-KV writer)
 template <bool PG, bool HF, class Args = QkvPostArgs>
 __global__ __launch_bounds__(256) void qkv_post_kernel(Args a) {
 #pragma clang fp contract(off)
@@ -265,30 +226,8 @@ __global__ __launch_bounds__(256) void qkv_post_kernel(Args a) {
                 dst = a.vc + kv_run_off(a.km, (int64_t)a.layer * a.nkv + g, hd) + kv_tok<PG>(a.km, seq, p, hd);
                 rope = false;
             }
-            float x0 = active ? bf2f((uint16_t)(raw[b] & 0xffffu)) : 0.f;
-            float x1 = active ? bf2f((uint16_t)(raw[b] >> 16)) : 0.f;
-            if (rope && nw) {
-                float ss = wave_sum(x0 * x0 + x1 * x1);
-                float rms = sqrtf((ss / (float)hd) + a.eps);
-                if (HF) {
-                    float inv = 1.0f / rms;
-                    x0 = rbf(bf2f(nw[i0]) * rbf(x0 * inv));
-                    x1 = rbf(bf2f(nw[i1]) * rbf(x1 * inv));
-                } else {
-                    x0 = rbf((x0 / rms) * bf2f(nw[i0]));
-                    x1 = rbf((x1 / rms) * bf2f(nw[i1]));
-                }
-            }
-            float y0 = x0, y1 = x1;
-            if (rope) {
-                if (HF) {
-                    y0 = rbf(rbf(x0 * c) + rbf(-x1 * s));
-                    y1 = rbf(rbf(x1 * c) + rbf(x0 * s));
-                } else {
-                    y0 = x0 * c - x1 * s;
-                    y1 = x1 * c + x0 * s;
-                }
-            }
+            float y0, y1;
+            qkv_post_pair<HF>(raw[b], active, rope, nw, i0, i1, c, s, hd, a.eps, y0, y1);
             if (active) {
                 if (HF) {
                     dst[i0] = f2bf(y0);

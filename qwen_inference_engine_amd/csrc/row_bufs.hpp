@@ -97,6 +97,7 @@ struct LayerRows {
     const int32_t* pos;                     // [M] positions on device; consecutive runs of
     int32_t rows_per_seq;                   //   rows_per_seq rows belong to one sequence
     const qie_row_segs* segs;               // set (host table): segments of any lengths instead
+    int32_t seq0 = 0, pos0 = 0;             // fp8-KV prompt passes (prefill_rows): the rows' first slot and position
 };
 inline LayerRows layer_rows(const RowBufs& r, int64_t M, int32_t rows_per_seq, const qie_row_segs* segs = nullptr) {
     return LayerRows{M, r.x, r.xn, r.qkv, r.q, r.att, r.h, r.part, r.pos, rows_per_seq, segs};

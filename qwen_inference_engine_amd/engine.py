@@ -179,7 +179,7 @@ class Comm:
 class Engine:
     def __init__(self, spec: ModelSpec, device: int = 0, max_ctx: int = 4096, use_graph: bool = True,
                  comm: Optional[Comm] = None, weight_fp8: bool = False, comm_always: bool = False,
-                 prefill_fp8: bool = False, weight_fp4: bool = False):
+                 prefill_fp8: bool = False, weight_fp4: bool = False, kv_fp8: bool = False):
         self.lib = _lib.load()
         self.spec = spec
         self._spec_c = spec.to_c()
@@ -197,6 +197,11 @@ class Engine:
         # HostWeights.fp4_dequantized(head_fp8=weight_fp8).  True / 1 keeps the dequantised bf16 copy
         # for passes of more than 16 rows; 2 keeps the codes alone (those passes run the MXFP4 GEMM)
         opts.weight_fp4 = int(weight_fp4)
+        # every batch holds an fp8 KV cache (e4m3 rows with per-row exponents): decode
+        # reads the codes, the prompt passes attend over the dequantised rows.  Forks, prefix handles,
+        # verify steps, ragged prefills and the persistent decode mode are refused on such batches
+        opts.kv_fp8 = int(kv_fp8)
+        self.kv_fp8 = bool(kv_fp8)
         self.comm = comm
         self._fp8 = weight_fp8
         h = C.c_void_p()
@@ -618,6 +623,18 @@ class Batch:
         c = _lib.KvCacheC()
         _lib.check(self.lib.qie_batch_kv_cache(self.h, seq, C.byref(c)), "qie_batch_kv_cache")
         return c
+
+    def kv_cache_fp8(self, seq: int) -> _lib.KvCacheFp8C:
+        """Raw fp8 KV descriptor of slot `seq` of an Engine(kv_fp8=True) batch."""
+        c = _lib.KvCacheFp8C()
+        _lib.check(self.lib.qie_batch_kv_cache_fp8(self.h, seq, C.byref(c)), "qie_batch_kv_cache_fp8")
+        return c
+
+    def kv_bytes(self) -> int:
+        """Device bytes of the batch's K/V pools (fp8: codes + exponents + the staging cache)."""
+        n = C.c_int64()
+        _lib.check(self.lib.qie_batch_kv_bytes(self.h, C.byref(n)), "qie_batch_kv_bytes")
+        return n.value
 
     def kv_rows(self, seq: int, layer: int, n: int):
         """Host copy of the cached K and V rows [n_kv_heads][n][head_dim] (bf16 bits) of

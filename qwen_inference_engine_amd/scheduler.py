@@ -199,6 +199,9 @@ class ContinuousBatcher:
         # captured per table (which slots, how many drafts each): a table the bounded cache has
         # not seen pays a capture first ("first call": 0.5 - 0.9 ms on
         # Qwen2-7B; the hit rate of a real request mix has not been measured).
+        if getattr(engine, "kv_fp8", False) and (ragged_prefill or drafter is not None or prefix_cache_pages):
+            raise ValueError("an fp8-KV engine (kv_fp8) refuses ragged prefills, verify steps and prefix handles: "
+                             "ragged_prefill, drafter and prefix_cache_pages cannot be used with it")
         self.drafter = drafter
         self.draft_tokens = int(draft_tokens)
         if drafter is not None and not 0 <= self.draft_tokens <= VERIFY_MAX_ROWS - 1:
