@@ -554,6 +554,19 @@ int qie_attention_decode_fp8(const void* qkv, int64_t B, const int32_t* pos, con
                              const void* k_norm, const float* rope_cos, const float* rope_sin,
                              int32_t n_heads, const qie_kv_cache_fp8* cache, int32_t layer, float eps,
                              int32_t numerics, void* out, void* ws, void* stream);
+/* qie_attention_extend's contract on an fp8 cache (row m attends to [0, pos[m]] of sequence
+ * m / rows_per_seq, the rows' own K/V already in the cache QUANTISED; head_dim 64 and 128, the same
+ * group limit, contiguous and paged; the same grid, split length, workspace
+ * (qie_attention_extend_workspace_bytes, need not be initialised) and merge launch).  The split-context
+ * tile walk reads the codes itself: a 64-key tile of codes goes global -> LDS once, is expanded there
+ * into bf16 images with each row's scale as the conversion's operand, and everything after that is
+ * the bf16 kernel's arithmetic in its sum orders: the result is, bit for bit, qie_attention_extend's on
+ * the bf16 cache holding the dequantised rows.  Rows past the last position of a block contribute
+ * exact zeros whatever codes and exponents the cache holds there.  -22, naming the op, for a bad
+ * head shape, layer, exponent array or alignment; nothing is launched. */
+int qie_attention_extend_fp8(const void* q, int64_t M, const int32_t* pos, int32_t rows_per_seq,
+                             const qie_kv_cache_fp8* cache, int32_t layer, int32_t n_heads,
+                             void* out, void* ws, void* stream);
 /* The K and V rows [pos0, pos0 + n_rows) of every kv head of layer `layer` of sequence src_seq,
  * expanded exactly to bf16 at the same positions of layer dst_layer of sequence dst_seq of `dst`
  * (a contiguous bf16 cache with the same n_kv_heads and head_dim), one launch; a paged source is

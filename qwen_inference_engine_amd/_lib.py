@@ -176,6 +176,7 @@ SIGNATURES = [
                                    C.POINTER(KvCacheFp8C), C.POINTER(KvCacheC), _I32, _F, _I32, _P, _P]),
     ("qie_attention_decode_fp8", C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _I32, C.POINTER(KvCacheFp8C), _I32, _F,
                                            _I32, _P, _P, _P]),
+    ("qie_attention_extend_fp8", C.c_int, [_P, _I64, _P, _I32, C.POINTER(KvCacheFp8C), _I32, _I32, _P, _P, _P]),
     ("qie_kv_dequantize_fp8", C.c_int, [C.POINTER(KvCacheFp8C), _I32, _I32, _I32, _I32, C.POINTER(KvCacheC), _I32,
                                         _I32, _P]),
     ("qie_kv_copy_fp8", C.c_int, [C.POINTER(KvCacheFp8C), _I32, C.POINTER(KvCacheFp8C), _I32, _I32, _I32, _P]),

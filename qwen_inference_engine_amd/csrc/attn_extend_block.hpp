@@ -26,15 +26,21 @@ struct ExtendAttnParams {
     float* part_ml;   // [M][nq][nsplit][2]: running max (log2 domain), sum
     uint16_t* out;    // [M][nq*HD]
 };
+// ... on an fp8 KV cache (attn_extend_fp8_kernel): kc / vc point at e4m3 codes, km counts bytes
+struct ExtendAttnParams8 : ExtendAttnParams {
+    Kv8Exps ex;
+};
 
 // The workgroup of (rows [row0, row0 + R) of the call, which belong to cache sequence seq;
 // block blk of their flattened rows; split s; kv head kvh).  256 threads.  Wave w owns the
 // block's 16-row groups (w, 7 - w): positions are non-decreasing in the flattened row index, so
 // the pair evens out the rows' own causal triangle as in the prefill kernel; the rectangle over
 // the prefix is the same for every group.
-template <int HD, bool PG>
-__device__ __forceinline__ void attn_extend_block(const ExtendAttnParams& a, const int seq, const int64_t row0,
-                                                  const int R, const int blk, const int s, const int kvh) {
+// KV8 (P = ExtendAttnParams8): the walk reads an fp8 cache (attn_mfma_walk's KV8 form); rows,
+// splits, partials and stores are the same code.
+template <int HD, bool PG, bool KV8 = false, class P>
+__device__ __forceinline__ void attn_extend_block(const P& a, const int seq, const int64_t row0, const int R,
+                                                  const int blk, const int s, const int kvh) {
     constexpr int NW = 4;
     constexpr int KT = 64;
     constexpr int KSTEPS = HD / 32;
@@ -69,8 +75,11 @@ __device__ __forceinline__ void attn_extend_block(const ExtendAttnParams& a, con
     const int nkt = min((k0 + a.split_len) / KT, kmax / KT + 1);   // tiles [k0 / KT, nkt); past kmax: not loaded
 
     const int64_t head_off = kv_run_off(a.km, (int64_t)a.layer * a.nkv + kvh, HD);
-    const uint16_t* kb = a.kc + head_off;
-    const uint16_t* vb = a.vc + head_off;
+    // (KV8: offsets are in elements = bytes)
+    const uint16_t* kb = KV8 ? reinterpret_cast<const uint16_t*>(reinterpret_cast<const uint8_t*>(a.kc) + head_off)
+                             : a.kc + head_off;
+    const uint16_t* vb = KV8 ? reinterpret_cast<const uint16_t*>(reinterpret_cast<const uint8_t*>(a.vc) + head_off)
+                             : a.vc + head_off;
 
     const int grp[QG] = {wave, NGB - 1 - wave};
     bool gact[QG];
@@ -93,7 +102,11 @@ __device__ __forceinline__ void attn_extend_block(const ExtendAttnParams& a, con
 
     f32x4_t oacc[QG][DT];
     float m_run[QG], l_run[QG];
-    attn_mfma_walk<HD, PG, NW, true>(kb, vb, a.km, seq, kmax, k0, nkt, qf, qpos, gpos, gmin, oacc, m_run, l_run);
+    if constexpr (KV8)
+        attn_mfma_walk<HD, PG, NW, true, true>(kb, vb, a.km, seq, kmax, k0, nkt, qf, qpos, gpos, gmin, oacc, m_run, l_run,
+                                               &a.ex, kv_run_off(a.ex.em, (int64_t)a.layer * a.nkv + kvh, 1));
+    else
+        attn_mfma_walk<HD, PG, NW, true>(kb, vb, a.km, seq, kmax, k0, nkt, qf, qpos, gpos, gmin, oacc, m_run, l_run);
 
     // every real row of the block leaves its slot, also the rows this split showed no key
     // ((-inf, 0) and a zero O): the workspace is never assumed initialised

@@ -38,12 +38,24 @@ namespace qie {
 // the running max (log2 domain) and the sum of each lane's row (lane & 15).
 // Dynamic LDS: 2 operands x 2 buffers x 64 keys x HD bf16.
 // SPLIT: the walk may show a row no key at all (see the exponent base below).
-template <int HD, bool PG, int NW, bool SPLIT>
+// KV8 (the fp8 KV cache, kv_fp8.hpp; NW = 4): kb / vb are byte addresses of e4m3 codes, ex the
+// cache's exponent arrays and ehead the (layer, kv head) run's offset in them.  The codes go
+// global -> LDS by the same per-tile bounded LDS-DMA (double-buffered, a linear copy of the tile:
+// 64 x HD bytes per operand), and once per tile the workgroup expands them into ONE bf16 K image
+// and ONE bf16 V image with the bf16 walk's swizzles: thread t converts 16 HD / 64 codes of key row
+// t / 4 of each operand, v_cvt_scalef32_pk_bf16_fp8 with the row's scale as its operand.  The tile
+// body then reads those images and is the bf16 walk's, instruction for instruction: the result is
+// bit for bit the bf16 walk's on a cache holding the dequantised rows.  Rows past kmax: the codes
+// read as zeros (the bounded resource) and their exponent bytes are never read (scale 1), so they
+// are exact zeros whatever the cache holds.  Dynamic LDS: 2 bf16 images + 2 operands x 2 code buffers, the
+// bf16 walk's byte count.
+template <int HD, bool PG, int NW, bool SPLIT, bool KV8 = false>
 __device__ __forceinline__ void attn_mfma_walk(const uint16_t* kb, const uint16_t* vb, const KvMap& km, const int seq,
                                                const int kmax, const int k0, const int nkt,
                                                const bf16x8_t (&qf)[2][HD / 32], const int (&qpos)[2],
                                                const int (&gpos)[2], const int (&gmin)[2], f32x4_t (&oacc)[2][HD / 16],
-                                               float (&m_run)[2], float (&l_run)[2]) {
+                                               float (&m_run)[2], float (&l_run)[2], const Kv8Exps* ex = nullptr,
+                                               const int64_t ehead = 0) {
     constexpr int KT = 64;
     constexpr int CPR = HD / 8;
     constexpr int KSTEPS = HD / 32;
@@ -51,7 +63,10 @@ __device__ __forceinline__ void attn_mfma_walk(const uint16_t* kb, const uint16_
     constexpr int QG = 2;                  // 16-row query groups per wave
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     uint16_t* Ks = reinterpret_cast<uint16_t*>(smem);
-    uint16_t* Vs = reinterpret_cast<uint16_t*>(smem + 2 * KT * HD * 2);
+    uint16_t* Vs = reinterpret_cast<uint16_t*>(smem + (KV8 ? 1 : 2) * KT * HD * 2);
+    // KV8: the code tiles behind the two bf16 images, [operand][buffer][64 x HD bytes]
+    unsigned char* Kc = smem + 2 * KT * HD * 2;
+    unsigned char* Vc = Kc + 2 * KT * HD;
     // V image chunk swizzle: the 16-B chunk c of key row r sits at c ^ vswz(r).  A
     // ds_read_b64_tr_b16 half-wave reads 8 rows x 32 B at one column; unswizzled, the rows
     // (a whole number of 256-B bank rows apart) hit the same banks: 8-way conflicts.
@@ -80,9 +95,35 @@ __device__ __forceinline__ void attn_mfma_walk(const uint16_t* kb, const uint16_
         koff[i] = (uint32_t)(r * HD + (pch ^ (r & (CPR - 1))) * 8) * 2;
         voff[i] = (uint32_t)(r * HD + (pch ^ vswz(r)) * 8) * 2;
     }
+    // KV8: a 1 KiB wave-instruction is 1024 / HD key rows of codes; this thread's share of the
+    // expansion is C16 16-code chunks from c0 of key row tid / 4, and it holds that row's two scales
+    constexpr int IPW8 = KT * HD / 1024 / NW;
+    constexpr int C16 = HD / 64;
+    static_assert(!KV8 || NW == 4, "attn_mfma_walk: the fp8 form converts with 256 threads");
+    const int crow = tid >> 2, c0 = (tid & 3) * C16;
+    uint32_t ke = 127, ve = 127, ke_n = 127, ve_n = 127;   // e8m0 bytes: this tile's, the prefetched tile's
     auto issue = [&](int kt, int buf) {
         const int64_t tb = kv_tok<PG>(km, seq, kt * KT, HD);
         const int rows = min(KT, kmax + 1 - kt * KT);
+        if constexpr (KV8) {
+            // the tile's exponents are 64 contiguous bytes (a tile never straddles a page).  Loaded
+            // ahead of the DMAs and not touched before the tile is expanded, so that nothing waits
+            // on them here; a row past kmax re-reads the tile's last row's byte and expand drops it
+            const int64_t eo = ehead + kv_tok<PG>(ex->em, seq, kt * KT, 1) + min(crow, rows - 1);
+            ke_n = ex->ke[eo];
+            ve_n = ex->ve[eo];
+            const auto rk = __builtin_amdgcn_make_buffer_rsrc((void*)((const unsigned char*)kb + tb), (short)0, rows * HD,
+                                                              0x00020000);
+            const auto rv = __builtin_amdgcn_make_buffer_rsrc((void*)((const unsigned char*)vb + tb), (short)0, rows * HD,
+                                                              0x00020000);
+#pragma unroll
+            for (int i = 0; i < IPW8; i++) {
+                const int inst = wave * IPW8 + i;
+                buf_lds16(rk, reinterpret_cast<uint16_t*>(Kc + buf * KT * HD + inst * 1024), inst * 1024 + lane * 16);
+                buf_lds16(rv, reinterpret_cast<uint16_t*>(Vc + buf * KT * HD + inst * 1024), inst * 1024 + lane * 16);
+            }
+            return;
+        }
         const auto rk = __builtin_amdgcn_make_buffer_rsrc((void*)(kb + tb), (short)0, rows * HD * 2, 0x00020000);
         const auto rv = __builtin_amdgcn_make_buffer_rsrc((void*)(vb + tb), (short)0, rows * HD * 2, 0x00020000);
 #pragma unroll
@@ -105,6 +146,8 @@ __device__ __forceinline__ void attn_mfma_walk(const uint16_t* kb, const uint16_
     const float sl2 = 1.4426950408889634f / sqrtf((float)HD);   // log2(e) / sqrt(hd)
 
     issue(kt0, 0);
+    ke = ke_n;
+    ve = ve_n;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     int cur = 0;
@@ -236,12 +279,45 @@ __device__ __forceinline__ void attn_mfma_walk(const uint16_t* kb, const uint16_
                 }
             }
         };
+    // KV8: code tile `buf` -> the bf16 images.  Every wave takes part for every tile of the
+    // workgroup, whichever case its own groups are in.
+    auto expand = [&](int kt, int buf) {
+        const bool in = kt * KT + crow <= kmax;   // past kmax: zero codes x scale 1
+        const float ksc = kv8_scale(in ? ke : 127u), vsc = kv8_scale(in ? ve : 127u);
+#pragma unroll
+        for (int i = 0; i < C16; i++) {
+            const uint4 kc = __builtin_bit_cast(
+                uint4, *reinterpret_cast<const bf16x8_t*>(Kc + buf * KT * HD + crow * HD + (c0 + i) * 16));
+            const uint4 vc = __builtin_bit_cast(
+                uint4, *reinterpret_cast<const bf16x8_t*>(Vc + buf * KT * HD + crow * HD + (c0 + i) * 16));
+            const int ch = 2 * (c0 + i);
+            uint16_t* kd = Ks + crow * HD;
+            uint16_t* vd = Vs + crow * HD;
+            *reinterpret_cast<uint4*>(kd + ((ch ^ (crow & (CPR - 1))) * 8)) = fp8x8_to_bf16x8(make_uint2(kc.x, kc.y), ksc);
+            *reinterpret_cast<uint4*>(kd + (((ch + 1) ^ (crow & (CPR - 1))) * 8)) =
+                fp8x8_to_bf16x8(make_uint2(kc.z, kc.w), ksc);
+            *reinterpret_cast<uint4*>(vd + ((ch ^ vswz(crow)) * 8)) = fp8x8_to_bf16x8(make_uint2(vc.x, vc.y), vsc);
+            *reinterpret_cast<uint4*>(vd + (((ch + 1) ^ vswz(crow)) * 8)) = fp8x8_to_bf16x8(make_uint2(vc.z, vc.w), vsc);
+        }
+    };
     int kt = kt0;
     auto run = [&](const int kend, auto q0c, auto q1c) {
         for (; kt < kend; kt++) {
             // into the other buffer: every wave finished tile kt-1 before the last barrier
-            if (kt + 1 < nkt) issue(kt + 1, cur ^ 1);
-            if constexpr (decltype(q0c)::value || decltype(q1c)::value)
+            if (!KV8 && kt + 1 < nkt) issue(kt + 1, cur ^ 1);
+            if constexpr (KV8) {
+                // the images are free (every wave left tile kt-1 at the last barrier) and code
+                // tile kt has landed; the images are read after this barrier.  The prefetch is
+                // issued behind the expansion: the compiler puts a vmcnt(0) in front of the
+                // expansion's LDS reads (it cannot tell them from the DMA's destination), which
+                // would otherwise wait for the tile just requested
+                expand(kt, cur);
+                __syncthreads();
+                if (kt + 1 < nkt) issue(kt + 1, cur ^ 1);
+                ke = ke_n;
+                ve = ve_n;
+                if constexpr (decltype(q0c)::value || decltype(q1c)::value) tile(kt, Ks, Vs, q0c, q1c);
+            } else if constexpr (decltype(q0c)::value || decltype(q1c)::value)
                 tile(kt, Ks + cur * KT * HD, Vs + cur * KT * HD, q0c, q1c);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMAs of tile kt+1
             __syncthreads();                                     // ... and every other wave's

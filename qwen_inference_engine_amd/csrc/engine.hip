@@ -998,16 +998,24 @@ static int enqueue_layer_rows(qie_batch* b, int l, const LayerRows& r, const Lay
     hipStream_t st = e->stream;
     QIE_TRY(run_proj(b, qkv_args(e, L, p.flags, r), p.in, r));
     if (b->kv8) {
-        // fp8 KV (prefill_rows' forms only): the rows below pos0 expanded into the staging cache, the
-        // new rows quantised into the cache and staged dequantised, then the bf16 attention over the
-        // staging cache at its layer 0 — the prompt attends over the values decode will read
+        // fp8 KV (prefill_rows' forms only): the new rows are quantised into the cache, and the prompt
+        // attends over the values decode will read.  Rows that continue a prefix run the split-context
+        // attention on the codes themselves (no expansion, nothing staged).  A fresh prefill stages its
+        // rows dequantised and runs the bf16 attention over the staging cache at its layer 0.
         QIE_REQUIRE(!r.segs, "internal: ragged rows on an fp8-KV batch");
         const qie_kv_cache_fp8 c8 = batch_cache8(b, r.seq0);
-        const qie_kv_cache stage = batch_stage(b, r.seq0);
-        if (r.pos0 >= 1) QIE_TRY(qie_kv_dequantize_fp8(&c8, 0, l, 0, r.pos0, &stage, 0, 0, st));
-        QIE_TRY(qie_qkv_post_fp8(r.qkv, r.M, r.pos, r.rows_per_seq, nullptr, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin,
-                                 e->sh.nq, &c8, &stage, l, s.rms_eps, s.numerics, r.q, st));
-        QIE_TRY(attend(r.q, r.M, r.pos, r.rows_per_seq, &stage, 0, e->sh.nq, r.att, attn_ws, st));
+        if (attend == &qie_attention_extend) {
+            // the fp8 descriptor's run length is the one attn_ws was sized with (prefill_attn_ws_bytes)
+            QIE_REQUIRE(c8.c.max_ctx == b->max_ctx + b->run_pad, "internal: fp8-KV run length");
+            QIE_TRY(qie_qkv_post_fp8(r.qkv, r.M, r.pos, r.rows_per_seq, nullptr, L.q_norm, L.k_norm, e->rope_cos,
+                                     e->rope_sin, e->sh.nq, &c8, nullptr, l, s.rms_eps, s.numerics, r.q, st));
+            QIE_TRY(qie_attention_extend_fp8(r.q, r.M, r.pos, r.rows_per_seq, &c8, l, e->sh.nq, r.att, attn_ws, st));
+        } else {
+            const qie_kv_cache stage = batch_stage(b, r.seq0);
+            QIE_TRY(qie_qkv_post_fp8(r.qkv, r.M, r.pos, r.rows_per_seq, nullptr, L.q_norm, L.k_norm, e->rope_cos,
+                                     e->rope_sin, e->sh.nq, &c8, &stage, l, s.rms_eps, s.numerics, r.q, st));
+            QIE_TRY(attend(r.q, r.M, r.pos, r.rows_per_seq, &stage, 0, e->sh.nq, r.att, attn_ws, st));
+        }
     } else if (r.segs) {
         QIE_TRY(qie_qkv_post_ragged(r.qkv, r.M, r.pos, r.segs, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, e->sh.nq,
                                     &cache, l, s.rms_eps, s.numerics, r.q, st));

@@ -56,6 +56,65 @@ __global__ __launch_bounds__(256, 2) void attn_extend_kernel(ExtendAttnParams a)
     attn_extend_block<HD, PG>(a, seq, row0, R, blockIdx.x, blockIdx.y, kvh);
 }
 
+// ... the same workgroup on an fp8 KV cache (qie_attention_extend_fp8): same grid, same splits,
+// same partials; attn_mfma_walk's KV8 form reads the codes.
+template <int HD, bool PG>
+__global__ __launch_bounds__(256, 2) void attn_extend_fp8_kernel(ExtendAttnParams8 a) {
+    const int kvh = blockIdx.z % a.nkv, seq = blockIdx.z / a.nkv;
+    const int64_t row0 = (int64_t)seq * a.rows_per_seq;
+    const int R = (int)min((int64_t)a.rows_per_seq, a.M - row0);
+    attn_extend_block<HD, PG, true>(a, seq, row0, R, blockIdx.x, blockIdx.y, kvh);
+}
+
+// The checks, parameters and grid both cache forms share (`c`: the bf16 descriptor, or the fp8
+// descriptor's layout part); nothing is launched.  `who` names the op in a refusal.
+static int extend_plan(const char* who, const void* q, int64_t M, const int32_t* pos, int32_t rows_per_seq,
+                       const qie_kv_cache* c, int32_t layer, int32_t n_heads, void* out, void* ws, ExtendAttnParams* a,
+                       dim3* grid) {
+    QIE_REQUIRE(c->head_dim == 64 || c->head_dim == 128, "%s: head_dim must be 64 or 128 (got %d)", who, c->head_dim);
+    QIE_REQUIRE(c->n_kv_heads > 0 && n_heads % c->n_kv_heads == 0 && n_heads / c->n_kv_heads <= kMaxGroup,
+                "%s: n_heads/n_kv_heads must be an integer <= %d", who, kMaxGroup);
+    QIE_REQUIRE(layer >= 0 && layer < c->n_layers, "%s: bad layer", who);
+    if (M == 0) return 0;
+    a->q = (const uint16_t*)q;
+    a->pos = pos;
+    a->rows_per_seq = rows_per_seq;
+    a->M = M;
+    a->kc = (const uint16_t*)c->k;
+    a->vc = (const uint16_t*)c->v;
+    QIE_TRY(kv_map_make(c, &a->km, who));
+    a->layer = layer;
+    a->nkv = c->n_kv_heads;
+    a->nq = n_heads;
+    extend_split(M, c->max_ctx, &a->split_len, &a->nsplit);
+    QIE_REQUIRE(a->nsplit == 1 || ws, "%s: workspace required", who);
+    const int64_t part = M * n_heads * (int64_t)a->nsplit;
+    a->part_o = (float*)ws;
+    a->part_ml = ws ? (float*)ws + part * c->head_dim : nullptr;
+    a->out = (uint16_t*)out;
+    const int64_t n_seqs = (M + rows_per_seq - 1) / rows_per_seq;
+    const int G = n_heads / c->n_kv_heads;
+    const int64_t nblk = ((int64_t)std::min<int64_t>(rows_per_seq, M) * G + kExtBlockRows - 1) / kExtBlockRows;
+    QIE_REQUIRE(n_seqs * a->nkv <= 65535 && nblk <= INT32_MAX && M <= INT32_MAX,
+                "%s: %lld sequences x %d kv heads exceed the launch grid", who, (long long)n_seqs, a->nkv);
+    *grid = dim3((unsigned)nblk, (unsigned)a->nsplit, (unsigned)(n_seqs * a->nkv));
+    return 0;
+}
+
+// the workgroups, then the merge of their partials where the cache has more than one split
+template <class K, class A>
+static int extend_launch(K k, const A& a, dim3 grid, int hd, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    const size_t shm = (size_t)2 * 2 * 64 * hd * 2;   // both forms: attn_mfma_walk's LDS
+    hipLaunchKernelGGL(k, grid, dim3(256), shm, st, a);
+    QIE_LAUNCH_CHECK();
+    if (a.nsplit > 1) {
+        launch_attn_combine<true>(hd, a.M, a.nq, a.nsplit, a.part_o, a.part_ml, a.out, st);
+        QIE_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
 }  // namespace qie
 
 using namespace qie;
@@ -80,48 +139,31 @@ int qie_attention_extend(const void* q, int64_t M, const int32_t* pos, int32_t r
                          void* stream) {
     QIE_REQUIRE(q && pos && cache && cache->k && cache->v && out && M >= 0 && rows_per_seq > 0 && n_heads > 0,
                 "qie_attention_extend: bad arguments");
-    QIE_REQUIRE(cache->head_dim == 64 || cache->head_dim == 128,
-                "qie_attention_extend: head_dim must be 64 or 128 (got %d)", cache->head_dim);
-    QIE_REQUIRE(cache->n_kv_heads > 0 && n_heads % cache->n_kv_heads == 0 &&
-                    n_heads / cache->n_kv_heads <= kMaxGroup,
-                "qie_attention_extend: n_heads/n_kv_heads must be an integer <= %d", kMaxGroup);
-    QIE_REQUIRE(layer >= 0 && layer < cache->n_layers, "qie_attention_extend: bad layer");
-    if (M == 0) return 0;
     ExtendAttnParams a;
-    a.q = (const uint16_t*)q;
-    a.pos = pos;
-    a.rows_per_seq = rows_per_seq;
-    a.M = M;
-    a.kc = (const uint16_t*)cache->k;
-    a.vc = (const uint16_t*)cache->v;
-    QIE_TRY(kv_map_make(cache, &a.km, "qie_attention_extend"));
-    a.layer = layer;
-    a.nkv = cache->n_kv_heads;
-    a.nq = n_heads;
-    extend_split(M, cache->max_ctx, &a.split_len, &a.nsplit);
-    QIE_REQUIRE(a.nsplit == 1 || ws, "qie_attention_extend: workspace required");
-    const int64_t part = M * n_heads * (int64_t)a.nsplit;
-    a.part_o = (float*)ws;
-    a.part_ml = ws ? (float*)ws + part * cache->head_dim : nullptr;
-    a.out = (uint16_t*)out;
-    const int64_t n_seqs = (M + rows_per_seq - 1) / rows_per_seq;
-    const int G = n_heads / cache->n_kv_heads;
-    const int64_t nblk = ((int64_t)std::min<int64_t>(rows_per_seq, M) * G + kExtBlockRows - 1) / kExtBlockRows;
-    QIE_REQUIRE(n_seqs * a.nkv <= 65535 && nblk <= INT32_MAX && M <= INT32_MAX,
-                "qie_attention_extend: %lld sequences x %d kv heads exceed the launch grid", (long long)n_seqs, a.nkv);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t shm = (size_t)2 * 2 * 64 * cache->head_dim * 2;
+    dim3 grid;
+    QIE_TRY(extend_plan("qie_attention_extend", q, M, pos, rows_per_seq, cache, layer, n_heads, out, ws, &a, &grid));
+    if (M == 0) return 0;
     const bool pg = a.km.table != nullptr;
-    dim3 grid((unsigned)nblk, (unsigned)a.nsplit, (unsigned)(n_seqs * a.nkv));
     auto k = cache->head_dim == 128 ? (pg ? attn_extend_kernel<128, true> : attn_extend_kernel<128, false>)
                                     : (pg ? attn_extend_kernel<64, true> : attn_extend_kernel<64, false>);
-    hipLaunchKernelGGL(k, grid, dim3(256), shm, st, a);
-    QIE_LAUNCH_CHECK();
-    if (a.nsplit > 1) {
-        launch_attn_combine<true>(cache->head_dim, M, n_heads, a.nsplit, a.part_o, a.part_ml, a.out, st);
-        QIE_LAUNCH_CHECK();
-    }
-    return 0;
+    return extend_launch(k, a, grid, cache->head_dim, stream);
+}
+
+int qie_attention_extend_fp8(const void* q, int64_t M, const int32_t* pos, int32_t rows_per_seq,
+                             const qie_kv_cache_fp8* cache, int32_t layer, int32_t n_heads, void* out, void* ws,
+                             void* stream) {
+    QIE_REQUIRE(q && pos && cache && cache->c.k && cache->c.v && out && M >= 0 && rows_per_seq > 0 && n_heads > 0,
+                "qie_attention_extend_fp8: bad arguments");
+    ExtendAttnParams8 a;
+    dim3 grid;
+    QIE_TRY(extend_plan("qie_attention_extend_fp8", q, M, pos, rows_per_seq, &cache->c, layer, n_heads, out, ws, &a,
+                        &grid));
+    if (M == 0) return 0;
+    QIE_TRY(kv8_exps_make(cache, a.km, &a.ex, "qie_attention_extend_fp8"));
+    const bool pg = a.km.table != nullptr;
+    auto k = cache->c.head_dim == 128 ? (pg ? attn_extend_fp8_kernel<128, true> : attn_extend_fp8_kernel<128, false>)
+                                      : (pg ? attn_extend_fp8_kernel<64, true> : attn_extend_fp8_kernel<64, false>);
+    return extend_launch(k, a, grid, cache->c.head_dim, stream);
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@ min .. max of `--repeats` samples of each kernel, and the K/V bytes a launch rea
 
     python tools/kv_fp8_bench.py --out profiles/kv_fp8.json
     QIE_LIB=.../lib/dev/libqie.so python tools/kv_fp8_bench.py --step-ab      # 128- against 256-key steps
+    python tools/kv_fp8_bench.py --extend --out profiles/kv_fp8_extend.json   # appends: the split-context attention
 """
 import argparse
 import ctypes as C
@@ -170,8 +171,105 @@ def bench_points(q, st, a, shape, variants):
     return results
 
 
+def extend_points(q, st, a):
+    """--extend: M new rows over a prefix, us per call, three variants alternating in one process:
+    qie_attention_extend on a bf16 cache; qie_kv_dequantize_fp8 of the prefix into a one-layer staging
+    cache followed by qie_attention_extend on it (what an fp8-KV append ran per layer before
+    qie_attention_extend_fp8); qie_attention_extend_fp8 on the codes."""
+    chk = _lib.check
+
+    def dmalloc(n, fill):
+        p = C.c_void_p()
+        chk(q.qie_malloc(C.byref(p), n), "qie_malloc")
+        chk(q.qie_memset(p.value, fill, n), "memset")
+        return p.value
+
+    results = []
+    for ctx in a.ctx:
+        for M in a.rows:
+            maxc = ctx + M + 128
+            per_seq = LAYERS * NKV * maxc * HD
+            c16, stg, c8 = _lib.KvCacheC(), _lib.KvCacheC(), _lib.KvCacheFp8C()
+            for c, n, layers in ((c16, per_seq * 2, LAYERS), (stg, per_seq // LAYERS * 2, 1), (c8.c, per_seq, LAYERS)):
+                c.k, c.v = dmalloc(n, 0x38), dmalloc(n, 0x38)
+                c.seq_stride, c.n_layers, c.n_kv_heads, c.head_dim, c.max_ctx = per_seq // LAYERS * layers, layers, NKV, HD, maxc
+            ne = LAYERS * NKV * maxc
+            c8.k_exps, c8.v_exps, c8.exp_stride = dmalloc(ne, 127), dmalloc(ne, 127), ne
+            qh = np.random.default_rng(ctx + M).standard_normal((M, NQ * HD)).astype(np.float32) * 0.05
+            qh = ((qh.view(np.uint32) + 0x8000) >> 16).astype(np.uint16)
+            pos = np.arange(ctx, ctx + M, dtype=np.int32)
+            dq, dpos = dmalloc(qh.nbytes, 0), dmalloc(pos.nbytes, 0)
+            chk(q.qie_memcpy_h2d(dq, qh.ctypes.data, qh.nbytes), "h2d")
+            chk(q.qie_memcpy_h2d(dpos, pos.ctypes.data, pos.nbytes), "h2d")
+            ws = dmalloc(max(16, q.qie_attention_extend_workspace_bytes(M, NQ, HD, maxc)), 0)
+            out = dmalloc(M * NQ * HD * 2, 0)
+            bufs = [c16.k, c16.v, stg.k, stg.v, c8.c.k, c8.c.v, c8.k_exps, c8.v_exps, dq, dpos, ws, out]
+
+            def run(name, n):
+                t0 = time.perf_counter()
+                for i in range(n):
+                    l = i % LAYERS
+                    if name == "bf16":
+                        chk(q.qie_attention_extend(dq, M, dpos, M, C.byref(c16), l, NQ, out, ws, st), name)
+                    elif name == "expand_then_bf16":
+                        chk(q.qie_kv_dequantize_fp8(C.byref(c8), 0, l, 0, ctx, C.byref(stg), 0, 0, st), name)
+                        chk(q.qie_attention_extend(dq, M, dpos, M, C.byref(stg), 0, NQ, out, ws, st), name)
+                    else:
+                        chk(q.qie_attention_extend_fp8(dq, M, dpos, M, C.byref(c8), l, NQ, out, ws, st), name)
+                chk(q.qie_stream_synchronize(st), "sync")
+                return (time.perf_counter() - t0) / n * 1e6
+
+            names = ("bf16", "expand_then_bf16", "fp8")
+            est = max((run(nm, LAYERS), run(nm, LAYERS))[1] for nm in names)   # warm-up
+            calls = max(LAYERS, int(a.sample_ms * 1e3 / est) // LAYERS * LAYERS)
+            samples = {nm: [] for nm in names}
+            for _ in range(a.repeats):
+                for nm in names:                          # alternating, same process
+                    samples[nm].append(run(nm, calls))
+            row = {"prefix": ctx, "rows": M, "calls_per_sample": calls}
+            for nm in names:
+                s = sorted(samples[nm])
+                row[nm + "_us"] = {"median": round(s[len(s) // 2], 2), "min": round(s[0], 2), "max": round(s[-1], 2)}
+            row["fp8_over_expand_then_bf16"] = round(row["fp8_us"]["median"] / row["expand_then_bf16_us"]["median"], 3)
+            row["fp8_over_bf16"] = round(row["fp8_us"]["median"] / row["bf16_us"]["median"], 3)
+            print(json.dumps(row), flush=True)
+            results.append(row)
+            for p in bufs:
+                chk(q.qie_free(p), "free")
+    return results
+
+
+def extend_engine(a):
+    """--extend --engines: Batch.prefill(chunk=512) of 8k and 32k tokens on a kv_fp8 engine, tok/s.
+    Run once per library (QIE_LIB selects another build) to compare two commits."""
+    import qwen_inference_engine_amd as Q
+    from qwen_inference_engine_amd import spec as S, weights as W
+    eng = Q.Engine(S.QWEN2_7B, max_ctx=32768 + 64, kv_fp8=True).init_synthetic(W.SynthParams(seed=0))
+    rows = []
+    for n in (8192, 32768):
+        ids = [int(t) for t in np.random.default_rng(1).integers(0, 1000, n)]
+        b = eng.batch(1, 32768 + 64)
+        tok = []
+        for i in range(a.repeats + 1):                    # sample 0: warm-up, dropped
+            eng.sync()
+            t0 = time.perf_counter()
+            b.prefill(0, ids, chunk=512)
+            eng.sync()
+            tok.append(n / (time.perf_counter() - t0))
+        tok = sorted(tok[1:])
+        rows.append({"tokens": n, "chunk": 512, "tok_s": {"median": round(tok[len(tok) // 2]), "min": round(tok[0]),
+                                                          "max": round(tok[-1])}})
+        print(json.dumps(rows[-1]), flush=True)
+        b.close()
+    eng.close()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--extend", action="store_true", help="the split-context attention over a prefix: bf16 cache, "
+                    "expand + bf16 on staging, and qie_attention_extend_fp8 (profiles/kv_fp8_extend.json)")
+    ap.add_argument("--rows", type=int, nargs="+", default=[16, 512], help="--extend: new rows per call")
     ap.add_argument("--ctx", type=int, nargs="+", default=[2048, 8192, 32768])
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 8])
     ap.add_argument("--launches", type=int, default=280, help="launches per sample at the least")
@@ -191,7 +289,14 @@ def main():
     if os.path.exists(a.out):                           # the sections this run does not measure are kept
         with open(a.out) as f:
             doc = json.load(f)
-    if a.step_ab:
+    if a.extend:
+        doc["what"] = ("M new rows over a prefix, us per call, Qwen2-7B heads (28 / 4 x 128), 28 layers visited in turn: "
+                       "qie_attention_extend on a bf16 cache; qie_kv_dequantize_fp8 of the prefix + qie_attention_extend "
+                       "on staging; qie_attention_extend_fp8")
+        doc["points"] = extend_points(q, st, a)
+        if a.engines:
+            doc["engine_chunked_prefill"] = extend_engine(a)
+    elif a.step_ab:
         assert os.environ.get("QIE_LIB"), "--step-ab needs the development build (make DEV=1; QIE_LIB)"
         ab = [("fp8_ks128", 1, 128), ("fp8_ks256", 1, 256)]
         doc["step_ab"] = {
