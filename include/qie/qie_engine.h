@@ -326,6 +326,33 @@ int qie_verify_logits(qie_batch* b, void* host_out);
 typedef struct qie_verify_seg { int32_t seq, n_draft; } qie_verify_seg;
 int qie_verify_batch(qie_batch* b, const qie_verify_seg* segs, int32_t n_segs, const int32_t* draft,
                      const qie_sampling* s, int32_t* out_ids, int32_t* n_out);
+/* qie_verify for a TREE of drafts: siblings are alternative guesses for the same
+ * position, and the longest root path the model agrees with is accepted.  Slot `seq` is at
+ * position p with pending token c, as for qie_verify.  Node 0 is c; node i (1 <= i <= n <= 15)
+ * holds draft[i - 1] (host) and has parent[i - 1] in [0, i), so indices rise along every path;
+ * depth(0) = 0, depth(i) = depth(parent) + 1.  One pass runs the M = n + 1 rows through the
+ * decode-form layer: row i is rotated at position p + depth(i), its K/V are written at cache row
+ * p + i, and it attends to rows [0, p) and to rows p + j of its ancestors-or-self j.  Row i picks
+ * t_i as in qie_verify (greedy: the fused arg-max keys; sampled: counter = the slot's step counter
+ * + depth(i); a slot sampling entry is honoured, the window being the slot's history followed by
+ * the ids on i's root path).  Acceptance: cur = 0, emit t_cur; while a child j of cur drafts
+ * t_cur, cur = the lowest such j, emit t_cur.  out_ids (host, n + 1 slots) receives the emitted
+ * tokens and *n_out = a + 1 >= 1, a the depth reached.  The slot is left exactly as after a + 1
+ * decode steps (qie_verify's words), qie_batch_logits row `seq` holds the logits of the last
+ * accepted node, and cache rows [p, p + a] hold the accepted path's K/V in depth order
+ * (qie_kv_compact moves them, bit for bit); rows past the new position fall under the
+ * qie_batch_set_position rule.  qie_verify_logits / qie_verify_logprobs return the M rows in node
+ * order.  A chain (parent[i - 1] = i - 1) equals qie_verify of the same drafts bit for bit, in
+ * every output and in the state.  The call synchronises once.  With use_graph the step is captured
+ * once per (slot, rows, sampling kind, entries) in qie_verify's bounded cache; the tree's shape is
+ * device data, not part of the key.  Tensor parallelism is out of scope: refused.
+ * All-or-nothing, nothing launched: -22 for bad arguments, a malformed tree (n outside [0, 15], a
+ * parent outside [0, i)), an idle slot, a draft id out of range, p + n + 1 >= max_ctx, a
+ * prefill_fp8 engine, a batch in decode mode 1, an fp8-KV batch, an engine with tp_comm or
+ * comm_always; -28 when the page pool cannot hold rows up to p + n (qie_verify's reservation). */
+typedef struct qie_draft_tree { int32_t n; int32_t parent[15]; } qie_draft_tree;
+int qie_verify_tree(qie_batch* b, int32_t seq, const int32_t* draft, const qie_draft_tree* tree,
+                    const qie_sampling* s, int32_t* out_ids, int32_t* n_out);
 /* qie_batch_logprobs over the rows qie_verify_logits would return: out[m] (host float [rows]) =
  * the log-probability of ids[m] (host [rows]; -1 = skip: 0.0f) under row m of the last qie_verify
  * or qie_verify_batch (qie_logprob_rows on the step's logits; gathered under tensor parallelism:

@@ -165,6 +165,17 @@ int qie_qkv_post_ragged(const void* qkv, int64_t M, const int32_t* pos, const qi
                         const float* rope_sin, int32_t n_heads, const qie_kv_cache* cache,
                         int32_t layer, float eps, int32_t numerics, void* q_out, void* stream);
 
+/* qie_qkv_post for the M <= 16 rows of a draft tree, all of sequence `seq`: row m
+ * is rotated at position rope_pos[m] and its K/V rows are written at cache row cache_row[m] (both
+ * device arrays; siblings of a tree share a position and never a row).  The per-row arithmetic is
+ * qie_qkv_post's: with cache_row == rope_pos the q, K and V bits are that operator's.  head_dim 64
+ * or 128, contiguous and paged caches (the pages of the rows held by the caller); never allocates
+ * or synchronises; capturable. */
+int qie_qkv_post_tree(const void* qkv, int32_t M, const int32_t* rope_pos, const int32_t* cache_row,
+                      int32_t seq, const void* q_norm, const void* k_norm, const float* rope_cos,
+                      const float* rope_sin, int32_t n_heads, const qie_kv_cache* cache,
+                      int32_t layer, float eps, int32_t numerics, void* q_out, void* stream);
+
 /* -------------------------------------------------------------- attention
  * Replaces launch_attn / selfattention (helpers.cuh:121-130,
  * self_attension.cu:10-149): GQA attention of query rows over the cache.
@@ -209,6 +220,21 @@ int qie_attention_extend(const void* q, int64_t M, const int32_t* pos, int32_t r
 int qie_attention_ragged(const void* q, const int32_t* pos, const qie_row_segs* segs,
                          const qie_kv_cache* cache, int32_t layer, int32_t n_heads, void* out,
                          void* ws, void* stream);
+
+/* qie_attention_extend for ONE run of M <= 16 rows that are the nodes of a draft tree (SpecInfer /
+ * Medusa style verification) of sequence `seq`.  Node i's K/V sit at cache row
+ * row[i] = p + i (device [M]; p = row[0]) and anc[i] (device [M]) has bit j set iff node j is i
+ * itself or an ancestor of i.  Key row k is visible to row i iff k < p, or k - p < M and bit k - p
+ * of anc[i] is set; a hidden row contributes exactly nothing whatever it holds (its V is read with
+ * non-finite elements as zeros in the tiles that hold rows of the run).  The same workgroups, split
+ * length (qie_attention_extend_split_tokens(M, max_ctx)), workspace and merge as
+ * qie_attention_extend at M rows; every row walks the key tiles up to p + M - 1 and only the tiles
+ * from the one holding row p on pay for the mask.  A chain (anc[i] = bits 0 .. i) equals
+ * qie_attention_extend at pos = row, rows_per_seq = M, bit for bit.  -22 for bad arguments;
+ * nothing is launched.  Never allocates or synchronises; capturable. */
+int qie_attention_extend_tree(const void* q, int32_t M, const int32_t* row, const int32_t* anc,
+                              int32_t seq, const qie_kv_cache* cache, int32_t layer,
+                              int32_t n_heads, void* out, void* ws, void* stream);
 
 /* Decode attention with the q/k post-projection fused in (one launch per layer):
  * qkv rows [B][(nq + 2 nkv) hd] straight from the QKV projection; applies qk-norm
@@ -263,6 +289,17 @@ int qie_kv_write(const void* k, const void* v, int64_t rows, int64_t ld, int32_t
  * and positions past either max_ctx return -22.  Never allocates or synchronises; capturable. */
 int qie_kv_copy(const qie_kv_cache* src, int32_t src_seq, const qie_kv_cache* dst, int32_t dst_seq,
                 int32_t pos0, int32_t n_rows, void* stream);
+
+/* After a tree verify step: for d = 1 .. a the K and V rows of cache row
+ * p + path[d] of sequence `seq` move to row p + d where the two differ, every layer and kv head,
+ * in one launch (one workgroup per (layer, kv head); every source row is loaded before the first
+ * store, and node indices rise along a path, so no destination is a later source).  p = p_dev[0],
+ * a = a_dev[0] (0 .. 15) and path_dev[0 .. a] (node indices < 16) are read from device memory; rows
+ * at or past max_ctx are not touched.  16-byte loads and stores only; head_dim 64 or 128,
+ * contiguous and paged caches (rows may cross a page boundary).  Never allocates or synchronises;
+ * capturable. */
+int qie_kv_compact(const qie_kv_cache* cache, int32_t seq, const int32_t* p_dev, const int32_t* a_dev,
+                   const int32_t* path_dev, void* stream);
 
 /* ------------------------------------------------------------- elementwise
  * launch_act + launch_elem (helpers.cuh:108-115) and launch_resadd (:116-119)

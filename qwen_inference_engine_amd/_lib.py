@@ -119,6 +119,11 @@ class VerifySegC(C.Structure):
     _fields_ = [("seq", C.c_int32), ("n_draft", C.c_int32)]
 
 
+class DraftTreeC(C.Structure):
+    """qie_draft_tree: n drafted nodes, parent[i - 1] in [0, i) the parent of node i."""
+    _fields_ = [("n", C.c_int32), ("parent", C.c_int32 * 15)]
+
+
 class EngineOptsC(C.Structure):
     _fields_ = [("device", C.c_int32), ("max_ctx", C.c_int32), ("use_graph", C.c_int32),
                 ("tp_rank", C.c_int32), ("tp_size", C.c_int32), ("tp_comm", C.c_void_p),
@@ -164,6 +169,10 @@ SIGNATURES = [
     ("qie_attention_extend_split_tokens", C.c_int32, [_I64, _I32]),
     ("qie_attention_extend", C.c_int, [_P, _I64, _P, _I32, C.POINTER(KvCacheC), _I32, _I32, _P, _P, _P]),
     ("qie_attention_ragged", C.c_int, [_P, _P, C.POINTER(RowSegsC), C.POINTER(KvCacheC), _I32, _I32, _P, _P, _P]),
+    ("qie_qkv_post_tree", C.c_int, [_P, _I32, _P, _P, _I32, _P, _P, _P, _P, _I32, C.POINTER(KvCacheC), _I32, _F, _I32,
+                                    _P, _P]),
+    ("qie_attention_extend_tree", C.c_int, [_P, _I32, _P, _P, _I32, C.POINTER(KvCacheC), _I32, _I32, _P, _P, _P]),
+    ("qie_kv_compact", C.c_int, [C.POINTER(KvCacheC), _I32, _P, _P, _P, _P]),
     ("qie_attention_decode_workspace_bytes", C.c_int64, [_I64, _I32, _I32, _I32, _I32]),
     ("qie_attention_decode", C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _I32, C.POINTER(KvCacheC), _I32, _F, _I32,
                                        _P, _P, _P]),
@@ -260,6 +269,7 @@ SIGNATURES = [
     ("qie_verify", C.c_int, [_P, _I32, _PI32, _I32, C.POINTER(SamplingC), _PI32, _PI32]),
     ("qie_verify_logits", C.c_int, [_P, _P]),
     ("qie_verify_batch", C.c_int, [_P, C.POINTER(VerifySegC), _I32, _PI32, C.POINTER(SamplingC), _PI32, _PI32]),
+    ("qie_verify_tree", C.c_int, [_P, _I32, _PI32, C.POINTER(DraftTreeC), C.POINTER(SamplingC), _PI32, _PI32]),
     ("qie_verify_logprobs", C.c_int, [_P, _PI32, _PF]),
     ("qie_batch_debug_verify_captures", C.c_int, [_P]),
     ("qie_decode_step", C.c_int, [_P, C.POINTER(SamplingC), _PI32]),

@@ -30,6 +30,24 @@ struct ExtendAttnParams {
 struct ExtendAttnParams8 : ExtendAttnParams {
     Kv8Exps ex;
 };
+// ... for the rows of a draft tree (attn_extend_tree_kernel, k_verify_tree.hip): ONE run of M <= 16
+// rows whose K/V sit at cache rows p + i (pos[i] = p + i), row i seeing the prefix [0, p) and the
+// rows p + j of its ancestors-or-self j (bit j of anc[i])
+struct ExtendTreeParams : ExtendAttnParams {
+    const int32_t* anc;   // [M]
+};
+
+// attn_mfma_walk's visibility policy of those rows.  Every tile from the one that holds row p on
+// is masked, for every group (the walk's gmin = p - 1), and its V fragments are scrubbed.
+struct VisTree {
+    static constexpr bool kScrubV = true;
+    int p;             // the run's first cache row
+    uint32_t anc[2];   // the lane's row's mask, per query group
+    __device__ __forceinline__ bool sees(int q, int key, int) const {
+        return key < p || ((unsigned)(key - p) < 16u && ((anc[q] >> (key - p)) & 1u));
+    }
+    __device__ __forceinline__ bool scrubs(int last_key) const { return last_key >= p; }
+};
 
 // The workgroup of (rows [row0, row0 + R) of the call, which belong to cache sequence seq;
 // block blk of their flattened rows; split s; kv head kvh).  256 threads.  Wave w owns the
@@ -38,7 +56,12 @@ struct ExtendAttnParams8 : ExtendAttnParams {
 // the prefix is the same for every group.
 // KV8 (P = ExtendAttnParams8): the walk reads an fp8 cache (attn_mfma_walk's KV8 form); rows,
 // splits, partials and stores are the same code.
-template <int HD, bool PG, bool KV8 = false, class P>
+// TREE (P = ExtendTreeParams): the run is a draft tree.  Every row walks the tiles up to the run's
+// last row p + R - 1 (a sibling's row may lie before an ancestor's), under VisTree; rows, splits,
+// partials and stores are the same code, and a chain (anc[i] = bits 0 .. i) gives every row the
+// scores, maxima and sums of the causal form: a tile that shows a row no key leaves its running
+// statistics and its O as they were.
+template <int HD, bool PG, bool KV8 = false, bool TREE = false, class P>
 __device__ __forceinline__ void attn_extend_block(const P& a, const int seq, const int64_t row0, const int R,
                                                   const int blk, const int s, const int kvh) {
     constexpr int NW = 4;
@@ -60,7 +83,7 @@ __device__ __forceinline__ void attn_extend_block(const P& a, const int seq, con
     auto part_idx = [&](int f) { return ((row0 + f / G) * a.nq + kvh * G + f % G) * ns + s; };
 
     // the block's last position bounds the keys any of its rows can see
-    const int kmax = __builtin_amdgcn_readfirstlane(a.pos[row0 + (min(f0 + kExtBlockRows, RG) - 1) / G]);
+    const int kmax = __builtin_amdgcn_readfirstlane(a.pos[row0 + (TREE ? R - 1 : (min(f0 + kExtBlockRows, RG) - 1) / G)]);
     const int k0 = s * a.split_len;
     if (k0 > kmax) {
         // no row of the block sees this split: (-inf, 0) in every slot the combine reads (it
@@ -85,6 +108,8 @@ __device__ __forceinline__ void attn_extend_block(const P& a, const int seq, con
     bool gact[QG];
     int qpos[QG], gpos[QG], gmin[QG];
     bf16x8_t qf[QG][KSTEPS];
+    std::conditional_t<TREE, VisTree, VisCausal> vis{};
+    if constexpr (TREE) vis.p = __builtin_amdgcn_readfirstlane(a.pos[row0]);
 #pragma unroll
     for (int q = 0; q < QG; q++) {
         gact[q] = f0 + 16 * grp[q] < RG;
@@ -95,6 +120,11 @@ __device__ __forceinline__ void attn_extend_block(const P& a, const int seq, con
         gpos[q] = __builtin_amdgcn_readfirstlane(gact[q] ? a.pos[row0 + min(fb + 15, RG - 1) / G] : -1);   // -1: no tile
         // the group's first position: a key tile ending at or before it needs no causal mask
         gmin[q] = __builtin_amdgcn_readfirstlane(a.pos[row0 + fb / G]);
+        if constexpr (TREE) {
+            gpos[q] = gact[q] ? kmax : -1;
+            gmin[q] = __builtin_amdgcn_readfirstlane(a.pos[row0]) - 1;
+            vis.anc[q] = (uint32_t)a.anc[row0 + t];
+        }
         const uint16_t* qp = a.q + (row0 + t) * (int64_t)a.nq * HD + (int64_t)(kvh * G + hq) * HD;
 #pragma unroll
         for (int ks = 0; ks < KSTEPS; ks++) qf[q][ks] = *reinterpret_cast<const bf16x8_t*>(qp + ks * 32 + g * 8);
@@ -105,6 +135,9 @@ __device__ __forceinline__ void attn_extend_block(const P& a, const int seq, con
     if constexpr (KV8)
         attn_mfma_walk<HD, PG, NW, true, true>(kb, vb, a.km, seq, kmax, k0, nkt, qf, qpos, gpos, gmin, oacc, m_run, l_run,
                                                &a.ex, kv_run_off(a.ex.em, (int64_t)a.layer * a.nkv + kvh, 1));
+    else if constexpr (TREE)
+        attn_mfma_walk<HD, PG, NW, true, false, VisTree>(kb, vb, a.km, seq, kmax, k0, nkt, qf, qpos, gpos, gmin, oacc, m_run,
+                                                         l_run, nullptr, 0, vis);
     else
         attn_mfma_walk<HD, PG, NW, true>(kb, vb, a.km, seq, kmax, k0, nkt, qf, qpos, gpos, gmin, oacc, m_run, l_run);
 

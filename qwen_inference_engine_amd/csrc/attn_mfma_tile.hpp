@@ -49,13 +49,30 @@ namespace qie {
 // read as zeros (the bounded resource) and their exponent bytes are never read (scale 1), so they
 // are exact zeros whatever the cache holds.  Dynamic LDS: 2 bf16 images + 2 operands x 2 code buffers, the
 // bf16 walk's byte count.
-template <int HD, bool PG, int NW, bool SPLIT, bool KV8 = false>
+// VIS: which keys a row sees in a tile that is not wholly at or before its group's first position
+// (gmin).  VisCausal, every caller's but one: the keys up to the row's position.  A policy with
+// kScrubV (VisTree, attn_extend_block.hpp: the rows of a draft tree see their ancestors only) has
+// the V fragments of the tiles it masks read with non-finite elements as zeros: there a hidden row
+// is another row's live K/V, not a row past kmax that the bounded resource already reads as zeros,
+// and P = 0 must stay 0 whatever that row holds.
+struct VisCausal {
+    static constexpr bool kScrubV = false;
+    __device__ __forceinline__ bool sees(int, int key, int qpos) const { return key <= qpos; }
+    __device__ __forceinline__ bool scrubs(int) const { return false; }
+};
+// bf16 pairs with Inf / NaN halves (all exponent bits set) replaced by +0
+__device__ __forceinline__ uint32_t finite_bf16x2(uint32_t w) {
+    if ((w & 0x7f80u) == 0x7f80u) w &= 0xffff0000u;
+    if ((w & 0x7f800000u) == 0x7f800000u) w &= 0x0000ffffu;
+    return w;
+}
+template <int HD, bool PG, int NW, bool SPLIT, bool KV8 = false, class VIS = VisCausal>
 __device__ __forceinline__ void attn_mfma_walk(const uint16_t* kb, const uint16_t* vb, const KvMap& km, const int seq,
                                                const int kmax, const int k0, const int nkt,
                                                const bf16x8_t (&qf)[2][HD / 32], const int (&qpos)[2],
                                                const int (&gpos)[2], const int (&gmin)[2], f32x4_t (&oacc)[2][HD / 16],
                                                float (&m_run)[2], float (&l_run)[2], const Kv8Exps* ex = nullptr,
-                                               const int64_t ehead = 0) {
+                                               const int64_t ehead = 0, const VIS& vis = VIS{}) {
     constexpr int KT = 64;
     constexpr int CPR = HD / 8;
     constexpr int KSTEPS = HD / 32;
@@ -199,7 +216,7 @@ __device__ __forceinline__ void attn_mfma_walk(const uint16_t* kb, const uint16_
 #pragma unroll
                         for (int r = 0; r < 4; r++) {
                             const int key = kt * KT + t * 16 + g * 4 + r;
-                            const float sc = key <= qpos[q] ? sacc[q][t][r] * sl2 : -INFINITY;
+                            const float sc = vis.sees(q, key, qpos[q]) ? sacc[q][t][r] * sl2 : -INFINITY;
                             sv[t][r] = sc;
                             mt = fmaxf(mt, sc);
                         }
@@ -268,8 +285,16 @@ __device__ __forceinline__ void attn_mfma_walk(const uint16_t* kb, const uint16_
                         __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) i16x4_t*)(a0));
                     const i16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
                         (__attribute__((address_space(3))) i16x4_t*)(a0 + 16 * HD));
-                    const bf16x8_t vb8 =
+                    bf16x8_t vb8 =
                         __builtin_bit_cast(bf16x8_t, __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7));
+                    if constexpr (VIS::kScrubV) {
+                        if (vis.scrubs(kt * KT + KT - 1)) {   // wave-uniform: the tile holds rows of the run
+                            u32x4_t w = __builtin_bit_cast(u32x4_t, vb8);
+#pragma unroll
+                            for (int j = 0; j < 4; j++) w[j] = finite_bf16x2(w[j]);
+                            vb8 = __builtin_bit_cast(bf16x8_t, w);
+                        }
+                    }
 #pragma unroll
                     for (int q = 0; q < QG; q++) {
                         if (!ON[q]) continue;

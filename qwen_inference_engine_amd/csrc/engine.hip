@@ -242,6 +242,8 @@ struct qie_batch {
     // vb_aux (made once by the first call): the result words [kVerifyBatchResWords], then the
     // rows' slots, tail offsets and tail lengths [kVerifyMaxRows] each
     int32_t* vb_aux = nullptr;
+    // the tree step's words (qie_verify_tree, verify.hpp kVt*): made once by the first call
+    int32_t* vt = nullptr;
     // scoring (qie_score, qie_batch_logprobs): device targets, log-probabilities and
     // greedy ids of sc.rows rows, and the fused head's workspace; grown before any launch
     ScoreRows sc;
@@ -990,8 +992,11 @@ static int enqueue_layer_decode(qie_batch* b, int l) {
 // (qie_prefill_ragged): the rows are segments of any lengths, each of its own sequence, and both
 // steps take their ragged forms (`attend` is not consulted).
 using AttentionFn = decltype(&qie_attention);
+// `tree` set (qie_verify_tree: the step's words, verify.hpp): the rows are the nodes of a draft tree
+// of cache sequence 0, r.pos their RoPE positions; K/V go to the rows kVtRow names and the attention
+// masks by kVtAnc (`attend` is not consulted).
 static int enqueue_layer_rows(qie_batch* b, int l, const LayerRows& r, const LayerPath& p, const qie_kv_cache& cache,
-                              AttentionFn attend, void* attn_ws) {
+                              AttentionFn attend, void* attn_ws, const int32_t* tree = nullptr) {
     qie_engine* e = b->e;
     const qie_model_spec& s = e->spec;
     const qie_layer_weights& L = p.layers[l];
@@ -1020,6 +1025,11 @@ static int enqueue_layer_rows(qie_batch* b, int l, const LayerRows& r, const Lay
         QIE_TRY(qie_qkv_post_ragged(r.qkv, r.M, r.pos, r.segs, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, e->sh.nq,
                                     &cache, l, s.rms_eps, s.numerics, r.q, st));
         QIE_TRY(qie_attention_ragged(r.q, r.pos, r.segs, &cache, l, e->sh.nq, r.att, attn_ws, st));
+    } else if (tree) {
+        QIE_TRY(qie_qkv_post_tree(r.qkv, (int32_t)r.M, r.pos, tree + kVtRow, 0, L.q_norm, L.k_norm, e->rope_cos,
+                                  e->rope_sin, e->sh.nq, &cache, l, s.rms_eps, s.numerics, r.q, st));
+        QIE_TRY(qie_attention_extend_tree(r.q, (int32_t)r.M, tree + kVtRow, tree + kVtAnc, 0, &cache, l, e->sh.nq, r.att,
+                                          attn_ws, st));
     } else {
         QIE_TRY(qie_qkv_post(r.qkv, r.M, r.pos, r.rows_per_seq, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, e->sh.nq,
                              &cache, l, s.rms_eps, s.numerics, r.q, st));
@@ -2119,7 +2129,7 @@ void qie_batch_destroy(qie_batch* b) {
     free_rows(b->v);
     free_rows(b->sc);
     for (void* p : {(void*)b->kc, (void*)b->vc, (void*)b->ke, (void*)b->ve, (void*)b->sk, (void*)b->sv, (void*)b->d_table, b->pk_mem, (void*)b->d_layers, b->d_attp,
-                    (void*)b->pk_ts, (void*)b->d_slots, b->rows_ws, (void*)b->vb_aux})
+                    (void*)b->pk_ts, (void*)b->d_slots, b->rows_ws, (void*)b->vb_aux, (void*)b->vt})
         if (p) hipFree(p);
     for (void* p : b->retired) hipFree(p);
     // (the DevBlock workspaces free themselves)
@@ -2706,6 +2716,131 @@ int qie_verify_logits(qie_batch* b, void* host_out) {
     QIE_HIP(hipStreamSynchronize(e->stream));
     QIE_TRY(comm_check(e, "qie_verify_logits"));
     QIE_HIP(d2h(e, host_out, src, (size_t)b->v_rows * e->spec.vocab * 2));
+    return 0;
+}
+
+// ------------------------------------------------------------ the tree verify step
+// the step's words (verify.hpp kVt*) beside the rows `v`: made once, never reallocated
+static int ensure_verify_tree_bufs(qie_batch* b) {
+    QIE_TRY(ensure_verify_bufs(b));
+    if (b->vt) return 0;
+    const size_t bytes = (size_t)kVtWords * 4;
+    void* p = nullptr;
+    QIE_TRY(dmalloc(&p, bytes));
+    hipError_t he = hipMemsetAsync(p, 0, bytes, b->e->stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(b->e->stream);
+    if (he != hipSuccess) {
+        hipFree(p);
+        return fail((int)he, "qie_verify_tree: buffer init: %s", hipGetErrorString(he));
+    }
+    b->vt = (int32_t*)p;
+    return 0;
+}
+
+// enqueue_verify with the rows a tree: rows -> the decode-form layers with the tree's q/k post-pass
+// and masked attention -> head -> commit -> compaction of the accepted path's K/V rows.  The
+// tree's shape is read from the step's words by every kernel: a linear chain on device state,
+// capturable once for every tree of M rows.
+static int enqueue_verify_tree(qie_batch* b, int seq, int M, const qie_sampling* smp) {
+    qie_engine* e = b->e;
+    const qie_model_spec& s = e->spec;
+    hipStream_t st = e->stream;
+    const int64_t H8 = (int64_t)s.hidden / 8;
+    int32_t* vt = b->vt;
+    VerifyTreeRowsArgs ra{seq, M, vt, s.vocab, (const uint4*)e->w.embed, (const uint4*)b->dec.x, H8,
+                          b->dec.pos, b->dec.step, (uint4*)b->v.x, b->v.pos, b->v.step};
+    QIE_TRY(launch_verify_tree_rows(ra, st));
+    const qie_kv_cache cache = batch_cache(b, seq);
+    const LayerRows r = layer_rows(b->v, M, M);
+    for (int l = 0; l < s.n_layers; l++)
+        QIE_TRY(enqueue_layer_rows(b, l, r, decode_path(e), cache, nullptr, b->v.attn_ws, vt));
+    // with an entry: row i's window ends at p + depth(i), history [.. p] and then the ids of its root path
+    EntryRows er{0, 0, b->v.pos, vt + kVtIds, vt + kVtDepth};
+    er.row_slot = vt + kVtSlot, er.tail_off = vt + kVtTailOff;
+    const bool entries = any_entry(b, seq, 1);
+    QIE_TRY(enqueue_head_rows(b, b->v.x, s.hidden, M, smp, head_bufs(b->v, 0, e->sh.vocab), entries ? &er : nullptr));
+    const bool greedy = !entries && is_greedy(smp);
+    VerifyTreeCommitArgs ca{seq, M, greedy ? b->v.keys : nullptr, b->v.ids, vt, s.vocab, b->dec.pos, b->dec.step,
+                            b->dec.hist, b->max_ctx, b->dec.ids, (const uint4*)e->w.embed, (uint4*)b->dec.x, H8,
+                            rope_cur_args(b), b->v.logits, b->dec.logits, (int64_t)e->sh.vocab};
+    QIE_TRY(launch_verify_tree_commit(ca, st));
+    return qie_kv_compact(&cache, 0, vt + kVtRow, vt + kVtAcc, vt + kVtPath, st);
+}
+
+// eager, or the captured step of (seq, M, sampling kind, entries) in v_graphs (launch_verify's cache
+// and bound; seq is stored as -2 - seq, apart from the chain's >= 0 and the batched step's -1)
+static int launch_verify_tree(qie_batch* b, int seq, int M, const qie_sampling* smp) {
+    qie_engine* e = b->e;
+    if (!e->opts.use_graph) return enqueue_verify_tree(b, seq, M, smp);
+    const bool greedy = is_greedy(smp), entries = any_entry(b, seq, 1);
+    for (const auto& g : b->v_graphs)
+        if (g.seq == -2 - seq && g.M == M && g.entries == entries &&
+            (entries || (g.greedy == greedy && (greedy || same_sampling(g.smp, smp))))) {
+            QIE_HIP(hipGraphLaunch(g.exec, e->stream));
+            return 0;
+        }
+    if (b->v_graphs.size() >= 64) {   // bounded: drop the oldest captured step
+        hipGraphExecDestroy(b->v_graphs.front().exec);
+        b->v_graphs.erase(b->v_graphs.begin());
+    }
+    hipGraphExec_t exec = nullptr;
+    QIE_TRY(capture_graph(e, "qie_verify_tree: ", [&] { return enqueue_verify_tree(b, seq, M, smp); }, &exec));
+    b->v_captures++;
+    b->v_graphs.push_back({-2 - seq, M, entries, greedy, smp ? *smp : qie_sampling{1, 0.f, 1.f, 0}, exec});
+    QIE_HIP(hipGraphLaunch(exec, e->stream));
+    return 0;
+}
+
+int qie_verify_tree(qie_batch* b, int32_t seq, const int32_t* draft, const qie_draft_tree* tree, const qie_sampling* smp,
+                    int32_t* out_ids, int32_t* n_out) {
+    const char* who = "qie_verify_tree";
+    // the tree first: its refusals need no batch
+    QIE_REQUIRE(tree && tree->n >= 0 && tree->n < QIE_VERIFY_MAX_ROWS, "%s: malformed tree (0 .. %d drafted nodes)", who,
+                QIE_VERIFY_MAX_ROWS - 1);
+    const int n = tree->n, M = n + 1;
+    for (int i = 1; i <= n; i++)
+        QIE_REQUIRE(tree->parent[i - 1] >= 0 && tree->parent[i - 1] < i,
+                    "%s: malformed tree (node %d has parent %d, not in [0, %d))", who, i, tree->parent[i - 1], i);
+    QIE_REQUIRE(b && out_ids && n_out && seq >= 0 && seq < b->B && (n == 0 || draft), "%s: bad arguments", who);
+    QIE_NO_KV8(b, who);
+    qie_engine* e = b->e;
+    const qie_model_spec& s = e->spec;
+    QIE_REQUIRE(!b->idle[seq], "%s: slot %d holds no live sequence", who, seq);
+    QIE_REQUIRE(!(e->fp8 && e->opts.prefill_fp8),
+                "%s: not available on a prefill_fp8 engine (block-scaled fp8 activations are defined for a "
+                "prefill from position 0 only)", who);
+    QIE_REQUIRE(b->decode_mode == 0, "%s: the batch is in decode mode 1 (the persistent step); verify runs "
+                                     "the five-launch layer, set mode 0 first", who);
+    QIE_REQUIRE(!e->comm && !e->opts.tp_comm && !e->opts.comm_always,
+                "%s: not available on an engine with tp_comm / comm_always (tensor parallelism is out of scope)", who);
+    for (int i = 0; i < n; i++)
+        QIE_REQUIRE(draft[i] >= 0 && draft[i] < s.vocab, "%s: draft id %d out of range", who, draft[i]);
+    const int p = b->h_pos[seq];
+    QIE_REQUIRE((int64_t)p + n + 1 < b->max_ctx, "%s: %d rows from position %d do not fit max_ctx %d", who, M, p,
+                b->max_ctx);
+    // all-or-nothing, before anything is allocated or launched: qie_verify's reservation for n drafts
+    const PagePool::Span span{seq, p, (int64_t)p + M - 1, false};
+    KvWrites kv;
+    QIE_TRY(plan_kv_writes(b, &span, 1, kv));
+    if (!kv.fits())
+        return fail(-28, "%s: KV pool exhausted (%lld more pages needed for %d rows at position %d, %lld free)", who,
+                    (long long)kv.r.need, M, p, (long long)kv.free);
+    QIE_TRY(ensure_verify_tree_bufs(b));
+    QIE_TRY(commit_kv_writes(b, kv));
+    hipStream_t st = e->stream;
+    // drafts and parents in one copy (words kVtDraft .. kVtParent + 16)
+    int32_t in[2 * kVerifyMaxRows] = {0};
+    for (int i = 0; i < n; i++) in[kVtDraft + i] = draft[i], in[kVtParent + i] = tree->parent[i];
+    QIE_HIP(hipMemcpyAsync(b->vt, in, sizeof(in), hipMemcpyHostToDevice, st));
+    QIE_TRY(launch_verify_tree(b, seq, M, smp));
+    int32_t res[kVerifyMaxRows + 1] = {0};
+    QIE_TRY(read_back(b, res, b->vt + kVtRes, sizeof(res), who));
+    const int got = res[0];
+    if (got < 1 || got > M) return fail(-5, "%s: the step reported %d accepted nodes of %d", who, got, M);
+    for (int i = 0; i < got; i++) out_ids[i] = res[1 + i];
+    *n_out = got;
+    b->h_pos[seq] = p + got;
+    b->v_rows = M;
     return 0;
 }
 

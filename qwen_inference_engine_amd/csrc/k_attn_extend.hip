@@ -66,6 +66,13 @@ __global__ __launch_bounds__(256, 2) void attn_extend_fp8_kernel(ExtendAttnParam
     attn_extend_block<HD, PG, true>(a, seq, row0, R, blockIdx.x, blockIdx.y, kvh);
 }
 
+// ... for the M <= 16 rows of a draft tree (qie_attention_extend_tree): one run of one sequence,
+// grid (row blocks, splits, nkv); attn_extend_block's TREE form masks by ancestry.
+template <int HD, bool PG>
+__global__ __launch_bounds__(256, 2) void attn_extend_tree_kernel(ExtendTreeParams a, int seq) {
+    attn_extend_block<HD, PG, false, true>(a, seq, 0, (int)a.M, blockIdx.x, blockIdx.y, blockIdx.z);
+}
+
 // The checks, parameters and grid both cache forms share (`c`: the bf16 descriptor, or the fp8
 // descriptor's layout part); nothing is launched.  `who` names the op in a refusal.
 static int extend_plan(const char* who, const void* q, int64_t M, const int32_t* pos, int32_t rows_per_seq,
@@ -147,6 +154,29 @@ int qie_attention_extend(const void* q, int64_t M, const int32_t* pos, int32_t r
     auto k = cache->head_dim == 128 ? (pg ? attn_extend_kernel<128, true> : attn_extend_kernel<128, false>)
                                     : (pg ? attn_extend_kernel<64, true> : attn_extend_kernel<64, false>);
     return extend_launch(k, a, grid, cache->head_dim, stream);
+}
+
+int qie_attention_extend_tree(const void* q, int32_t M, const int32_t* row, const int32_t* anc, int32_t seq,
+                              const qie_kv_cache* cache, int32_t layer, int32_t n_heads, void* out, void* ws,
+                              void* stream) {
+    const char* who = "qie_attention_extend_tree";
+    QIE_REQUIRE(q && row && anc && cache && cache->k && cache->v && out && M >= 1 && M <= 16 && n_heads > 0 && seq >= 0,
+                "%s: bad arguments (1 .. 16 rows)", who);
+    ExtendTreeParams a;
+    dim3 grid;
+    QIE_TRY(extend_plan(who, q, M, row, M, cache, layer, n_heads, out, ws, &a, &grid));
+    a.anc = anc;
+    const bool pg = a.km.table != nullptr;
+    auto k = cache->head_dim == 128 ? (pg ? attn_extend_tree_kernel<128, true> : attn_extend_tree_kernel<128, false>)
+                                    : (pg ? attn_extend_tree_kernel<64, true> : attn_extend_tree_kernel<64, false>);
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k, grid, dim3(256), (size_t)2 * 2 * 64 * cache->head_dim * 2, st, a, seq);
+    QIE_LAUNCH_CHECK();
+    if (a.nsplit > 1) {
+        launch_attn_combine<true>(cache->head_dim, a.M, a.nq, a.nsplit, a.part_o, a.part_ml, a.out, st);
+        QIE_LAUNCH_CHECK();
+    }
+    return 0;
 }
 
 int qie_attention_extend_fp8(const void* q, int64_t M, const int32_t* pos, int32_t rows_per_seq,

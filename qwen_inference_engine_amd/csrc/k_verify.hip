@@ -24,24 +24,6 @@ __global__ __launch_bounds__(256) void verify_rows_kernel(VerifyRowsArgs a) {
     }
 }
 
-// n bf16 elements src -> dst in 16-byte words where the two rows share their offset within a
-// 16-byte line (element-wise up to the first boundary and past the last), else element-wise
-__device__ __forceinline__ void copy_row_bf16(const uint16_t* __restrict__ src, uint16_t* __restrict__ dst, int64_t n) {
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const uintptr_t so = (uintptr_t)src & 15, dof = (uintptr_t)dst & 15;
-    if (so != dof) {
-        for (int64_t j = tid; j < n; j += nt) dst[j] = src[j];
-        return;
-    }
-    const int64_t head = so ? min((int64_t)((16 - so) / 2), n) : 0;
-    const int64_t body = (n - head) / 8;
-    for (int64_t j = tid; j < head; j += nt) dst[j] = src[j];
-    const uint4* s4 = reinterpret_cast<const uint4*>(src + head);
-    uint4* d4 = reinterpret_cast<uint4*>(dst + head);
-    for (int64_t j = tid; j < body; j += nt) d4[j] = s4[j];
-    for (int64_t j = head + body * 8 + tid; j < n; j += nt) dst[j] = src[j];
-}
-
 // One block.  Row i chose token t_i (fused arg-max keys or sampled ids, clamped as
 // finalize_kernel clamps); the accepted length is the largest a with draft[j - 1] == t_(j - 1)
 // for all 1 <= j <= a.  The sequence is left exactly as after a + 1 decode steps: history

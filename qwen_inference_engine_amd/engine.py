@@ -491,6 +491,29 @@ class Batch:
         self._verify_rows = n + 1
         return [int(t) for t in out[:n_out.value]]
 
+    def verify_tree(self, seq: int, ids: Sequence[int], parents: Sequence[int],
+                    sampling: Sampling = GREEDY) -> List[int]:
+        """verify() for a tree of drafts (qie_verify_tree).  Node 0 is the pending current token;
+        node i >= 1 holds ids[i - 1] and hangs under node parents[i - 1] < i, so siblings are
+        alternative guesses for one position (at most 15 nodes).  One pass over the weights
+        scores every node against its own root path; returns the tokens of the longest root path
+        the model agrees with, t_0 .. t_a.  The sequence is then exactly as after len(result)
+        decode steps; verify_logits() returns the rows in node order."""
+        n = len(ids)
+        if len(parents) != n:
+            raise ValueError("verify_tree: one parent per drafted id")
+        if n > _lib.QIE_VERIFY_MAX_ROWS - 1:
+            raise ValueError(f"verify_tree: at most {_lib.QIE_VERIFY_MAX_ROWS - 1} drafted nodes")
+        arr = (C.c_int32 * max(n, 1))(*[int(i) for i in ids])
+        tree = _lib.DraftTreeC(n, (C.c_int32 * 15)(*[int(p) for p in parents]))
+        out = (C.c_int32 * (n + 1))()
+        n_out = C.c_int32(0)
+        sc = sampling.to_c()
+        _lib.check(self.lib.qie_verify_tree(self.h, seq, arr, C.byref(tree), C.byref(sc), out, C.byref(n_out)),
+                   "qie_verify_tree")
+        self._verify_rows = n + 1
+        return [int(t) for t in out[:n_out.value]]
+
     def verify_batch(self, items: Sequence[tuple], sampling: Sampling = GREEDY) -> List[List[int]]:
         """verify() for several slots in one pass over the weights (qie_verify_batch).  items: a
         list of (seq, draft), slots strictly increasing, every slot with its current token and

@@ -51,6 +51,46 @@ class NgramDrafter:
                     return h[i + n:i + n + k]
         return []
 
+    def propose_tree(self, history: Sequence[int], k: int, width: int):
+        """A draft tree for ``Batch.verify_tree``: (ids, parents) of at most k nodes.  Takes the
+        `width` most recent earlier occurrences of the longest recurring suffix whose continuations
+        differ, most recent first, and merges the continuations into a trie (node 0 is the pending
+        token; a shared prefix is one path).  The most recent continuation is inserted whole before
+        the next one starts, so width 1 gives propose()'s chain."""
+        h = list(history)
+        ids: List[int] = []
+        parents: List[int] = []
+        if k <= 0 or width <= 0:
+            return ids, parents
+        for n in range(self.max_ngram, self.min_ngram - 1, -1):
+            if len(h) <= n:
+                continue
+            suffix = h[-n:]
+            conts: List[List[int]] = []
+            for i in range(len(h) - n - 1, -1, -1):
+                if h[i:i + n] == suffix:
+                    c = h[i + n:i + n + k]
+                    if c and c not in conts:
+                        conts.append(c)
+                        if len(conts) == width:
+                            break
+            if not conts:
+                continue
+            child: Dict[tuple, int] = {}   # (parent node, id) -> node
+            for c in conts:
+                cur = 0
+                for t in c:
+                    nxt = child.get((cur, t))
+                    if nxt is None:
+                        if len(ids) == k:
+                            break
+                        ids.append(t)
+                        parents.append(cur)
+                        nxt = child[(cur, t)] = len(ids)
+                    cur = nxt
+            return ids, parents
+        return ids, parents
+
 
 class ModelDrafter:
     """Proposes k greedy decode steps of a draft model (slot `seq` of `draft_batch`, a batch of
@@ -108,10 +148,14 @@ class SpeculativeDecoder:
     ``drafted`` (ids handed to verify), ``accepted`` (drafts the target agreed with) and
     ``emitted`` (tokens returned, the prefill's first token included)."""
 
-    def __init__(self, batch, drafter, seq: int = 0, k: int = 4):
+    def __init__(self, batch, drafter, seq: int = 0, k: int = 4, tree_width: int = 1):
         if not 0 <= k <= MAX_DRAFT:
             raise ValueError(f"SpeculativeDecoder: k must be in [0, {MAX_DRAFT}]")
+        if tree_width < 1:
+            raise ValueError("SpeculativeDecoder: tree_width must be >= 1")
         self.b, self.drafter, self.seq, self.k = batch, drafter, seq, k
+        # > 1: a drafter with propose_tree drafts a tree of k nodes for Batch.verify_tree
+        self.tree_width = tree_width
         self.stats: Dict[str, int] = dict(verify_calls=0, drafted=0, accepted=0, emitted=0)
         if getattr(drafter, "target_vocab", 0) is None:
             drafter.target_vocab = batch.e.spec.vocab
@@ -133,12 +177,21 @@ class SpeculativeDecoder:
             if room < 0:
                 break
             k = min(self.k, max_new - len(out) - 1, room)
-            draft = [int(t) for t in self.drafter.propose(history, k)][:k] if k > 0 else []
-            for i, t in enumerate(draft):                # never hand the target an id it lacks
-                if not 0 <= t < vocab:
-                    draft = draft[:i]
-                    break
-            ids = self.b.verify(self.seq, draft, sampling)
+            if self.tree_width > 1 and k > 0 and hasattr(self.drafter, "propose_tree"):
+                draft, parents = self.drafter.propose_tree(history, k, self.tree_width)
+                draft, parents = [int(t) for t in draft][:k], [int(q) for q in parents][:k]
+                if all(0 <= t < vocab for t in draft):
+                    ids = self.b.verify_tree(self.seq, draft, parents, sampling)
+                else:                                    # never hand the target an id it lacks
+                    draft = []
+                    ids = self.b.verify(self.seq, draft, sampling)
+            else:
+                draft = [int(t) for t in self.drafter.propose(history, k)][:k] if k > 0 else []
+                for i, t in enumerate(draft):            # never hand the target an id it lacks
+                    if not 0 <= t < vocab:
+                        draft = draft[:i]
+                        break
+                ids = self.b.verify(self.seq, draft, sampling)
             self.stats["verify_calls"] += 1
             self.stats["drafted"] += len(draft)
             self.stats["accepted"] += len(ids) - 1
