@@ -463,9 +463,24 @@ int qie_batch_prefix_drop(qie_batch* b, qie_kv_prefix* p);
  * re-captures the decode graph.  qie_batch_decode_mode returns the current mode.  Mode 1 is
  * SLOWER on MI355X (Qwen2-7B 317.5 vs 370.9 tok/s, Qwen2-0.5B 1,065 vs 1,566: its cross-CU
  * hand-offs cost more than the kernel boundaries they replace); mode 0 is
- * the default and the measured path. */
+ * the default and the measured path.
+ * 2 = mode 0's step with the shared-prefix decode attention (qie_attention_decode_shared,
+ * DESIGN.md §25) in place of qie_attention_decode: slots that hold the same leading KV pages
+ * (forks, prefix-cache loads) form a group, and the group's shared prompt prefix is read once per
+ * step for all of them.  The engine derives the share table from its block tables and positions
+ * before every step and uploads it when it changed; the captured step follows it without
+ * re-capture.  Mode 2 covers paged bf16-KV batches of a single-rank engine (no tp_comm, no
+ * comm_always) with head_dim 64 or 128; anything else returns QIE_EINVAL naming what is not
+ * covered.  Prefill, append, ragged, score and the verify calls run as in mode 0.  Results are
+ * within mode 0's parity bound, not bit-equal (other split boundaries and merge order).  Opt-in:
+ * on MI355X (Qwen2-7B heads, B = 8) mode 2 is FASTER only for many forks of a
+ * long prompt (eight forks at 32k tokens: 1,326 vs 1,225 tok/s) and SLOWER elsewhere (forks at 2k
+ * / 8k: 1,484 vs 1,888 / 1,427 vs 1,680 tok/s; eight unrelated sequences: 0.73 - 0.80 x).
+ * qie_batch_shared_prefix: the share table the next step would use (host arrays [B]); every
+ * entry is {m, 0} outside mode 2. */
 int qie_batch_set_decode_mode(qie_batch* b, int32_t mode);
 int qie_batch_decode_mode(const qie_batch* b);
+int qie_batch_shared_prefix(qie_batch* b, int32_t* leader, int32_t* n_shared);
 /* Diagnostics of decode mode 1: enable != 0 makes the persistent step record s_memrealtime
  * stamps (100 MHz, chip-wide) at its phase boundaries, [n_cu][n_layers][12] uint64 (slots:
  * 0 layer start, 1 x gathered, 2 QKV done, 3 attention done (attention CUs), 4 attention

@@ -255,6 +255,38 @@ int qie_attention_decode(const void* qkv, int64_t B, const int32_t* pos, const v
                          int32_t n_heads, const qie_kv_cache* cache, int32_t layer, float eps,
                          int32_t numerics, void* out, void* ws, void* stream);
 
+/* qie_attention_decode for slots that share a prompt prefix (cascade / Hydragen decoding,
+ * DESIGN.md §25).  The contract is qie_attention_decode's — row m is one query token of sequence
+ * m at pos[m], qk-norm and RoPE fused or QIE_ATTN_PREROPED, the new K/V row appended at pos[m] with
+ * the same bits, attention over keys [0, pos[m]] — with one change, the prefix rule: keys
+ * [0, share[m].n_shared) of row m are read from sequence share[m].leader's rows (its block-table
+ * row or contiguous region).  The caller guarantees that those rows hold what m's own would; the
+ * kernel never compares pages and never reads m's own rows below n_shared.  A group's prefix is
+ * read once for all its members, whose q rows are stacked as the MFMA M dimension.
+ * share is device data [B] (a captured launch follows any table).  Table rules (the host cannot
+ * check them; an entry that breaks them is read as a shorter prefix or a plain slot):
+ *   leader[m] <= m, and a leader's own entry has leader == itself;
+ *   n_shared % 128 == 0 (paged: a multiple of page_tokens as well), n_shared[m] <= pos[m];
+ *   a leader's own n_shared is at least every member's and at most pos[leader];
+ *   {m, 0} is a plain slot.
+ * B <= 8, n_heads / n_kv_heads <= 8, head_dim 64 or 128, contiguous and paged caches.  Results are
+ * not bit-equal to qie_attention_decode's (other split boundaries and merge order); they meet the
+ * same bound.  ws must hold qie_attention_decode_shared_workspace_bytes() and need not be
+ * initialised.  Two launches (the key walk, the merge); never allocates or synchronises;
+ * capturable.  -22 with nothing launched for null pointers, B outside [1, 8], a bad head shape or
+ * layer, or no workspace. */
+typedef struct qie_prefix_share {
+    int32_t leader;
+    int32_t n_shared;
+} qie_prefix_share;
+int64_t qie_attention_decode_shared_workspace_bytes(int64_t B, int32_t n_heads, int32_t n_kv_heads,
+                                                    int32_t head_dim, int32_t max_ctx);
+int qie_attention_decode_shared(const void* qkv, int64_t B, const int32_t* pos,
+                                const qie_prefix_share* share, const void* q_norm,
+                                const void* k_norm, const float* rope_cos, const float* rope_sin,
+                                int32_t n_heads, const qie_kv_cache* cache, int32_t layer,
+                                float eps, int32_t numerics, void* out, void* ws, void* stream);
+
 /* Diagnostics: one wave, lane l reads 8 bytes at element 4*l of an LDS array whose
  * element i holds i, through ds_read_b64_tr_b16; out_dev[l*4 + e] receives element e
  * of lane l (pins the transposed-read lane mapping the prefill attention relies on). */

@@ -103,6 +103,11 @@ class KvCacheFp8C(C.Structure):
     _fields_ = [("c", KvCacheC), ("k_exps", C.c_void_p), ("v_exps", C.c_void_p), ("exp_stride", C.c_int64)]
 
 
+class PrefixShareC(C.Structure):
+    """qie_prefix_share: keys [0, n_shared) of the row are read from sequence `leader`."""
+    _fields_ = [("leader", C.c_int32), ("n_shared", C.c_int32)]
+
+
 QIE_RAGGED_MAX_SEGS = 8
 
 
@@ -176,6 +181,9 @@ SIGNATURES = [
     ("qie_attention_decode_workspace_bytes", C.c_int64, [_I64, _I32, _I32, _I32, _I32]),
     ("qie_attention_decode", C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _I32, C.POINTER(KvCacheC), _I32, _F, _I32,
                                        _P, _P, _P]),
+    ("qie_attention_decode_shared_workspace_bytes", C.c_int64, [_I64, _I32, _I32, _I32, _I32]),
+    ("qie_attention_decode_shared", C.c_int, [_P, _I64, _P, _P, _P, _P, _P, _P, _I32, C.POINTER(KvCacheC), _I32, _F,
+                                              _I32, _P, _P, _P]),
     ("qie_debug_tr16_probe", C.c_int, [_P]),
     ("qie_qknorm", C.c_int, [_P, _I64, _I64, _I32, _I32, _P, _F, _I32, _P]),
     ("qie_rope", C.c_int, [_P, _I64, _I64, _I32, _I32, _P, _I32, _P, _P, _I32, _P]),
@@ -289,6 +297,7 @@ SIGNATURES = [
     ("qie_batch_dims", C.c_int, [_P, _PI32, _PI32]),
     ("qie_batch_set_decode_mode", C.c_int, [_P, _I32]),
     ("qie_batch_decode_mode", C.c_int, [_P]),
+    ("qie_batch_shared_prefix", C.c_int, [_P, _P, _P]),
     ("qie_batch_pk_trace", C.c_int, [_P, _I32, _P, C.c_int64]),
     ("qie_batch_kv_cache", C.c_int, [_P, _I32, C.POINTER(KvCacheC)]),
     ("qie_batch_kv_cache_fp8", C.c_int, [_P, _I32, C.POINTER(KvCacheFp8C)]),

@@ -218,6 +218,12 @@ struct qie_batch {
     // step epoch and the error word (zeroed once; the finalize kernel advances the epoch)
     int decode_mode = 0;
     void* pk_mem = nullptr;
+    // mode 2 (shared-prefix decode attention): the attention's workspace, the device
+    // share table [B] the captured step reads and the host copy of what was last uploaded; made
+    // together by the first switch to mode 2
+    void* sh_ws = nullptr;
+    qie_prefix_share* d_share = nullptr;
+    std::vector<qie_prefix_share> h_share;
     qie_layer_weights* d_layers = nullptr;
     void* d_attp = nullptr;      // the attention role's parameters per layer (persist_attn_table)
     unsigned long long* pk_ts = nullptr;   // qie_batch_pk_trace: phase timestamps [cu][layer][slots]
@@ -963,6 +969,13 @@ static int attend_decode(qie_batch* b, int l, void* out) {
         set_decode_rope_cur(nullptr);
         return rc;
     }
+    if (b->decode_mode == 2) {   // the slots' shared prompt prefixes are read once per group
+        set_decode_rope_cur(nullptr);
+        return qie_attention_decode_shared(b->dec.qkv, b->B, b->dec.pos, b->d_share, L.q_norm, L.k_norm, e->rope_cos,
+                                           e->rope_sin, e->sh.nq, &cache, l, s.rms_eps,
+                                           s.numerics | (rope_in_projection(b) ? QIE_ATTN_PREROPED : 0), out, b->sh_ws,
+                                           e->stream);
+    }
     const int rc = qie_attention_decode(b->dec.qkv, b->B, b->dec.pos, L.q_norm, L.k_norm, e->rope_cos, e->rope_sin, e->sh.nq,
                                         &cache, l, s.rms_eps,
                                         s.numerics | (rope_in_projection(b) ? QIE_ATTN_PREROPED : 0), out, b->dec.dec_ws,
@@ -1697,6 +1710,33 @@ static int flush_table(qie_batch* b) {
     return 0;
 }
 
+// Decode mode 2: the share table of the next step (page_pool.hpp derive_prefix_share) from the
+// pool's host mirror and the slots' positions.  Everything that moves a block-table row or a position
+// (prefill, append, ragged, fork, prefix load, release, set_position, copy-on-write, growth) goes
+// through that mirror and h_pos, so the table is derived anew before every step — a few hundred
+// integer compares — and uploaded only when its values changed: the captured step reads d_share,
+// values change, never the capture.  The copy completes before the host copy may change again.
+static void derive_share(const qie_batch* b, std::vector<qie_prefix_share>& t) {
+    int32_t leader[kMaxBatchSlots], n_shared[kMaxBatchSlots];
+    for (int m = 0; m < b->B; m++) leader[m] = m, n_shared[m] = 0;
+    if (b->decode_mode == 2) derive_prefix_share(b->pool, b->B, b->h_pos.data(), b->idle.data(), leader, n_shared);
+    t.resize(b->B);
+    for (int m = 0; m < b->B; m++) t[m] = qie_prefix_share{leader[m], n_shared[m]};
+}
+static int refresh_share(qie_batch* b) {
+    if (b->decode_mode != 2) return 0;
+    std::vector<qie_prefix_share> t;
+    derive_share(b, t);
+    bool same = t.size() == b->h_share.size();
+    for (size_t m = 0; same && m < t.size(); m++)
+        same = t[m].leader == b->h_share[m].leader && t[m].n_shared == b->h_share[m].n_shared;
+    if (same) return 0;
+    QIE_HIP(hipMemcpyAsync(b->d_share, t.data(), t.size() * sizeof(qie_prefix_share), hipMemcpyHostToDevice, b->e->stream));
+    QIE_HIP(hipStreamSynchronize(b->e->stream));
+    b->h_share = t;
+    return 0;
+}
+
 // The reservation of one engine call: every call that writes KV rows names them
 // as spans — positions [lo, hi] of a slot; hi < lo: only growth to lo tokens; restart: the slot
 // begins a new sequence — plans them, compares need with free under its own error line, and
@@ -2129,7 +2169,7 @@ void qie_batch_destroy(qie_batch* b) {
     free_rows(b->v);
     free_rows(b->sc);
     for (void* p : {(void*)b->kc, (void*)b->vc, (void*)b->ke, (void*)b->ve, (void*)b->sk, (void*)b->sv, (void*)b->d_table, b->pk_mem, (void*)b->d_layers, b->d_attp,
-                    (void*)b->pk_ts, (void*)b->d_slots, b->rows_ws, (void*)b->vb_aux, (void*)b->vt})
+                    (void*)b->pk_ts, (void*)b->d_slots, b->rows_ws, (void*)b->vb_aux, (void*)b->vt, b->sh_ws, (void*)b->d_share})
         if (p) hipFree(p);
     for (void* p : b->retired) hipFree(p);
     // (the DevBlock workspaces free themselves)
@@ -2524,7 +2564,10 @@ static int prepare_steps(qie_batch* b, int n_steps, const char* who) {
             QIE_TRY(set_slot_state(b, m, 0, 0, 0, 1));
             b->h_pos[m] = 0;
         }
-    return 0;
+    // mode 2: after the steps' copy-on-write and growth.  One derivation covers all n_steps replays:
+    // the pages every step writes were made private and grown just above, so no block-table row
+    // moves between the replays, and positions only grow, so n_shared <= pos keeps holding
+    return refresh_share(b);
 }
 
 int qie_decode_step(qie_batch* b, const qie_sampling* smp, int32_t* next_ids) {
@@ -2673,7 +2716,7 @@ int qie_verify(qie_batch* b, int32_t seq, const int32_t* draft, int32_t n_draft,
     QIE_REQUIRE(!(e->fp8 && e->opts.prefill_fp8),
                 "qie_verify: not available on a prefill_fp8 engine (block-scaled fp8 activations are defined for a "
                 "prefill from position 0 only)");
-    QIE_REQUIRE(b->decode_mode == 0, "qie_verify: the batch is in decode mode 1 (the persistent step); verify runs "
+    QIE_REQUIRE(b->decode_mode != 1, "qie_verify: the batch is in decode mode 1 (the persistent step); verify runs "
                                      "the five-launch layer, set mode 0 first");
     for (int i = 0; i < n_draft; i++)
         QIE_REQUIRE(draft[i] >= 0 && draft[i] < s.vocab, "qie_verify: draft id %d out of range", draft[i]);
@@ -2809,7 +2852,7 @@ int qie_verify_tree(qie_batch* b, int32_t seq, const int32_t* draft, const qie_d
     QIE_REQUIRE(!(e->fp8 && e->opts.prefill_fp8),
                 "%s: not available on a prefill_fp8 engine (block-scaled fp8 activations are defined for a "
                 "prefill from position 0 only)", who);
-    QIE_REQUIRE(b->decode_mode == 0, "%s: the batch is in decode mode 1 (the persistent step); verify runs "
+    QIE_REQUIRE(b->decode_mode != 1, "%s: the batch is in decode mode 1 (the persistent step); verify runs "
                                      "the five-launch layer, set mode 0 first", who);
     QIE_REQUIRE(!e->comm && !e->opts.tp_comm && !e->opts.comm_always,
                 "%s: not available on an engine with tp_comm / comm_always (tensor parallelism is out of scope)", who);
@@ -2949,7 +2992,7 @@ int qie_verify_batch(qie_batch* b, const qie_verify_seg* segs, int32_t n_segs, c
     QIE_REQUIRE(!(e->fp8 && e->opts.prefill_fp8),
                 "%s: not available on a prefill_fp8 engine (block-scaled fp8 activations are defined for a "
                 "prefill from position 0 only)", who);
-    QIE_REQUIRE(b->decode_mode == 0, "%s: the batch is in decode mode 1 (the persistent step); verify runs "
+    QIE_REQUIRE(b->decode_mode != 1, "%s: the batch is in decode mode 1 (the persistent step); verify runs "
                                      "the five-launch layer, set mode 0 first", who);
     qie_row_segs t{};
     PagePool::Span spans[kMaxBatchSlots];   // n_segs <= B <= kMaxBatchSlots
@@ -3029,8 +3072,37 @@ int qie_verify_logprobs(qie_batch* b, const int32_t* ids, float* out) {
 }
 
 int qie_batch_set_decode_mode(qie_batch* b, int32_t mode) {
-    QIE_REQUIRE(b && (mode == 0 || mode == 1), "qie_batch_set_decode_mode: bad arguments (mode 0 or 1)");
+    QIE_REQUIRE(b && (mode == 0 || mode == 1 || mode == 2), "qie_batch_set_decode_mode: bad arguments (mode 0, 1 or 2)");
     qie_engine* e = b->e;
+    if (mode == 2) {
+        QIE_NO_KV8(b, "qie_batch_set_decode_mode(2)");
+        QIE_REQUIRE(b->d_table, "qie_batch_set_decode_mode: mode 2 (shared-prefix decode attention) needs a paged "
+                                "batch: a contiguous batch's forks copy rows, there is nothing to share");
+        QIE_REQUIRE(!e->comm && !e->opts.tp_comm && !e->opts.comm_always && e->sh.tp == 1,
+                    "qie_batch_set_decode_mode: mode 2 is not available on an engine with tp_comm / comm_always");
+        QIE_REQUIRE(e->spec.head_dim == 64 || e->spec.head_dim == 128,
+                    "qie_batch_set_decode_mode: mode 2 needs head_dim 64 or 128 (got %d)", (int)e->spec.head_dim);
+        static_assert(kMaxBatchSlots <= 8, "qie_attention_decode_shared serves at most 8 rows: every batch must fit");
+        if (!b->sh_ws || !b->d_share) {
+            // both or none: a failed allocation leaves the batch in its mode with nothing held
+            hipFree(b->sh_ws);
+            hipFree(b->d_share);
+            b->sh_ws = nullptr;
+            b->d_share = nullptr;
+            const qie_kv_cache cache = batch_cache(b, 0);
+            void *ws = nullptr, *tb = nullptr;
+            if (dmalloc(&ws, (size_t)qie_attention_decode_shared_workspace_bytes(b->B, e->sh.nq, e->sh.nkv, e->spec.head_dim,
+                                                                                 cache.max_ctx)) ||
+                dmalloc(&tb, sizeof(qie_prefix_share) * b->B)) {
+                hipFree(ws);
+                hipFree(tb);
+                return fail(-2, "qie_batch_set_decode_mode: device allocation failed: %s", qie_last_error());
+            }
+            b->sh_ws = ws;
+            b->d_share = (qie_prefix_share*)tb;
+        }
+        b->h_share.clear();   // the next step uploads the table
+    }
     if (mode == 1) {
         QIE_NO_KV8(b, "qie_batch_set_decode_mode(1)");
         const char* why = "";
@@ -3074,6 +3146,14 @@ int qie_batch_set_decode_mode(qie_batch* b, int32_t mode) {
 }
 
 int qie_batch_decode_mode(const qie_batch* b) { return b ? b->decode_mode : -22; }
+
+int qie_batch_shared_prefix(qie_batch* b, int32_t* leader, int32_t* n_shared) {
+    QIE_REQUIRE(b && leader && n_shared, "qie_batch_shared_prefix: bad arguments");
+    std::vector<qie_prefix_share> t;
+    derive_share(b, t);
+    for (int m = 0; m < b->B; m++) leader[m] = t[m].leader, n_shared[m] = t[m].n_shared;
+    return 0;
+}
 
 int qie_batch_pk_trace(qie_batch* b, int32_t enable, uint64_t* host_out, int64_t n) {
     QIE_REQUIRE(b, "qie_batch_pk_trace: null batch");
@@ -3227,6 +3307,7 @@ int qie_batch_time_kernel(qie_batch* b, int32_t which, int32_t iters, double* av
     qie_engine* e = b->e;
     if (which >= 5) QIE_NO_KV8(b, "qie_batch_time_kernel (which 5 / 6)");
     if (which == 6) return time_persistent(b, iters, avg_us, bytes);
+    if (which == 5) QIE_TRY(refresh_share(b));   // mode 2: the table the next step would use
     const qie_model_spec& s = e->spec;
     const TpShard& sh = e->sh;   // this rank's shard sizes
     const int64_t H = s.hidden, hd = s.head_dim, QD = (int64_t)sh.nq * hd, KD = (int64_t)sh.nkv * hd;

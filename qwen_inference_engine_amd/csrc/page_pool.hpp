@@ -212,4 +212,33 @@ struct PagePool {
     }
 };
 
+// The share table of the shared-prefix decode attention (qie_attention_decode_shared, DESIGN.md
+// §25) from the pool's block tables and the slots' positions; plain host code.  A live slot's leader
+// is the lowest live slot with which it has at least one identical leading page id (so a leader
+// leads itself: equal first pages are transitive); n_shared = page_tokens x the count of identical
+// leading page ids with that leader, capped so that n_shared <= pos of the slot and of the leader; a
+// leader's entry is the maximum of its members'.  Idle slots and slots that share nothing get
+// {m, 0}.  Pages past the shared run are private, so growth never adds to it: the run only shrinks,
+// through copy-on-write or a release.
+inline void derive_prefix_share(const PagePool& pool, int B, const int32_t* pos, const char* idle, int32_t* leader,
+                                int32_t* n_shared) {
+    for (int m = 0; m < B; m++) leader[m] = m, n_shared[m] = 0;
+    for (int m = 1; m < B; m++) {
+        if (idle[m]) continue;
+        for (int l = 0; l < m; l++) {
+            if (idle[l]) continue;
+            const int lim = pool.held[l] < pool.held[m] ? pool.held[l] : pool.held[m];
+            int run = 0;
+            while (run < lim && pool.row(l)[run] == pool.row(m)[run] && pool.row(m)[run] != 0) run++;
+            const int cap = (pos[m] < pos[l] ? pos[m] : pos[l]) / pool.page_tokens;
+            if (run > cap) run = cap;
+            if (run == 0) continue;
+            leader[m] = l;
+            n_shared[m] = run * pool.page_tokens;
+            if (n_shared[m] > n_shared[l]) n_shared[l] = n_shared[m];
+            break;
+        }
+    }
+}
+
 }  // namespace qie

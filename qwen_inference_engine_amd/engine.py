@@ -691,8 +691,16 @@ class Batch:
         return list(out), xs
 
     def set_decode_mode(self, mode: int) -> None:
-        """0: five launches per layer; 1: the persistent layer stack (qie_batch_set_decode_mode)."""
+        """0: five launches per layer; 1: the persistent layer stack; 2: mode 0 with the shared-prefix
+        decode attention, paged batches only (qie_batch_set_decode_mode)."""
         _lib.check(self.lib.qie_batch_set_decode_mode(self.h, mode), "qie_batch_set_decode_mode")
+
+    def shared_prefix(self):
+        """(leader, n_shared) per slot: the share table the next decode step would use in mode 2
+        (qie_batch_shared_prefix); every entry is (m, 0) in the other modes."""
+        leader, n_shared = (C.c_int32 * self.B)(), (C.c_int32 * self.B)()
+        _lib.check(self.lib.qie_batch_shared_prefix(self.h, leader, n_shared), "qie_batch_shared_prefix")
+        return list(leader), list(n_shared)
 
     @property
     def decode_mode(self) -> int:
