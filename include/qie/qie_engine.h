@@ -431,7 +431,11 @@ int qie_batch_fork(qie_batch* b, int32_t src, int32_t dst, int32_t n_tokens, int
  * sampler's own workspace beside it); a set is a copy ordered on the engine's stream.  The
  * captured decode graph and captured verify steps READ the table: changing an entry's values
  * never re-captures; "some slot has an entry" flipping does, as a change of the call's
- * qie_sampling does.  Tensor parallelism / comm_always: rows of a launch with an entry take the
+ * qie_sampling does.  top_k == QIE_TOP_K_ALL (the whole vocabulary; qie_types.h) in an entry or
+ * in the call's qie_sampling needs two launches of its own behind qie_sample_rows' two: "some
+ * slot's entry, or the call's qie_sampling, has top_k == QIE_TOP_K_ALL" is tracked and re-captures
+ * in the same way, and a step holds those launches only then — a batch that never uses the
+ * value launches exactly what it launched before the value existed.  Tensor parallelism / comm_always: rows of a launch with an entry take the
  * gathered-row path of the sampled head, every rank samples the same full row — the caller
  * sets the same entries on every rank. */
 int qie_batch_set_slot_sampling(qie_batch* b, int32_t seq, const qie_slot_sampling* p);

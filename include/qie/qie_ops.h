@@ -352,7 +352,9 @@ int qie_residual_add_f32(void* x, const float* sum, int64_t n, void* stream);
 /* ---------------------------------------------------------------- sampling
  * Replaces sample_topk_bf16 / topk_temperature_softmax_sampling_kernel_bf16
  * (helpers.cuh:157-166, logit_decode.cu:149-274).  Writes the chosen id of each
- * of the M logit rows to out_ids (device).  top_k <= 1 -> greedy arg-max.
+ * of the M logit rows to out_ids (device).  top_k <= 1 -> greedy arg-max, except
+ * top_k == QIE_TOP_K_ALL with temperature > 0: the whole vocabulary (the contract at
+ * qie_sample_rows, on the unprocessed row, min_p off; two launches of their own).
  * ws must hold qie_sample_workspace_bytes(). */
 int64_t qie_sample_workspace_bytes(int64_t M, int64_t V);
 int qie_sample(const void* logits, int64_t M, int64_t V, int64_t ld, const qie_sampling* s,
@@ -380,6 +382,33 @@ int qie_keys_to_ids(const uint64_t* keys, int64_t M, int32_t* out_ids, void* str
  *     w_i = expf(v_i - m); min_p in (0, 1]: the leading entries with w_i >= min_p stay (entry 0
  *     always); then top_p and the one XORWOW draw from seed + step exactly as qie_sample.
  * A row with no selectable element (NaN / -inf only) yields -1.
+ *
+ * The whole vocabulary: top_k == QIE_TOP_K_ALL and temperature > 0 (0, 1 and every other negative
+ * top_k stay greedy; !(temperature > 0) stays greedy whatever top_k is).  l' as above; then
+ *   1. candidates: every j < V with l'[j] selectable (not NaN, above -inf), in descending
+ *      selection-key order; none: -1.
+ *   2. a candidate's weight depends on its bf16 value b alone: w(b) = expf(b / T - m) in fp32,
+ *      uncontracted, m = (max b) / T — the formulas of the top-k path.
+ *   3. bins: the value's monotone 16-bit key (the top half of the selection key) gives at most
+ *      65,536 bins, a bin's mass is (float)count * w(b) with an integer count.
+ *   4. min_p in (0, 1]: the bins with w(b) >= min_p stay, the top bin always.
+ *   5. cumulative masses over the remaining non-empty bins in descending key order, in ONE fixed
+ *      two-level order: a group of 256 consecutive keys (key >> 8) sums its bins sequentially in
+ *      fp32, descending, from 0; the 256 group sums are summed sequentially, descending, from 0;
+ *      cum(bin) = (the sum of the groups above its group) + (its group's own sum down to it).
+ *   6. top_p in (0, 1): the shortest prefix of bins with cum >= top_p * total stays, total the
+ *      last bin's cum.  The cut bin stays WHOLE — ties at the threshold value all stay; the
+ *      top-k path cuts between equal values.  kept_total = the cut bin's cum.
+ *   7. u = xorwow_uniform_first(seed + step) * kept_total; the bin is the first with cum >= u;
+ *      inside it the member is the smallest r with u <= cum_before + (float)(r + 1) * w (fp32,
+ *      uncontracted; cum_before the previous bin's cum, 0 for the first), clamped to the last
+ *      member, members in descending selection-key order: bitrev8(idx & 255) down, then idx up.
+ *   8. integer atomics only, no float atomics, no workgroup waits on another: two runs are
+ *      bit-identical.
+ * Where every partial sum is exact (a support of equal values, everything else at weight exactly
+ * 0) the result is the top-k path's.  Rows in ALL mode run two launches of their own and leave
+ * the two top-k launches at once, the other rows the reverse; the public forms always enqueue
+ * all four (the table is device data).
  * Window of row m: the ids at positions [lo, q] of its slot's history row, q = q_dev[m],
  *     lo = max(e.penalty_start, e.penalty_last_n > 0 ? q + 1 - e.penalty_last_n : 0, 0);
  * with a tail (tail_len_dev[m] = n > 0) the positions (q - n, q] hold tail_dev[0 .. n) instead

@@ -86,7 +86,11 @@ typedef struct qie_model_weights {
  * (logit_decode.cu:149-274): k rounds of masked arg-max (k <= 256), softmax at
  * temperature T, one cuRAND-XORWOW uniform draw seeded (seed, subseq = 0).
  * top_p < 1 additionally truncates the top-k list to the smallest prefix whose
- * probability mass reaches top_p (qie extension; the reference has no top-p). */
+ * probability mass reaches top_p (qie extension; the reference has no top-p).
+ * top_k == QIE_TOP_K_ALL (with temperature > 0) samples from the whole vocabulary: no top-k
+ * cut, only temperature, top_p and (in an entry) min_p — the contract is stated at
+ * qie_sample_rows in qie_ops.h.  0 and every other negative value stay greedy. */
+#define QIE_TOP_K_ALL (-1)
 typedef struct qie_sampling {
     int32_t top_k;
     float temperature;

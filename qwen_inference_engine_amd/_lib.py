@@ -63,6 +63,7 @@ class SamplingC(C.Structure):
 
 
 QIE_SLOT_BIAS_MAX = 32
+QIE_TOP_K_ALL = -1   # top_k of SamplingC / SlotSamplingC: sample from the whole vocabulary (qie_types.h)
 
 
 class SlotSamplingC(C.Structure):

@@ -16,6 +16,7 @@
 // device memory so the graph replays without host edits.
 #include "qie_common.hpp"
 #include "linear_plan.hpp"
+#include "launch_util.hpp"
 #include "../../include/qie/qie_engine.h"
 #include "qie_index.hpp"
 #include "qie_comm.hpp"
@@ -239,6 +240,7 @@ struct qie_batch {
         qie_row_segs segs{};   // qie_verify_batch: the table (n >= 1, and seq = -1); qie_verify: n = 0
         bool all_entries = false;   // qie_verify_batch: EVERY segment's slot held an entry (else the
                                     // call's sampling is captured for the rows of slots without one)
+        bool all_mode = false;      // captured with the whole-vocabulary launches
     };
     int v_captures = 0;   // verify steps captured so far, both kinds (qie_batch_debug_verify_captures)
     std::vector<VerifyGraph> v_graphs;
@@ -261,10 +263,12 @@ struct qie_batch {
     std::vector<qie_slot_sampling> slot_h;
     std::vector<char> slot_set;
     int n_slot_set = 0;
+    int n_slot_all = 0;   // ... of them with top_k == QIE_TOP_K_ALL
     qie_slot_sampling* d_slots = nullptr;
     int32_t* d_tail_len = nullptr;
     void* rows_ws = nullptr;
     bool g_entries = false;   // the decode graph was captured on the entry path
+    bool g_all = false;       // ... with the whole-vocabulary launches (all_mode)
 };
 
 namespace qie {
@@ -1053,7 +1057,9 @@ static int enqueue_layer_rows(qie_batch* b, int l, const LayerRows& r, const Lay
     return run_row_proj(b, down_args(e, L, p.flags, r), p.in, r);
 }
 
-static bool is_greedy(const qie_sampling* s) { return !s || s->top_k <= 1 || !(s->temperature > 0.f); }
+static bool is_greedy(const qie_sampling* s) {
+    return !s || (s->top_k <= 1 && s->top_k != QIE_TOP_K_ALL) || !(s->temperature > 0.f);
+}
 
 // tmp[r][i][j] (rank r's logit shard of row i) -> full[m0 + i][r * Vl + j]
 __global__ void unshard_rows_kernel(const uint16_t* __restrict__ tmp, uint16_t* __restrict__ full, int tp, int M,
@@ -1112,6 +1118,13 @@ struct EntryRows {
     const int32_t *q, *tail, *tail_len;
     const int32_t *row_slot = nullptr, *tail_off = nullptr;
 };
+// Can a row that samples through the entry table be in ALL mode: some slot's entry, or the
+// call's sampling (what rows without an entry use), has top_k == QIE_TOP_K_ALL?  Entries are
+// device data, so this decides at enqueue (and capture) time whether the whole-vocabulary
+// launches are part of the step; it is part of every captured step's key.
+static bool all_mode(const qie_batch* b, const qie_sampling* smp) {
+    return b->n_slot_all > 0 || (smp && smp->top_k == QIE_TOP_K_ALL);
+}
 // does a slot of [m0, m0 + M) hold an entry?
 static bool any_entry(const qie_batch* b, int m0, int M) {
     if (b->n_slot_set == 0) return false;
@@ -1147,8 +1160,7 @@ static int enqueue_head_rows(qie_batch* b, const uint16_t* x, int64_t ldx, int M
             ra.hist = b->dec.hist, ra.hist_stride = b->max_ctx;
             ra.q_dev = er->q, ra.tail_dev = er->tail, ra.tail_len_dev = er->tail_len;
             ra.step_dev = hb.step, ra.out_ids = hb.ids, ra.ws = b->rows_ws;
-            if (er->row_slot) QIE_TRY(qie_sample_rows_mapped(&ra, er->row_slot, er->tail_off, st));
-            else QIE_TRY(qie_sample_rows(&ra, st));
+            QIE_TRY(sample_rows_launch(&ra, er->row_slot, er->tail_off, all_mode(b, smp), st));
         } else {
             QIE_TRY(qie_sample(lg, M, s.vocab, s.vocab, smp, hb.step, hb.ids, hb.samp_ws, st));
         }
@@ -1912,6 +1924,8 @@ static int write_slot_entry(qie_batch* b, int seq, const qie_slot_sampling* p) {
     QIE_HIP(hipMemcpyAsync(b->d_slots + seq, &v, sizeof(v), hipMemcpyHostToDevice, b->e->stream));
     QIE_HIP(hipStreamSynchronize(b->e->stream));   // `v` goes out of scope
     b->n_slot_set += (p ? 1 : 0) - (b->slot_set[seq] ? 1 : 0);
+    b->n_slot_all += (p && p->top_k == QIE_TOP_K_ALL ? 1 : 0) -
+                     (b->slot_set[seq] && b->slot_h[seq].top_k == QIE_TOP_K_ALL ? 1 : 0);
     b->slot_set[seq] = p ? 1 : 0;
     b->slot_h[seq] = p ? *p : qie_slot_sampling{};
     return 0;
@@ -2526,13 +2540,15 @@ static int launch_step(qie_batch* b, const qie_sampling* smp) {
     qie_engine* e = b->e;
     if (!e->opts.use_graph) return enqueue_decode(b, smp);
     // (entry VALUES are read from the device table: only "some slot has an entry" is captured)
-    if (!b->graph_ok || !same_sampling(b->gs, smp) || b->g_entries != (b->n_slot_set > 0)) {
+    if (!b->graph_ok || !same_sampling(b->gs, smp) || b->g_entries != (b->n_slot_set > 0) ||
+        b->g_all != all_mode(b, smp)) {
         if (b->gexec) hipGraphExecDestroy(b->gexec);
         b->gexec = nullptr;
         b->graph_ok = false;
         QIE_TRY(capture_graph(e, "", [&] { return enqueue_decode(b, smp); }, &b->gexec));
         b->gs = smp ? *smp : qie_sampling{1, 0.f, 1.f, 0};
         b->g_entries = b->n_slot_set > 0;
+        b->g_all = all_mode(b, smp);
         b->graph_ok = true;
     }
     QIE_HIP(hipGraphLaunch(b->gexec, e->stream));
@@ -2686,7 +2702,7 @@ static int launch_verify(qie_batch* b, int seq, int M, const qie_sampling* smp) 
     if (!e->opts.use_graph) return enqueue_verify(b, seq, M, smp);
     const bool greedy = is_greedy(smp), entries = any_entry(b, seq, 1);
     for (const auto& g : b->v_graphs)
-        if (g.seq == seq && g.M == M && g.entries == entries &&
+        if (g.seq == seq && g.M == M && g.entries == entries && g.all_mode == all_mode(b, smp) &&
             (entries || (g.greedy == greedy && (greedy || same_sampling(g.smp, smp))))) {
             QIE_HIP(hipGraphLaunch(g.exec, e->stream));
             return 0;
@@ -2698,7 +2714,7 @@ static int launch_verify(qie_batch* b, int seq, int M, const qie_sampling* smp) 
     hipGraphExec_t exec = nullptr;
     QIE_TRY(capture_graph(e, "qie_verify: ", [&] { return enqueue_verify(b, seq, M, smp); }, &exec));
     b->v_captures++;
-    b->v_graphs.push_back({seq, M, entries, greedy, smp ? *smp : qie_sampling{1, 0.f, 1.f, 0}, exec});
+    b->v_graphs.push_back({seq, M, entries, greedy, smp ? *smp : qie_sampling{1, 0.f, 1.f, 0}, exec, {}, false, all_mode(b, smp)});
     QIE_HIP(hipGraphLaunch(exec, e->stream));
     return 0;
 }
@@ -2817,7 +2833,7 @@ static int launch_verify_tree(qie_batch* b, int seq, int M, const qie_sampling* 
     if (!e->opts.use_graph) return enqueue_verify_tree(b, seq, M, smp);
     const bool greedy = is_greedy(smp), entries = any_entry(b, seq, 1);
     for (const auto& g : b->v_graphs)
-        if (g.seq == -2 - seq && g.M == M && g.entries == entries &&
+        if (g.seq == -2 - seq && g.M == M && g.entries == entries && g.all_mode == all_mode(b, smp) &&
             (entries || (g.greedy == greedy && (greedy || same_sampling(g.smp, smp))))) {
             QIE_HIP(hipGraphLaunch(g.exec, e->stream));
             return 0;
@@ -2829,7 +2845,7 @@ static int launch_verify_tree(qie_batch* b, int seq, int M, const qie_sampling* 
     hipGraphExec_t exec = nullptr;
     QIE_TRY(capture_graph(e, "qie_verify_tree: ", [&] { return enqueue_verify_tree(b, seq, M, smp); }, &exec));
     b->v_captures++;
-    b->v_graphs.push_back({-2 - seq, M, entries, greedy, smp ? *smp : qie_sampling{1, 0.f, 1.f, 0}, exec});
+    b->v_graphs.push_back({-2 - seq, M, entries, greedy, smp ? *smp : qie_sampling{1, 0.f, 1.f, 0}, exec, {}, false, all_mode(b, smp)});
     QIE_HIP(hipGraphLaunch(exec, e->stream));
     return 0;
 }
@@ -2965,6 +2981,7 @@ static int launch_verify_batch(qie_batch* b, const qie_row_segs& t, const qie_sa
     const bool greedy = is_greedy(smp), entries = any_entry_segs(b, t), all = entries && every_entry_segs(b, t);
     for (const auto& g : b->v_graphs)
         if (g.seq == -1 && same_segs(g.segs, t) && g.entries == entries && g.all_entries == all &&
+            g.all_mode == all_mode(b, smp) &&
             (all || (g.greedy == greedy && (greedy || same_sampling(g.smp, smp))))) {
             QIE_HIP(hipGraphLaunch(g.exec, e->stream));
             return 0;
@@ -2975,7 +2992,7 @@ static int launch_verify_batch(qie_batch* b, const qie_row_segs& t, const qie_sa
     }
     hipGraphExec_t exec = nullptr;
     QIE_TRY(capture_graph(e, "qie_verify_batch: ", [&] { return enqueue_verify_batch(b, t, smp); }, &exec));
-    b->v_graphs.push_back({-1, t.row0[t.n], entries, greedy, smp ? *smp : qie_sampling{1, 0.f, 1.f, 0}, exec, t, all});
+    b->v_graphs.push_back({-1, t.row0[t.n], entries, greedy, smp ? *smp : qie_sampling{1, 0.f, 1.f, 0}, exec, t, all, all_mode(b, smp)});
     b->v_captures++;
     QIE_HIP(hipGraphLaunch(exec, e->stream));
     return 0;

@@ -19,6 +19,13 @@ int raise_dynamic_lds(const void* fn, size_t bytes);
 // threads, shm); `fallback` where the query fails.  Thread-safe.
 int resident_blocks_per_cu(const void* fn, int threads, size_t shm, int fallback);
 
+// qie_sample_rows (row_slot_dev null) or qie_sample_rows_mapped for a caller that knows whether
+// a row of the launch can be in ALL mode (top_k == QIE_TOP_K_ALL in its entry or in the
+// fallback): all_mode false leaves the two whole-vocabulary launches out — a row in ALL mode
+// would then get no id.  The public forms pass true: their table is device data.
+int sample_rows_launch(const qie_sample_rows_args* a, const int32_t* row_slot_dev, const int32_t* tail_off_dev,
+                       bool all_mode, void* stream);
+
 // Runtime epilogue -> compile-time constant: calls f(std::integral_constant<int, E>) for the E
 // among EPIS that equals `epi`, the LAST of EPIS otherwise (the sites' former `default:`).
 // Only the listed epilogues are instantiated.

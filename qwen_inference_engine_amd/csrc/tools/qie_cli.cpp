@@ -5,8 +5,10 @@
 //   qie_cli [--model Qwen2-7B|Qwen2-0.5B|Qwen2-72B|Qwen3-14B] [--numerics ref|hf]
 //           [--weights weights.bin --meta meta_data.txt | --synthetic SEED]
 //           [--prompt 151643,785,... | --prompt-file ids.txt] [--gen N] [--greedy] [--device D]
-//           [--no-graph] [--stream] [--page-tokens T]
+//           [--no-graph] [--stream] [--page-tokens T] [--top-k K [--temperature T] [--top-p P]]
 //
+// --top-k K samples every step under {K, T (default 1), P (default 1), seed 1234 + step} instead
+// of the reference's schedule; K = -1 (QIE_TOP_K_ALL) draws from the whole vocabulary.
 // --prompt-file: token ids separated by commas / whitespace (the reference hard-codes them,
 // iengine.cu:325, after tokenising with temp.py:4); --stream prints each id as it is
 // generated (the reference prints per step, qwen_main.cu:392-398); --page-tokens runs on a
@@ -51,6 +53,8 @@ int main(int argc, char** argv) {
     std::vector<int> prompt = {151643, 785, 4767, 315, 279, 3639, 4180, 374};
     long seed = -1;
     int gen = 32, device = 0, greedy = 0, graph = 1, stream = 0, page_tokens = 0;
+    qie_sampling user{0, 1.0f, 1.0f, 1234};
+    bool user_set = false;
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto next = [&]() -> std::string {
@@ -68,6 +72,9 @@ int main(int argc, char** argv) {
         else if (a == "--no-graph") graph = 0;
         else if (a == "--stream") stream = 1;
         else if (a == "--page-tokens") page_tokens = std::atoi(next().c_str());
+        else if (a == "--top-k") { user.top_k = std::atoi(next().c_str()); user_set = true; }
+        else if (a == "--temperature") user.temperature = (float)std::atof(next().c_str());
+        else if (a == "--top-p") user.top_p = (float)std::atof(next().c_str());
         else if (a == "--prompt-file") {
             std::ifstream f(next());
             if (!f) { std::fprintf(stderr, "cannot read %s\n", argv[i]); return 2; }
@@ -129,9 +136,14 @@ int main(int argc, char** argv) {
     if (brc) { std::fprintf(stderr, "%s\n", qie_last_error()); return 1; }
     batch_metadata* seq = create_new_sequence(0, prompt.data(), (int)prompt.size(), b, 0);
     qie_sampling g{1, 1.0f, 1.0f, 0};
+    if (user_set && (user.top_k < QIE_TOP_K_ALL || user.top_k == 0)) {
+        std::fprintf(stderr, "--top-k: a count >= 1, or -1 for the whole vocabulary\n");
+        return 2;
+    }
+    const qie_sampling* smp = greedy ? &g : user_set ? &user : nullptr;
     std::vector<int> out;
     auto tp0 = std::chrono::steady_clock::now();
-    int tok = llm(seq, greedy ? &g : nullptr);
+    int tok = llm(seq, smp);
     auto tp1 = std::chrono::steady_clock::now();
     if (config().error) return 1;
     out.push_back(tok);
@@ -140,7 +152,7 @@ int main(int argc, char** argv) {
     seq->generated_token = tok;
     seq->state = decode;
     while ((int)out.size() < gen && tok != kRefEos) {
-        tok = llm(seq, greedy ? &g : nullptr);
+        tok = llm(seq, smp);
         if (config().error) return 1;
         out.push_back(tok);
         if (stream) { std::printf("%d\n", tok); std::fflush(stdout); }

@@ -26,6 +26,9 @@ REF_EOS = 151645                                                    # qwen_main.
 
 @dataclasses.dataclass
 class Sampling:
+    """The call's sampling (qie_sampling).  top_k <= 1 or temperature <= 0 is greedy; top_k >= 2
+    draws from the min(top_k, 256) best; top_k=-1 (QIE_TOP_K_ALL) draws from the whole
+    vocabulary under temperature and top_p alone."""
     top_k: int = 1
     temperature: float = 1.0
     top_p: float = 1.0
@@ -45,7 +48,8 @@ class SlotSampling:
     """One slot's own sampling entry (qie_slot_sampling; Batch.set_sampling): the four values of
     Sampling, min-p, the repetition / presence / frequency penalties over the window
     [max(penalty_start, q + 1 - penalty_last_n), q] of the slot's token history, and a logit
-    bias per token id (-inf bans the token)."""
+    bias per token id (-inf bans the token).  top_k=-1 (QIE_TOP_K_ALL) with temperature > 0
+    samples the slot from the whole vocabulary: temperature, top_p and min_p, no top-k cut."""
     top_k: int = 1
     temperature: float = 1.0
     top_p: float = 1.0

@@ -12,6 +12,10 @@
    qie_sampling (k = 50, T = 0.7: the path without entries) and through entries with the same
    values plus penalties over the last 4,096 ids.  hipEvents on the engine's stream around STEPS
    replays of the captured step, every window from the same positions; alternated, REPS times.
+3. --all -> profiles/sample_all.json: the whole-vocabulary mode (top_k = -1), V = 151,936, M = 1, 8 and
+   16, T = 1, top-p 0.95, against the top_k = 256 launches on the same rows, through qie_sample and
+   through entries without penalties and with a 4,096-id window; and the decode step of 2. with the
+   call's top_k = 256 sampling alone and with slot 0 under an ALL-mode entry.
 """
 import argparse
 import ctypes as C
@@ -98,7 +102,8 @@ def dmem(lib, keep, a):
     return p
 
 
-def op_table(lib, hip, M):
+def op_table(lib, hip, M, all_mode=False):
+    V = 151936 if all_mode else globals()["V"]
     r = np.random.default_rng(M)
     keep = []
     st = C.c_void_p()
@@ -135,6 +140,21 @@ def op_table(lib, hip, M):
              "rows_neutral": rows_call(table_of(0))}
     for w in (512, 4096, 32768):
         calls[f"rows_window_{w}"] = rows_call(table_of(w))
+    if all_mode:
+        def sample_call(k):
+            c = Q.Sampling(top_k=k, temperature=1.0, top_p=0.95, seed=1234).to_c()
+            return lambda: _lib.check(lib.qie_sample(d_lg, M, V, V, C.byref(c), d_step, d_ids, d_ws, st), "qie_sample")
+
+        def entry_table(k, window):
+            pen = dict(repetition_penalty=1.1, presence_penalty=0.2, frequency_penalty=0.1, penalty_last_n=window) if window else {}
+            arr = (_lib.SlotSamplingC * M)(*[Q.SlotSampling(top_k=k, temperature=1.0, top_p=0.95, seed=1234, **pen).to_c()
+                                             for _ in range(M)])
+            return dmem(lib, keep, np.frombuffer(bytes(arr), np.uint8).copy())
+
+        calls = {"qie_sample_top256": sample_call(256), "qie_sample_all": sample_call(-1)}
+        for k, name in ((256, "top256"), (-1, "all")):
+            calls[f"rows_{name}"] = rows_call(entry_table(k, 0))
+            calls[f"rows_{name}_window_4096"] = rows_call(entry_table(k, 4096))
     graphs = {}
     for name, call in calls.items():
         call()                                    # outside a capture first: LDS limits, code objects
@@ -158,12 +178,14 @@ def op_table(lib, hip, M):
 
 
 # ------------------------------------------------------------------------------- 2. the decode step
-def step_table(hip, n_layers):
+def step_table(hip, n_layers, all_mode=False):
     spec = S.QWEN2_7B if n_layers is None else S.QWEN2_7B.replace(n_layers=n_layers)
     B, max_ctx = 8, CTX + 256
     eng = Q.Engine(spec, max_ctx=max_ctx, weight_fp8=True).init_synthetic(W.SynthParams(seed=0))
     b = eng.batch(B, max_ctx, page_tokens=128)
     smp = Q.Sampling(top_k=50, temperature=0.7, seed=1234)
+    if all_mode:
+        smp = Q.Sampling(top_k=256, temperature=1.0, top_p=0.95, seed=1234)
     r = np.random.default_rng(5)
     toks = []
     for s in range(B):
@@ -173,19 +195,23 @@ def step_table(hip, n_layers):
     entry = Q.SlotSampling(top_k=50, temperature=0.7, seed=1234, repetition_penalty=1.1, presence_penalty=0.2,
                            frequency_penalty=0.1, penalty_last_n=4096)
     st = eng.stream
+    names = ("call_sampling", "entries_window_4096")
+    if all_mode:
+        names = ("call_top256", "slot0_all_mode")
+        entry = Q.SlotSampling(top_k=-1, temperature=1.0, top_p=0.95, seed=1234)
 
     def window(entries):
         for s in range(B):
-            b.set_sampling(s, entry if entries else None)
+            b.set_sampling(s, entry if entries and (s == 0 or not all_mode) else None)
             b.set_position(s, CTX - 1, toks[s])   # every window decodes from the same positions
         b.decode(4, smp, want_ids=False)           # (re-)captures the step, warm
         eng.sync()
         ms = hip.elapsed_ms(st, lambda: _lib.check(eng.lib.qie_decode(b.h, STEPS, C.byref(smp.to_c()), None), "qie_decode"))
         return ms * 1e3 / STEPS
 
-    cells = {"call_sampling": [], "entries_window_4096": []}
+    cells = {names[0]: [], names[1]: []}
     for rep in range(REPS + 1):                    # repetition 0 is dropped
-        for name, entries in (("call_sampling", False), ("entries_window_4096", True)):
+        for name, entries in ((names[0], False), (names[1], True)):
             us = window(entries)
             if rep:
                 cells[name].append(us)
@@ -201,9 +227,23 @@ def main():
     ap.add_argument("--out", default=OUT)
     ap.add_argument("--layers", type=int, default=None, help="fewer layers than Qwen2-7B's 28 (rehearsal)")
     ap.add_argument("--skip-step", action="store_true")
+    ap.add_argument("--all", action="store_true", help="the whole-vocabulary mode -> profiles/sample_all.json")
     args = ap.parse_args()
     lib = _lib.load()
     hip = Hip()
+    if args.all:
+        out = args.out if args.out != OUT else os.path.join(ROOT, "profiles", "sample_all.json")
+        doc = {"operator": {"V": 151936, "temperature": 1.0, "top_p": 0.95, "unit": "us per call",
+                            "method": "hipEvents around %d replays of a hipGraph of %d back-to-back calls; %d alternated "
+                                      "repetitions: median, [min, max]" % (REPLAYS, INNER, REPS),
+                            **{"M%d" % M: op_table(lib, hip, M, True) for M in (1, 8, 16)}}}
+        if not args.skip_step:
+            doc["decode_step"] = {"model": "Qwen2-7B widths, %s layers, fp8 weights, B = 8, paged KV, context %d, T = 1, "
+                                           "top-p 0.95" % (args.layers or 28, CTX), "unit": "us per step",
+                                  **step_table(hip, args.layers, True)}
+        with open(out, "w") as f:
+            json.dump(doc, f, indent=1)
+        return
     doc = {"operator": {"V": V, "k": 50, "temperature": 0.7, "unit": "us per call",
                         "method": "hipEvents around %d replays of a hipGraph of %d back-to-back calls; %d alternated "
                                   "repetitions: median, [min, max]" % (REPLAYS, INNER, REPS),
