@@ -169,7 +169,15 @@ void qie_engine_destroy(qie_engine* e);
 
 /* ------------------------------------------------------------------ batch
  * B independent sequences decoded together (weights streamed once per step).
- * KV cache [B][L][nkv][max_ctx][hd] bf16; token history [B][max_ctx]. */
+ * KV cache [B][L][nkv][max_ctx][hd] bf16; token history [B][max_ctx].
+ * 1 <= B <= 64 (qie_batch_create and qie_batch_create_paged).  Up to 16 slots the decode step
+ * launches what it always launched (the M <= 16 linear kernels).  More than 16 slots run the four
+ * layer projections on the 17..64-row kernel (QIE_LINEAR_ROWS64, qie_ops.h) and the
+ * head in pieces of 16 rows; such a batch is refused (-22, before anything is allocated) on a
+ * weight_fp4 engine, on an engine with tp_comm / comm_always, and where a projection's shape is
+ * outside that kernel (K % 64, segments of whole 16-row tiles).  qie_batch_set_decode_mode(1) stays
+ * B = 1 and mode 2 stays B <= 8 (-22 otherwise); verify, ragged and prefill-batch calls keep their
+ * own limits (8 segments, 16 rows) on any B. */
 int qie_batch_create(qie_engine* e, int32_t batch, int32_t max_ctx, qie_batch** out);
 void qie_batch_destroy(qie_batch* b);
 

@@ -595,6 +595,26 @@ int qie_debug_fp8_decode_bf16(uint16_t* out_dev);
  * order); no float atomics, two runs bit-identical, row m independent of M.  No bf16 weight is
  * written anywhere: an engine can keep the codes alone (qie_engine_opts.weight_fp4 = 2). */
 #define QIE_LINEAR_FP4_GEMM 256
+/* QIE_LINEAR_ROWS64: the decode projection of 17 <= M <= 64 rows (k_decode_rows64.hip, DESIGN.md
+ * §26) — a weight-streaming MFMA kernel that reads every weight byte once per launch and feeds it
+ * to all M rows, instead of the prefill GEMM that M > 16 takes without the flag.  Opt-in: without
+ * the bit every launch plans and computes as before.  The engine sets it on the four layer
+ * projections of the decode step of a batch of more than 16 slots, and nowhere else.
+ *   weights:   bf16 [N, K]; QIE_LINEAR_FP8 (plain); QIE_LINEAR_FP8 | QIE_LINEAR_FP8_T16 (tiled);
+ *   epilogues: QIE_EPI_STORE (up to three segments, biases), QIE_EPI_RESIDUAL, QIE_EPI_SWIGLU;
+ *   shapes:    K % 64 == 0, N <= 32,768, ldx % 8 == 0; a segment that another follows (tiled
+ *              weights: every segment) is whole 16-row tiles; each segment under 2^31 bytes.
+ * Everything else returns -22 and launches nothing: M outside [17, 64], the MXFP4 / fp8-activation /
+ * tile-override flags, QIE_EPI_F32, a fused norm (norm_w: the kernel has none, the caller norms the
+ * rows first), argmax_keys.  Long K is split over workgroups; the split needs a per-stream
+ * workspace (32 MiB) that cannot be allocated during a graph capture: the first such launch of a
+ * stream (or qie_batch_create of more than 16 slots) makes it.
+ * Numerics: products of the bf16 rows and the exactly dequantised bf16 weights, fp32 sums per K
+ * part in k order (64-column units, two 32-product MFMA steps each), parts added in part order by
+ * the last arriving workgroup, times the fp8 row scale, then the epilogue's roundings.  No float
+ * atomics and no waiting on another workgroup: two runs are bit-identical.  Rows past M - 1 of x
+ * are never read. */
+#define QIE_LINEAR_ROWS64 512
 int64_t qie_fp4_weight_bytes(int64_t rows, int64_t cols);
 int qie_quantize_fp4(const void* w_bf16, int64_t rows, int64_t cols, void* out, void* stream);
 int qie_quantize_fp4_host(const void* w_bf16, int64_t rows, int64_t cols, void* out);

@@ -29,6 +29,7 @@ QIE_LINEAR_ACT_FP8 = 32
 QIE_LINEAR_FP4 = 64
 QIE_LINEAR_FP4_T16 = 128
 QIE_LINEAR_FP4_GEMM = 256   # with QIE_LINEAR_FP4: M > 16 rows run the MXFP4 prefill GEMM
+QIE_LINEAR_ROWS64 = 512     # 17 <= M <= 64 rows on the weight-streaming decode kernel (k_decode_rows64.hip)
 QIE_ATTN_PREROPED = 0x100   # qie_attention_decode numerics flag: q / new k arrive rotated
 QIE_VERIFY_MAX_ROWS = 16    # qie_verify: the current token + at most 15 drafts
 QIE_SCORE_UNFUSED = 1       # qie_score flag: the <= 16-row head launches + qie_logprob_rows

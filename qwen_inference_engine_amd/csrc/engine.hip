@@ -16,6 +16,7 @@
 // device memory so the graph replays without host edits.
 #include "qie_common.hpp"
 #include "linear_plan.hpp"
+#include "rows64_plan.hpp"
 #include "launch_util.hpp"
 #include "../../include/qie/qie_engine.h"
 #include "qie_index.hpp"
@@ -36,6 +37,7 @@ bool dec8_applies(const qie_linear_args* a);
 int dec8_reserve(hipStream_t st);
 bool dec4_applies(const qie_linear_args* a);
 int dec4_reserve(hipStream_t st);
+int rows64_reserve(hipStream_t st);
 bool persist_supported(const qie_model_spec& s, int B, int tp, bool fp8, bool fp4, bool paged, int ncu, const char** why);
 size_t persist_attn_table_bytes(int n_layers);
 int persist_attn_table(const qie_model_spec& s, const qie_layer_weights* h_layers, const void* qkv_scratch,
@@ -794,6 +796,7 @@ static int row_parallel(qie_batch* b, qie_linear_args& a, uint16_t* x, float* pa
 // The decision (qie_batch_time_kernel applies it without launching a norm) ...
 static bool prenorm_applies(const qie_linear_args& a) {
     static const int on = dev_env("QIE_PRENORM", 1);
+    if (a.flags & QIE_LINEAR_ROWS64) return a.norm_w != nullptr;   // the 17..64-row kernel has no fused norm
     if (!on || a.M < 2 || a.M > 16 || !a.norm_w) return false;
     if (a.flags & QIE_LINEAR_FP4) return false;   // the MXFP4 kernel fuses the norm at every M it takes
     return !dec8_applies(&a) || dev_env("QIE_DEC8_PRENORM", 0) != 0;   // the fp8 batched-decode kernel fuses the norm
@@ -936,6 +939,14 @@ struct LayerPath {
     InputForm in;
 };
 static LayerPath decode_path(const qie_engine* e) { return LayerPath{e->layers.data(), proj_flags(e), InputForm::Decode}; }
+// the decode step of a batch: more than kRows16 slots run their four projections on the
+// 17..64-row kernel (QIE_LINEAR_ROWS64, k_decode_rows64.hip); up to 16 exactly as decode_path
+constexpr int kRows16 = 16;
+static LayerPath decode_step_path(const qie_batch* b) {
+    LayerPath p = decode_path(b->e);
+    if (b->B > kRows16) p.flags |= QIE_LINEAR_ROWS64;
+    return p;
+}
 
 // input stage, then the launch: QKV and gate/up as built ...
 static int run_proj(qie_batch* b, qie_linear_args a, InputForm in, const LayerRows& r,
@@ -990,7 +1001,7 @@ static int attend_decode(qie_batch* b, int l, void* out) {
 
 static int enqueue_layer_decode(qie_batch* b, int l) {
     qie_engine* e = b->e;
-    const LayerPath p = decode_path(e);
+    const LayerPath p = decode_step_path(b);
     const qie_layer_weights& L = p.layers[l];
     const LayerRows r = layer_rows(b->dec, b->B, 1);
     QIE_TRY(run_proj(b, qkv_args(e, L, p.flags, r), p.in, r, decode_qkv_extras(b)));
@@ -1174,9 +1185,15 @@ static int enqueue_head(qie_batch* b, const uint16_t* x, int64_t ldx, int m0, in
     const qie_model_spec& s = e->spec;
     hipStream_t st = e->stream;
     // a slot's position is its pending token's: the window's last position
-    const EntryRows er{m0, 1, b->dec.pos + m0, nullptr, nullptr};
     const bool entries = any_entry(b, m0, M);
-    QIE_TRY(enqueue_head_rows(b, x, ldx, M, smp, head_bufs(b->dec, m0, b->e->sh.vocab), entries ? &er : nullptr));
+    // more than 16 rows (the decode step of a large batch): the head launch in pieces of <= 16 rows,
+    // every piece with its rows' own logits / keys / ids; one finalisation over all of them
+    for (int p0 = 0; p0 < M; p0 += kRows16) {
+        const int mp = std::min(kRows16, M - p0);
+        const EntryRows er{m0 + p0, 1, b->dec.pos + m0 + p0, nullptr, nullptr};
+        QIE_TRY(enqueue_head_rows(b, x + (int64_t)p0 * ldx, ldx, mp, smp, head_bufs(b->dec, m0 + p0, b->e->sh.vocab),
+                                  entries ? &er : nullptr));
+    }
     const bool greedy = !entries && is_greedy(smp);
     hipLaunchKernelGGL(finalize_kernel, dim3(M), dim3(256), 0, st, m0, greedy ? b->dec.keys : nullptr,
                        b->dec.ids, b->dec.ids, b->dec.pos, b->dec.step, b->dec.hist, b->max_ctx,
@@ -2079,11 +2096,37 @@ int qie_batch_prefix_drop(qie_batch* b, qie_kv_prefix* p) {
     return fail(-22, "qie_batch_prefix_drop: not an open handle of this batch");
 }
 
+// A batch of more than 16 slots decodes its projections on the 17..64-row kernel: what that step
+// does not cover is refused here, naming the reason
+static int rows64_batch_check(const qie_engine* e, int batch) {
+    QIE_REQUIRE(!e->fp4, "qie_batch_create: B = %d: weight_fp4 engines decode at most 16 slots (the MXFP4 kernel reads "
+                         "M <= 16 rows)", batch);
+    QIE_REQUIRE(!e->comm && !e->opts.tp_comm && !e->opts.comm_always && e->sh.tp == 1,
+                "qie_batch_create: B = %d: engines with tp_comm / comm_always decode at most 16 slots", batch);
+    const LayerRows r{batch};
+    const qie_layer_weights& L = e->layers[0];
+    const int fl = proj_flags(e) | QIE_LINEAR_ROWS64;
+    qie_linear_args o = o_args(e, L, fl, r), down = down_args(e, L, fl, r);
+    o.epilogue = down.epilogue = QIE_EPI_RESIDUAL;
+    const qie_linear_args all[] = {qkv_args(e, L, fl, r), o, gate_up_args(e, L, fl, r), down};
+    const char* names[] = {"QKV", "O", "gate/up", "down"};
+    for (int i = 0; i < 4; i++) {
+        qie_linear_args a = all[i];
+        a.norm_w = nullptr;   // the step norms the rows first (prenorm_applies)
+        const Rows64Plan pl = plan_rows64(a, device_cu_count());
+        QIE_REQUIRE(pl.error == Rows64Error::None,
+                    "qie_batch_create: B = %d: the %s projection (K=%lld N=%lld) is outside the 17..64-row decode "
+                    "kernel: it takes %s", batch, names[i], (long long)a.K, (long long)a.N, rows64_error_text(pl.error));
+    }
+    return 0;
+}
+
 static int batch_create(qie_engine* e, int32_t batch, int32_t max_ctx, int32_t page_tokens, int32_t n_pages,
                         qie_batch** out) {
     QIE_REQUIRE(e && out && batch > 0 && batch <= kMaxBatchSlots && max_ctx > 1,
                 "qie_batch_create: bad arguments (B <= %d)", kMaxBatchSlots);
     QIE_REQUIRE(e->have_weights, "qie_batch_create: engine has no weights");
+    if (batch > kRows16) QIE_TRY(rows64_batch_check(e, batch));   // before anything is allocated
     QIE_REQUIRE(max_ctx <= e->rope_rows, "qie_batch_create: max_ctx %d > engine max_ctx %d", max_ctx, e->rope_rows);
     const qie_model_spec& s = e->spec;
     qie_batch* b = new qie_batch();
@@ -2149,6 +2192,7 @@ static int batch_create(qie_engine* e, int32_t batch, int32_t max_ctx, int32_t p
         // the fp8 batched-decode split-K workspace of this stream, before any graph capture
         if (e->fp8 && (batch >= 2 || e->fp8_t16)) QIE_TRY(dec8_reserve(e->stream));
         if (e->fp4) QIE_TRY(dec4_reserve(e->stream));   // (the MXFP4 kernel has no other kernel to decline to)
+        if (batch > kRows16) QIE_TRY(rows64_reserve(e->stream));   // the 17..64-row kernel's split-K workspace
         return 0;
     };
     if (const int rc = make()) {
@@ -3099,7 +3143,8 @@ int qie_batch_set_decode_mode(qie_batch* b, int32_t mode) {
                     "qie_batch_set_decode_mode: mode 2 is not available on an engine with tp_comm / comm_always");
         QIE_REQUIRE(e->spec.head_dim == 64 || e->spec.head_dim == 128,
                     "qie_batch_set_decode_mode: mode 2 needs head_dim 64 or 128 (got %d)", (int)e->spec.head_dim);
-        static_assert(kMaxBatchSlots <= 8, "qie_attention_decode_shared serves at most 8 rows: every batch must fit");
+        QIE_REQUIRE(b->B <= 8, "qie_batch_set_decode_mode: mode 2 (shared-prefix decode attention) serves at most 8 "
+                               "slots (B = %d)", b->B);
         if (!b->sh_ws || !b->d_share) {
             // both or none: a failed allocation leaves the batch in its mode with nothing held
             hipFree(b->sh_ws);
@@ -3359,7 +3404,7 @@ int qie_batch_time_kernel(qie_batch* b, int32_t which, int32_t iters, double* av
     HeadBufs hb = head_bufs(b->dec, 0, b->e->sh.vocab);
     hb.logits = scratch;
     hb.keys = (unsigned long long*)(((uintptr_t)(scratch + B * V) + 7) & ~(uintptr_t)7);
-    const LayerPath p = decode_path(e);
+    const LayerPath p = decode_step_path(b);
     const int nl = s.n_layers;
     auto run = [&](int i) -> int {
         const int l = which == 4 || nl == 1 ? 0 : 1 + i % (nl - 1);
@@ -3369,7 +3414,7 @@ int qie_batch_time_kernel(qie_batch* b, int32_t which, int32_t iters, double* av
                             : which == 1 ? down_args(e, L, p.flags, r)
                             : which == 2 ? qkv_args(e, L, p.flags, r)
                             : which == 3 ? o_args(e, L, p.flags, r)
-                                         : head_args(e, b->dec.x, H, (int)B, true, hb);
+                                         : head_args(e, b->dec.x, H, (int)std::min<int64_t>(B, kRows16), true, hb);   // (the head runs in pieces of <= 16 rows)
         if (which == 1 || which == 3) {
             a.y = scratch;
             a.epilogue = QIE_EPI_STORE;

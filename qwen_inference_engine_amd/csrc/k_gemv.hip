@@ -1159,6 +1159,7 @@ static int launch_skinny(const GemvParams& p, const LinearPlan& pl, hipStream_t 
 int gemm(const qie_linear_args* a, hipStream_t st);
 int dec8_linear(const qie_linear_args* a, const LinearPlan& pl, hipStream_t st, bool* done);
 int dec4_linear(const qie_linear_args* a, const LinearPlan& pl, hipStream_t st);
+int rows64_linear(const qie_linear_args* a, bool extras, hipStream_t st);
 
 // true when the MXFP4 kernel takes this projection (the engine then skips its separate norm)
 bool dec4_applies(const qie_linear_args* a) {
@@ -1299,6 +1300,8 @@ int linear(const qie_linear_args* a, const LinearExtras& ex, hipStream_t st) {
                      ex.rope.pos && ex.rope.cs && ex.rope.sn),
                 "qie_linear: fused RoPE: M = 1 STORE projections only");
     if (ex.push_taken) *ex.push_taken = false;
+    // QIE_LINEAR_ROWS64: the 17..64-row decode kernel (k_decode_rows64.hip) takes the launch or names the refusal
+    if (a->flags & QIE_LINEAR_ROWS64) return rows64_linear(a, ex.rope.pos || ex.rope.rows || ex.push, st);
     // QIE_LINEAR_FP4_GEMM: M > 16 on fp4 weights runs gemm4_kernel (k_gemm_fp4.hip); M <= 16 as without it
     if (a->flags & QIE_LINEAR_FP4_GEMM) {
         QIE_REQUIRE(a->flags & QIE_LINEAR_FP4, "qie_linear: QIE_LINEAR_FP4_GEMM needs QIE_LINEAR_FP4 weights (flags %d)", a->flags);

@@ -20,7 +20,7 @@
 
 namespace qie {
 
-constexpr int kMaxBatchSlots = 8;   // the most slots a batch can have: a reservation's capacity
+constexpr int kMaxBatchSlots = 64;  // the most slots a batch can have: a reservation's capacity
 
 struct PagePool {
     int page_tokens = 0, max_pages = 0, n_pages = 0, n_slots = 0;

@@ -10,6 +10,7 @@
 
 #include "gemm_plan.hpp"
 #include "linear_plan.hpp"
+#include "rows64_plan.hpp"
 
 namespace qie {
 
@@ -50,12 +51,26 @@ inline std::string format_gemm_plan(const GemmPlan& g, int epi) {
     return s;
 }
 
+// QIE_LINEAR_ROWS64: the 17..64-row decode kernel's plan (rows64_plan.hpp), or its refusal
+inline std::string format_rows64_plan(const Rows64Plan& p) {
+    std::string s;
+    if (p.error != Rows64Error::None) {
+        plan_appendf(s, "rows64 error %d", (int)p.error);
+        return s;
+    }
+    plan_appendf(s, "rows64_kernel<%s,%d,%d> tiles=%d col_blocks=%d chunks=%d parts=%d cpp=%d grid=%u threads=%d lds=%zu ws=%zu",
+                 epi_name(p.epi), p.wt, p.mt, p.n_tiles, p.col_blocks, p.chunks, p.parts, p.cpp, p.grid, p.threads,
+                 p.lds_bytes, p.ws_bytes);
+    return s;
+}
+
 // One line (no newline) for the launch qie_linear makes of `a`: its routing (fp8 activations and
 // M > 16 straight to the GEMM), then plan_linear.  resident_blocks: what the occupancy query
 // returns for the launch; <= 0 where it is not known, and a grid that depends on it prints as
 // "grid=?".
 inline std::string format_linear_plan(const qie_linear_args& a, const Knobs& k, const GemmKnobs& gk, int cus,
                                       int resident_blocks, bool allow_split = true) {
+    if (a.flags & QIE_LINEAR_ROWS64) return format_rows64_plan(plan_rows64(a, cus));
     // fp4 weights: plan_linear's at every M, but for M > 16 under QIE_LINEAR_FP4_GEMM (qie_linear's routing)
     const bool g4 = (a.flags & QIE_LINEAR_FP4) && (a.flags & QIE_LINEAR_FP4_GEMM) && a.M > 16;
     const bool fp4 = (a.flags & (QIE_LINEAR_FP4 | QIE_LINEAR_FP4_T16)) != 0 && !g4;

@@ -13,7 +13,7 @@
 //   plan slot lo hi         the writers' planning step, nothing changes
 //                           -> plan first last n_private copy_index copy_rows grow fresh
 //   write slot lo hi        a one-span reservation                             -> cow OLD NEW | fail 28
-//   reserve slot lo hi [slot lo hi ...]   the writers' reservation over up to kMaxBatchSlots spans
+//   reserve slot lo hi [slot lo hi ...]   the writers' reservation over up to 8 spans (kCmdMaxSpans)
 //   restart slot len [slot len ...]       the same for slots that begin new sequences of len tokens
 //                           -> ok NEED [cow SLOT INDEX ROWS OLD NEW]... | fail 28 need N free F
 //   release slot
@@ -28,6 +28,11 @@
 #include "../page_pool.hpp"
 
 using namespace qie;
+
+// A command line names at most 8 spans, as it always has; the pool itself takes a reservation of
+// kMaxBatchSlots spans (a prefill of every slot of a 64-slot batch).
+constexpr size_t kCmdMaxSpans = 8;
+static_assert(kCmdMaxSpans <= (size_t)kMaxBatchSlots, "a command's spans fit a reservation");
 
 int main() {
     PagePool p;
@@ -103,7 +108,7 @@ int main() {
             std::vector<long long> v;
             while (in >> a) v.push_back(a);
             const size_t n = v.size() / per;
-            bool ok = in.eof() && n >= 1 && v.size() == n * per && n <= (op == "write" ? 1 : (size_t)kMaxBatchSlots);
+            bool ok = in.eof() && n >= 1 && v.size() == n * per && n <= (op == "write" ? 1 : kCmdMaxSpans);
             PagePool::Span spans[kMaxBatchSlots];
             for (size_t i = 0; ok && i < n; i++) {
                 const long long* f = &v[i * per];

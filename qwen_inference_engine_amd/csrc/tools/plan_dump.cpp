@@ -1,6 +1,7 @@
 // plan_dump — prints the launch plan of linear layers without a GPU: M <= 16 rows by
 // plan_linear (linear_plan.hpp); more rows, rows that plan hands to the GEMM, and fp8 activations
-// (QIE_LINEAR_ACT_FP8) at any M by plan_gemm (gemm_plan.hpp), in plan_format.hpp's wording.
+// (QIE_LINEAR_ACT_FP8) at any M by plan_gemm (gemm_plan.hpp), rows that carry QIE_LINEAR_ROWS64 by
+// plan_rows64 (rows64_plan.hpp), in plan_format.hpp's wording.
 // Plain host program (`make plan_dump`); tests/test_linear_plan_cpu.py and
 // tests/test_gemm_plan_cpu.py compare its output with tables derived by hand,
 // tests/test_linear_variants_cpu.py with the instantiations tests/linear_cases.py declares.

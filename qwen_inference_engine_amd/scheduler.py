@@ -360,6 +360,11 @@ class ContinuousBatcher:
             if off:
                 return {r.rid: self.batch.append(r.slot, ids, off, self.sampling)}
             return {r.rid: self.batch.prefill(r.slot, ids, self.sampling)}
+        if len(pieces) > VERIFY_MAX_SEGS:   # a ragged call takes QIE_RAGGED_MAX_SEGS segments: more slots, more calls
+            first: Dict[int, int] = {}
+            for i in range(0, len(pieces), VERIFY_MAX_SEGS):
+                first.update(self._prefill_pieces(pieces[i:i + VERIFY_MAX_SEGS]))
+            return first
         toks = self.batch.prefill_ragged(ragged_group(pieces), self.sampling)
         by_slot = {r.slot: r for r, _, _ in pieces}
         return {by_slot[slot].rid: tok for slot, tok in zip(sorted(by_slot), toks)}
